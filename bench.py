@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- k-subgraphs sampled per second on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
                     [--workload c5_er_1m|c2_mutag_b1024|c3_proteins_b8192|c4_qm9_b65536|er_<n>_<cols>_<m>_<k>]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (fresh child processes, before anything
 touches a GPU) and relays rank 0's line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+`--full` adds everything else, after the timed steps: per-kernel HIP-event times and the roofline block, the parity check of
+a reference step against the CPU oracle, the CPU baselines (oracle port, the reference C++ where oracle/_ref exists, all
+cores), the drop-in call, the other workloads, the epsilon sampler, the weak-scaling extra and the placement check of the
+collated batch (N > 1).  `--dump-outputs DIR` writes what the last timed step computed (rank 0's batch; a fixed, seeded
+sample of its rows) as DIR/<name>.npy in float64, so that two builds can be compared output for output.
 
 A *step* is one pass of the hot path over one batch: walk kernel(s) + scan + fill kernel, producing the reference's
 tensors (nodes, edge_index, edge_ptr, edge_src) in HBM from a plan (preprocessed graph batch) that is already resident
@@ -63,6 +70,9 @@ def parse_args(argv=None):
     ap.add_argument("--force-collate", action="store_true", help="run the multi-GPU collation path even with one rank (rehearsal)")
     ap.add_argument("--rehearse", action="store_true", help="N ranks on ONE GPU over gloo (every rank uses cuda:0): exercises the multi-rank control flow "
                     "of this script where only one GPU is at hand; the numbers mean nothing")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements and checks (roofline, CPU baselines, parity against the "
+                    "oracle, other workloads, weak-scaling extra, placement check); off by default: a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs (sampled rows) to DIR/<name>.npy")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -319,7 +329,7 @@ def timed_run(torch, dist, job, steps, warmup, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.perf_counter()
-    job.run_steps(warmup, steps, timed=True)
+    last = job.run_steps(warmup, steps, timed=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -334,7 +344,43 @@ def timed_run(torch, dist, job, steps, warmup, world, dev):
     cms = None
     if job.use_collate and job.cev:
         cms = sum(a.elapsed_time(b) for a, b in job.cev) / len(job.cev)
-    return float(el_t.item()), cms
+    if not job.use_collate:                              # the last timed step's own buffers: (nodes, edge_index, edge_ptr, edge_src)
+        b = (warmup + steps - 1) % job.nsets
+        last = (job.nodes[b], job.eidx[b], job.eptr[b], job.esrc[b])
+    return float(el_t.item()), cms, last
+
+
+DUMP_ROWS = 65536                 # rows of the last step written by --dump-outputs (a fixed, seeded sample of the batch)
+DUMP_BYTES = 60 << 20             # and at most this many bytes in all
+
+
+def dump_outputs(torch, np, out_dir, batch):
+    """--dump-outputs: the batch a caller of the timed path receives -- (nodes [R,k], edge_index [2,>=E], edge_ptr [R+1],
+    edge_src [>=E]) with E = edge_ptr[-1] -- as float64 .npy files (every value is an int64 far below 2**53, so exact).  Rows:
+    a fixed sample (numpy seed 0) of DUMP_ROWS rows, fewer if their edges would pass DUMP_BYTES, in ascending order.
+    Written: rows (sampled row ids), nodes [S,k], edge_ptr [S+1] (the offsets of the sampled rows and the batch's total: they
+    depend on every row's edge count), edge_count [S], edge_index [2,Es] and edge_src [Es] (the sampled rows' edges, row by row)."""
+    nodes, eidx, eptr, esrc = batch
+    R, k = int(nodes.size(0)), int(nodes.size(1))
+    eptr_h = eptr[:R + 1].cpu().numpy()
+    pick = np.random.default_rng(0).permutation(R)[:min(R, DUMP_ROWS)]
+    counts = eptr_h[pick + 1] - eptr_h[pick]
+    row_bytes = 8 * (k + 3 + 3 * counts)                                 # nodes, offset, count, 3 edge values per edge entry
+    keep = int(np.searchsorted(np.cumsum(row_bytes), DUMP_BYTES, side="right"))
+    rows = np.sort(pick[:keep])
+    counts = eptr_h[rows + 1] - eptr_h[rows]
+    starts = eptr_h[rows]
+    ends = np.cumsum(counts)
+    eix = np.repeat(starts - (ends - counts), counts) + np.arange(int(ends[-1]) if len(ends) else 0, dtype=np.int64)
+    dev = nodes.device
+    rows_t, eix_t = torch.from_numpy(rows).to(dev), torch.from_numpy(eix).to(dev)
+    arrays = {"rows": rows, "nodes": nodes.index_select(0, rows_t).cpu().numpy(),
+              "edge_ptr": np.append(starts, eptr_h[R]), "edge_count": counts,
+              "edge_index": eidx.index_select(1, eix_t).cpu().numpy(), "edge_src": esrc.index_select(0, eix_t).cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "rows": int(len(rows)), "of_rows": R, "edge_entries": int(len(eix)), "bytes": sum(8 * int(a.size) for a in arrays.values())}
 
 
 def main():
@@ -442,12 +488,12 @@ def main():
 
     job.run_steps(0, 1)                                   # first touch of every buffer outside the event-timed region
     torch.cuda.synchronize()
-    plan.set_timing(True)
-    elapsed, collate_ms = timed_run(torch, dist, job, args.steps, args.warmup, world, dev)
+    plan.set_timing(args.full)                            # per-kernel HIP events (roofline, per_rank): --full only
+    elapsed, collate_ms, last = timed_run(torch, dist, job, args.steps, args.warmup, world, dev)
     timing = plan.get_timing()
     plan.set_timing(False)
     per_rank = None
-    if use_collate:                                       # every rank's rows and kernel times, for rank 0's line (a collective: before the ranks part)
+    if use_collate and args.full:                         # every rank's rows and kernel times, for rank 0's line (a collective: before the ranks part)
         tm = lambda key: timing[key][0] / max(timing[key][1], 1)     # noqa: E731
         mine = torch.tensor([float(row_count), tm("walk"), tm("scan"), tm("fill"), float(collate_ms or 0.0), float(my_share)], dtype=torch.float64, device=dev)
         every = torch.empty((world, 6), dtype=torch.float64, device=dev)
@@ -457,15 +503,27 @@ def main():
             every.copy_(mine.reshape(1, 6))
         per_rank = [{"rank": r_, "rows": int(v[0]), "walk_ms": round(v[1], 4), "scan_ms": round(v[2], 4), "fill_ms": round(v[3], 4),
                      "collate_ms": round(v[4], 4), "walk_share": int(v[5])} for r_, v in enumerate(every.cpu().tolist())]
-        if job.collator.overflowed():                     # lazy capacity check of the collation (one read-back, after the timed region)
-            raise SystemExit("a step's edge total exceeded the collation capacity: result invalid")
+    if use_collate and job.collator.overflowed():         # lazy capacity check of the collation (one read-back, after the timed region)
+        raise SystemExit("a step's edge total exceeded the collation capacity: result invalid")
+    if args.dump_outputs and rank == 0:                   # rank 0 holds the batch: its own (N = 1) or the collated one
+        dumped = dump_outputs(torch, np, args.dump_outputs, last)
+        log(f"[bench] outputs of step {args.warmup + args.steps - 1} (seed {42 + args.warmup + args.steps - 1}): {dumped}")
+    del last
+
+    if not args.full:
+        if rank == 0:
+            emit(json.dumps(headline(args, world, G, ei, k, total_rows, row_count, elapsed, collate_ms, use_collate, calibration)))
+        if world > 1 or args.force_collate:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     extras = {}
     if world > 1 and args.scaling == "strong" and not args.no_extras:
         # the other scaling mode, short: every rank adds a whole batch (N*B rows per step collated on rank 0)
         wjob = Job(torch, dist, ud, plan, args, G, m * world, k, rank, world, dev, node_bound, ei.shape[1], True, weights)
         wsteps = max(3, args.steps // 2)
-        wel, wcms = timed_run(torch, dist, wjob, wsteps, 2, world, dev)
+        wel, wcms, _ = timed_run(torch, dist, wjob, wsteps, 2, world, dev)
         extras["weak_scaling"] = {"value": round(wjob.total_rows * wsteps / wel, 1), "ms_per_step": round(wel / wsteps * 1e3, 4), "steps": wsteps,
                                   "global_rows": wjob.total_rows, "rows_per_gpu": wjob.row_count, "collate_ms_per_step": round(wcms, 4) if wcms else None}
         del wjob
@@ -498,8 +556,7 @@ def main():
         dist.destroy_process_group()
         return
 
-    value = total_rows * args.steps / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
+    out = headline(args, world, G, ei, k, total_rows, row_count, elapsed, collate_ms, use_collate, calibration)
     # timing["walk"] etc. include the warm-up steps of timed_run: per-launch means
     walk_ms = timing["walk"][0] / max(timing["walk"][1], 1)
     scan_ms = timing["scan"][0] / max(timing["scan"][1], 1)
@@ -586,20 +643,10 @@ def main():
             except Exception as e:   # noqa: BLE001
                 cpu_all = {"error": str(e)[:200]}
 
-    out = {"metric": "k_subgraphs_sampled_per_sec", "value": round(value, 1), "unit": "k-subgraphs/s", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-           "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-           "config": {"workload": args.workload, "graphs": G, "columns": int(ei.shape[1]), "k": k, "rows_per_gpu": row_count,
-                      "global_rows": total_rows, "mode": args.mode, "sharding": f"rows{world}" if world > 1 else "none",
-                      "collate": "gather to rank 0 over RCCL every step (fixed-size narrowed messages, device-side offsets, no host round trip), "
-                                 f"the gather overlaps the next step's sampling, rank 0 unpacks one step behind (walk kernels on {args.walk_share}% of each "
-                                 f"CU on the destination so that RCCL's kernels find wave slots, {args.walk_share_others}% elsewhere); rows split {args.dst_rows}"
-                                 if use_collate else "none (single GPU)"},
-           "collate_ms_per_step": round(collate_ms, 4) if collate_ms is not None else None,
-           "per_rank": per_rank, "split_calibration": calibration,
-           "roofline": roofline, "cpu_baseline": cpu_baseline, "cpu_baseline_port": cpu_port if cpu_baseline else None,
-           "cpu_baseline_all_cores": cpu_all, "parity_checked_rows": parity_rows,
-           "parity_checked_tensors": ["nodes", "edge_ptr", "edge_index", "edge_src"] if parity_rows else []}
+    out.update({"per_rank": per_rank, "split_calibration": calibration,
+                "roofline": roofline, "cpu_baseline": cpu_baseline, "cpu_baseline_port": cpu_port if cpu_baseline else None,
+                "cpu_baseline_all_cores": cpu_all, "parity_checked_rows": parity_rows,
+                "parity_checked_tensors": ["nodes", "edge_ptr", "edge_index", "edge_src"] if parity_rows else []})
     if extras:
         out["extras"] = extras
 
@@ -641,6 +688,23 @@ def main():
     if world > 1 or args.force_collate:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def headline(args, world, G, ei, k, total_rows, row_count, elapsed, collate_ms, use_collate, calibration):
+    """the head of the result line: what a plain run prints (--full appends its measurements to it)"""
+    value = total_rows * args.steps / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+    return {"metric": "k_subgraphs_sampled_per_sec", "value": round(value, 1), "unit": "k-subgraphs/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+            "config": {"workload": args.workload, "graphs": G, "columns": int(ei.shape[1]), "k": k, "rows_per_gpu": row_count,
+                       "global_rows": total_rows, "mode": args.mode, "sharding": f"rows{world}" if world > 1 else "none",
+                       "collate": "gather to rank 0 over RCCL every step (fixed-size narrowed messages, device-side offsets, no host round trip), "
+                                  f"the gather overlaps the next step's sampling, rank 0 unpacks one step behind (walk kernels on {args.walk_share}% of each "
+                                  f"CU on the destination so that RCCL's kernels find wave slots, {args.walk_share_others}% elsewhere); rows split {args.dst_rows}"
+                                  if use_collate else "none (single GPU)"},
+            "collate_ms_per_step": round(collate_ms, 4) if collate_ms is not None else None,
+            "split_calibration": calibration, "full": bool(args.full)}
 
 
 def bench_drop_in(name, ugs_sampler, ei_t, ptr_t, m, k, mode, dev, reps):

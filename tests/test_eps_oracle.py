@@ -1,6 +1,8 @@
-"""CPU, build container only: the exact-enumeration law of oracle/eps_oracle.py against the REFERENCE epsilon_uniform_sampler
-itself (oracle/_ref, built from /root/reference by oracle/build_ref.py).  The reference has no reproducible output (per-thread
-generators), so the check is a chi-square goodness-of-fit of its empirical frequencies against the enumerated law."""
+"""CPU: the exact-enumeration law of oracle/eps_oracle.py against the REFERENCE epsilon_uniform_sampler itself.  The reference
+has no reproducible output (per-thread generators), so the check is a chi-square goodness-of-fit of its empirical frequencies
+against the enumerated law.  One draw of the reference per case is stored in tests/golden/f13_eps_reference_draws.npz
+(generator: oracle/make_golden_vs_ref.py, from the module built by oracle/build_ref.py), so the test runs anywhere; where the
+reference's sources are present, a fresh draw of the live module is checked as well."""
 import os
 
 import numpy as np
@@ -9,7 +11,9 @@ import pytest
 import eps_oracle
 
 REF_SRC = "/root/reference/src/samplers/epsilon_uniform_sampler"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="reference sources not present on this machine")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f13_eps_reference_draws.npz")
+CASES = [(3, 0.1), (4, 0.5), (3, 0.01)]
+M, SEED, FORMAT_ROWS = 40000, 1234, 50
 
 GRAPHS = {
     # name: (n, columns)
@@ -57,29 +61,57 @@ def check_rows_against_law(nodes, law, p_fail, what):
 
 @pytest.fixture(scope="module")
 def ref():
+    """the reference module where its sources are present, else None (the stored draws stand in for it)"""
+    if not os.path.isdir(REF_SRC):
+        return None
     import build_ref
     build_ref.build_eps()
     os.environ["OMP_NUM_THREADS"] = "1"
     return build_ref.load_eps()
 
 
-@pytest.mark.parametrize("name", sorted(GRAPHS))
-@pytest.mark.parametrize("k,eps", [(3, 0.1), (4, 0.5), (3, 0.01)])
-def test_reference_follows_the_enumerated_law(ref, name, k, eps):
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(GOLDEN) as z:
+        return {key: z[key] for key in z.files}
+
+
+def draw(ref, name, k, eps):
+    """one call of the reference: all M rows' nodes; edge_ptr, edge_index and edge_src of the first FORMAT_ROWS rows"""
     import torch
+    n, cols = GRAPHS[name]
+    ei = torch.tensor(cols, dtype=torch.long).t().contiguous()
+    nodes, eidx, eptr, sptr, esrc = ref.sample_batch(ei, torch.tensor([0, n]), M, k, "sample", SEED, eps)
+    nodes, eidx, eptr, esrc = nodes.numpy(), eidx.numpy(), eptr.numpy(), esrc.numpy()
+    ne = int(eptr[FORMAT_ROWS])
+    return nodes, eidx[:, :ne], eptr[:FORMAT_ROWS + 1], esrc[:ne]
+
+
+def golden_key(name, k, eps):
+    return f"{name}_k{k}_eps{eps}"
+
+
+def check_draw(name, k, eps, nodes, eidx, eptr, esrc, what):
     n, cols = GRAPHS[name]
     law, p_fail = eps_oracle.sample_law(eps_oracle.adjacency(cols, n), n, k, eps)
     assert abs(sum(law.values()) + p_fail - 1.0) < 1e-9
-    ei = torch.tensor(cols, dtype=torch.long).t().contiguous()
-    m = 40000
-    nodes, eidx, eptr, sptr, esrc = ref.sample_batch(ei, torch.tensor([0, n]), m, k, "sample", 1234, eps)
-    check_rows_against_law(nodes.numpy(), law, p_fail, f"reference {name} k={k} eps={eps}")
+    assert nodes.shape == (M, k)
+    check_rows_against_law(nodes, law, p_fail, f"{what} {name} k={k} eps={eps}")
     # output format of the first successful row against expected_edges
-    nodes, eidx, eptr, esrc = nodes.numpy(), eidx.numpy(), eptr.numpy(), esrc.numpy()
-    for r in range(50):
+    for r in range(FORMAT_ROWS):
         if nodes[r, 0] < 0:
             assert eptr[r + 1] == eptr[r]
             continue
         want = eps_oracle.expected_edges(cols, [int(x) for x in nodes[r]], "sample")
         got = list(zip(eidx[0, eptr[r]:eptr[r + 1]].tolist(), eidx[1, eptr[r]:eptr[r + 1]].tolist(), esrc[eptr[r]:eptr[r + 1]].tolist()))
         assert got == want
+
+
+@pytest.mark.parametrize("name", sorted(GRAPHS))
+@pytest.mark.parametrize("k,eps", CASES)
+def test_reference_follows_the_enumerated_law(ref, golden, name, k, eps):
+    key = golden_key(name, k, eps)
+    stored = [golden[f"{key}_{part}"].astype(np.int64) for part in ("nodes", "edge_index", "edge_ptr", "edge_src")]
+    check_draw(name, k, eps, *stored, "reference (stored draw)")
+    if ref is not None:
+        check_draw(name, k, eps, *draw(ref, name, k, eps), "reference")

@@ -13,5 +13,5 @@ PMC_MORE=1 tools/profile_pmc.sh r03_c3 --workload c3_proteins_b8192 > $O/pmc_c3.
 PMC_MORE=1 tools/profile_pmc.sh r03_c4 --workload c4_qm9_b65536 > $O/pmc_c4.log 2>&1
 python3 tools/summarize_pmc.py gpurun_out/pmc_r03_c3 > $O/r03_c3_pmc_summary.json
 python3 tools/summarize_pmc.py gpurun_out/pmc_r03_c4 > $O/r03_c4_pmc_summary.json
-timeout -k 10 400 python bench.py > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc $?"
+timeout -k 10 400 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc $?"
 ls $O | head -40
