@@ -58,7 +58,7 @@ int ugs_device_count(int *count);
 /* Select the HIP device used by the calling thread's subsequent calls (default: current HIP device). */
 int ugs_set_device(int device);
 
-/* Stream of the calling thread's subsequent JOBS (ugs_sample_*, ugs_sample_batch_*, ugs_eps_*): `use` != 0 runs their kernels
+/* Stream of the calling thread's subsequent JOBS (ugs_sample_*, ugs_sample_batch_*, ugs_eps_*, ugs_uniform_*): `use` != 0 runs their kernels
  * and copies on `stream` (a hipStream_t; NULL = the default stream) instead of the library's own non-blocking stream; `use` = 0
  * restores the library's stream.  A caller that hands in DEVICE output buffers obtained from a stream-ordered allocator
  * (torch.empty on torch's current stream) must run the job on that stream: a block the allocator just recycled may still be
@@ -246,6 +246,33 @@ int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
                                ugs_job **job_out, int64_t *total_edges_out);
 int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                 int64_t *edge_src, int dst_is_device);
+
+/* ---- uniform_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed): replaces the reference's
+ *      src/samplers/uniform_sampler/src/uniform_sampler.cpp:86-285 (exact uniform sampling over ALL connected k-subsets).
+ *      The law, for each graph g in batch order, vertices [ptr[g], ptr[g+1]), n = ptr[g+1] - ptr[g]:
+ *        1. adjacency: only columns with both endpoints inside g's range count, symmetrised (:121-136);
+ *        2. S_g: every k-subset of g's local vertices whose induced subgraph is connected, in lexicographic order of the
+ *           ascending vertex tuples (combination DFS :47-80); k = 0 or n < k gives an empty list;
+ *        3. draws: ONE std::mt19937_64(seed) for the call (:144); for each graph with S_g non-empty, m draws in order, each
+ *           std::uniform_int_distribution<int>(0, |S_g|-1) (:189, include/uniform_sampler.hpp:16-29) = libstdc++'s Lemire step
+ *           with a 128-bit product; graphs with S_g empty consume no draws and give m rows of -1 without edges;
+ *        4. a row holds ptr[g] + v for the drawn subset's ascending local vertices;
+ *        5. its edges: every batch column e, in column order, with both endpoints in g's range and in the subset (loops and
+ *           duplicate columns included), edge_src = e; mode 0 ("sample") numbers the endpoints by position in the row, any
+ *           other mode keeps batch ids (:193-236).
+ *      The whole computation runs on the device (ugs_uniform.hip): extension-set enumeration of the connected subsets only
+ *      (never all C(n, k)), per-root sort into lexicographic order, one-workgroup mt19937_64, rows and edges.  Bit-exact.
+ *      Same two-phase job protocol and stream rules as ugs_sample_batch_*; finish writes nodes[G*m,k], edge_index[2,total],
+ *      edge_ptr[G*m+1], sample_ptr[G+1], edge_src[total].
+ *      Errors: UGS_E_BAD_ARG for num_graphs < 0 (empty ptr), m < 0, k < 0, a decreasing ptr (the reference aborts on the last
+ *      three); UGS_E_UNSUPPORTED for a graph of more than 64 vertices with at least k vertices, and for a call with more than
+ *      2^25 connected k-subsets in all (the device budget; it also keeps every |S_g| within the reference's int).
+ *      The library stays usable after any of them. */
+int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                   int64_t num_graphs, int m_per_graph, int k, int mode, uint64_t seed,
+                                   ugs_job **job_out, int64_t *total_edges_out);
+int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                    int64_t *edge_src, int dst_is_device);
 
 /* ---- apx_ugs_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, epsilon): replaces the reference's
  *      src/samplers/apx_ugs_sampler/src/apx_ugs_sampler.cpp:461-519.  First graph only;

@@ -189,3 +189,41 @@ int64_t ugs_global_ws_words(int64_t gcap, int64_t gbcap, int64_t gpcap, int64_t 
 uint32_t ugs_chain_at_least(int64_t c, int *index_out);
 uint32_t ugs_chain_value(int idx);
 int64_t ugs_ord_words(int stages);
+
+// ---- uniform_sampler (ugs_uniform.hip): exact uniform connected k-subgraph sampling, graphs of at most 64 vertices ----
+#define UGS_UNI_BUDGET ((int64_t)1 << 25)    /* connected k-subsets (64-bit masks) one call may hold on the device */
+struct UgsUniGraph {
+    int64_t lo;           // ptr[g]
+    int64_t vbase;        // first entry of this graph in the enumerated vertices (adj, items >> 6)
+    int32_t n;            // vertices
+    int32_t enumerable;   // 1 <= k <= n <= 64: its subsets are enumerated; otherwise S_g is empty
+};
+struct UgsUniCall {
+    int64_t G, E, nv, rows, budget;          // graphs, columns, enumerated vertices, G * m rows, mask budget
+    int32_t m, k, mode;                      // mode 0: "sample" (row positions), otherwise batch ids
+    uint64_t seed;
+    const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
+    const UgsUniGraph *graphs;               // [G]
+    const int32_t *vgraph;                   // [nv] graph of an enumerated vertex
+    void *cub_tmp; size_t cub_bytes;         // hipCUB scratch (ugs_uniform_cub_bytes)
+    uint32_t *ckey, *ckey2; int32_t *cval, *cval2;   // [E] column -> graph (G: none), before / after the stable sort
+    int64_t *cstart;                         // [G + 1] graph g's columns at sorted positions [cstart[g], cstart[g+1])
+    uint16_t *bpair;                         // [E] local endpoints u | v << 8 of a sorted column (enumerable graphs)
+    uint64_t *adj;                           // [nv] neighbour mask of each enumerated vertex (no self bits)
+    uint32_t *icount;                        // [nv * 64] subsets of item (root vertex, first extension w)
+    int64_t *ioff;                           // [nv * 64 + 1] exclusive scan of icount
+    int64_t *scan_tmp;                       // ugs_scan_tmp_words(max(nv * 64, rows))
+    int32_t *seg_lo, *seg_hi;                // [nv] root buckets of the segmented radix sort (empty unless large)
+    uint64_t *keys_a, *keys_b;               // [budget] subset keys ~brev(mask) and the sort's second buffer
+    const uint64_t *keys_sorted;             // set by ugs_uniform_begin: keys_a or keys_b
+    int64_t *gstart, *gsize;                 // [G] first key and |S_g|
+    int32_t *nepos, *ne_list;                // [G] position among the graphs with S_g non-empty (-1: empty) / its inverse
+    int32_t *draws;                          // [G * m] index into S_g of each draw
+    uint64_t *rowmask;                       // [rows] subset of each row (0: a row of -1)
+    uint32_t *ecount;                        // [rows] edge entries per row
+    int64_t *status;                         // [4] running subset count, over-budget flag
+    int64_t *nodes, *edge_ptr;               // outputs: [rows, k], [rows + 1]
+};
+size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget);
+hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s);
+hipError_t ugs_uniform_fill(const UgsUniCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);

@@ -2235,6 +2235,10 @@ struct ugs_job {
     PoolBuf eps_blob;                  // pooled: hipMalloc/hipFree per call cost milliseconds once the process holds large plans
     UgsEpsLaunch eps_l{};
     PoolBuf eps_counts, eps_scantmp;
+    // uniform_sampler path (ugs_uniform.hip): the call's device arrays in one pooled blob; finish runs uni_fill from them
+    bool uni = false;
+    PoolBuf uni_blob;
+    UgsUniCall uni_c{};
 };
 
 namespace {
@@ -2244,6 +2248,7 @@ void free_job(ugs_job *j) {
     pool_put(j->nodes);
     pool_put(j->eps_counts); pool_put(j->eps_scantmp);
     pool_put(j->eps_blob);
+    pool_put(j->uni_blob);
     plan_unref(j->plan);
     delete j;
 }
@@ -2344,6 +2349,9 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
             UgsEpsLaunch l = j->eps_l;
             l.edge_ptr = j->d_eptr; l.edge_index = d_ei; l.edge_src = d_es; l.ld = tot;
             HIP_TRY(ugs_eps_launch(l, 1, j->dc.cus, s));
+        } else if (tot > 0 && j->uni) {
+            if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
+            HIP_TRY(ugs_uniform_fill(j->uni_c, d_ei, d_es, tot, s));
         } else if (tot > 0 && !packed) {
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
             if (int r = ugs_plan_fill(j->plan, j->m, j->k, j->mode, j->extra, 0, rows, s, static_cast<const int64_t *>(j->nodes.p),
@@ -2727,4 +2735,100 @@ int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_inde
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 
+// ---- uniform_sampler.sample_batch (reference src/samplers/uniform_sampler/src/uniform_sampler.cpp) ----
+int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                                   int m_per_graph, int k, int mode, uint64_t seed, ugs_job **job_out, int64_t *total_edges_out) {
+    if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+    if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
+    if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
+    if (k < 0) return fail(UGS_E_BAD_ARG, "k must be >= 0");
+    if (num_cols >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^31 - 1");
+    const int64_t G = num_graphs, E = num_cols;
+    std::vector<UgsUniGraph> gd((size_t)G);
+    int64_t nv = 0;
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t n = ptr[g + 1] - ptr[g];
+        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
+        if (k >= 1 && n >= k && n > 64)
+            return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
+                                           " vertices; graphs of more than 64 vertices (and at least k) are not supported");
+        UgsUniGraph &d = gd[(size_t)g];
+        d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = nv;
+        d.enumerable = k >= 1 && n >= k ? 1 : 0;
+        if (d.enumerable) nv += n;
+    }
+    DeviceCtx dc;
+    if (int rc = device_ctx(dc)) return rc;
+    const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? UGS_UNI_BUDGET : 0;
+    // one blob: inputs first (uploaded in one copy), then the scratch of every stage
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
+    const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
+                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), in_bytes = off;
+    const size_t cub_bytes = ugs_uniform_cub_bytes(E, nv, budget);
+    const size_t o_cub = take(cub_bytes), o_ck = take((size_t)E * 4), o_ck2 = take((size_t)E * 4), o_cv = take((size_t)E * 4),
+                 o_cv2 = take((size_t)E * 4), o_cst = take((size_t)(G + 1) * 8), o_bp = take((size_t)E * 2), o_adj = take((size_t)nv * 8),
+                 o_ic = take((size_t)items * 4), o_io = take((size_t)(items + 1) * 8),
+                 o_st = take((size_t)ugs_scan_tmp_words(std::max(items, rows)) * 8), o_sl = take((size_t)nv * 4), o_sh = take((size_t)nv * 4),
+                 o_ka = take((size_t)budget * 8), o_kb = take((size_t)budget * 8), o_gs = take((size_t)G * 8), o_gz = take((size_t)G * 8),
+                 o_np = take((size_t)G * 4), o_nl = take((size_t)G * 4), o_dr = take((size_t)rows * 4), o_rm = take((size_t)rows * 8),
+                 o_ec = take((size_t)rows * 4), o_status = take(4 * 8), total = off;
+    std::vector<char> host(in_bytes, 0);
+    for (int64_t e = 0; e < E; ++e) {
+        reinterpret_cast<int64_t *>(host.data() + o_src)[e] = edge_index[e];
+        reinterpret_cast<int64_t *>(host.data() + o_dst)[e] = edge_index[row_stride + e];
+    }
+    std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
+    if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsUniGraph));
+    auto *vg = reinterpret_cast<int32_t *>(host.data() + o_vg);
+    for (int64_t g = 0; g < G; ++g)
+        if (gd[(size_t)g].enumerable) for (int32_t v = 0; v < gd[(size_t)g].n; ++v) vg[gd[(size_t)g].vbase + v] = (int32_t)g;
+    auto *j = new ugs_job();
+    j->dc = dc; j->uni = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G; j->rows = rows;
+    auto bail = [&](int rc) { free_job(j); return rc; };
+    if (int rc = pool_get(total, dc.id, j->uni_blob)) return bail(rc);
+    if (int rc = pool_get((size_t)(rows * k + rows + 1) * sizeof(int64_t), dc.id, j->nodes)) return bail(rc);
+    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + rows * k;
+    char *b = static_cast<char *>(j->uni_blob.p);
+    UgsUniCall &c = j->uni_c;
+    c.G = G; c.E = E; c.nv = nv; c.rows = rows; c.budget = budget; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
+    c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
+    c.ptr = reinterpret_cast<const int64_t *>(b + o_ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + o_gd);
+    c.vgraph = reinterpret_cast<const int32_t *>(b + o_vg);
+    c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
+    c.ckey = reinterpret_cast<uint32_t *>(b + o_ck); c.ckey2 = reinterpret_cast<uint32_t *>(b + o_ck2);
+    c.cval = reinterpret_cast<int32_t *>(b + o_cv); c.cval2 = reinterpret_cast<int32_t *>(b + o_cv2);
+    c.cstart = reinterpret_cast<int64_t *>(b + o_cst); c.bpair = reinterpret_cast<uint16_t *>(b + o_bp);
+    c.adj = reinterpret_cast<uint64_t *>(b + o_adj); c.icount = reinterpret_cast<uint32_t *>(b + o_ic);
+    c.ioff = reinterpret_cast<int64_t *>(b + o_io); c.scan_tmp = reinterpret_cast<int64_t *>(b + o_st);
+    c.seg_lo = reinterpret_cast<int32_t *>(b + o_sl); c.seg_hi = reinterpret_cast<int32_t *>(b + o_sh);
+    c.keys_a = reinterpret_cast<uint64_t *>(b + o_ka); c.keys_b = reinterpret_cast<uint64_t *>(b + o_kb);
+    c.gstart = reinterpret_cast<int64_t *>(b + o_gs); c.gsize = reinterpret_cast<int64_t *>(b + o_gz);
+    c.nepos = reinterpret_cast<int32_t *>(b + o_np); c.ne_list = reinterpret_cast<int32_t *>(b + o_nl);
+    c.draws = reinterpret_cast<int32_t *>(b + o_dr); c.rowmask = reinterpret_cast<uint64_t *>(b + o_rm);
+    c.ecount = reinterpret_cast<uint32_t *>(b + o_ec); c.status = reinterpret_cast<int64_t *>(b + o_status);
+    c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    hipError_t e = hipMemcpyAsync(b, host.data(), in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (e == hipSuccess) e = ugs_uniform_begin(c, dc.stream);
+    if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
+    int64_t status[4] = {0, 0, 0, 0};
+    e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
+    if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
+    if (status[1])
+        return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the batch has more than " + std::to_string(budget) +
+                                            " connected k-subsets (the device budget; " + std::to_string(status[0]) + " counted before stopping)"));
+    *job_out = j;
+    if (total_edges_out) *total_edges_out = j->total;
+    return UGS_OK;
+}
+
+int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                    int64_t *edge_src, int dst_is_device) {
+    if (!job || !job->uni) return fail(UGS_E_BAD_ARG, "not a uniform_sampler job");
+    return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
+}
+
 }  // extern "C"
+

@@ -94,3 +94,12 @@ def algorithmic_bytes(nodes, edge_ptr, k, csr_degree_of_node):
     es = np.diff(np.asarray(edge_ptr)).astype(np.int64)
     per = 16 + (16 * valid.sum(1) + 4 * deg.sum(1)) + 4 * deg[:, : max(k - 1, 0)].sum(1) + 4 * es + 8 * k + 8 + 24 * es
     return float(per.mean()) if len(per) else 0.0
+
+
+def csl_graph(n, skip):
+    """Circular skip-link graph (CSL, Murphy et al. 2019): an n-cycle plus the chords (i, i + skip); returns int64 [2, 4n], every
+    undirected edge in both directions (first (i, j) for every edge, then (j, i))."""
+    und = [(i, (i + 1) % n) for i in range(n)] + [(i, (i + skip) % n) for i in range(n)]
+    us = [u for u, _ in und] + [v for _, v in und]
+    vs = [v for _, v in und] + [u for u, _ in und]
+    return np.array([us, vs], dtype=np.int64)

@@ -1,0 +1,210 @@
+"""uniform_law.py -- CPU restatement of the reference's `uniform_sampler.sample_batch` (AniruddhaMandal/SS-GNN
+src/samplers/uniform_sampler/src/uniform_sampler.cpp:86-285), for the tests.
+
+The law (include/ugs_mi355.h, ugs_uniform_sample_batch_begin, states it in full):
+  * per graph g, the columns with both endpoints in [ptr[g], ptr[g+1]) form its adjacency (:121-136);
+  * S_g = every k-subset of g's local vertices whose induced subgraph is connected, in lexicographic order of the ascending
+    vertex tuples (the combination DFS, :47-80);
+  * one std::mt19937_64(seed) for the call (:144); per graph with S_g non-empty, m draws
+    std::uniform_int_distribution<int>(0, |S_g|-1) (:189), i.e. libstdc++'s Lemire step with a 128-bit product;
+    graphs with S_g empty draw nothing and give m rows of -1;
+  * a row's edges: every batch column, in column order, with both endpoints in the graph's range and in the subset;
+    mode "sample" numbers them by position in the row, any other mode keeps batch ids (:193-236).
+
+Pure Python + numpy: `mt19937_64`, `lemire`, two enumerations (`connected_subsets_comb`, the literal definition, and
+`connected_subsets_esu` / `sorted_masks`, extension-set search + sort, fast enough for 64-vertex graphs with ~1e5 subsets) and
+`sample_batch`, the output assembly.
+"""
+import itertools
+
+import numpy as np
+
+M64 = (1 << 64) - 1
+
+
+class mt19937_64:
+    """std::mt19937_64 (C++ [rand.predef]: the 10000th output for the default seed 5489 is 9981545732273789042)."""
+    N, M = 312, 156
+    A = 0xB5026F5AA96619E9
+    UM, LM = 0xFFFFFFFF80000000, 0x7FFFFFFF
+
+    def __init__(self, seed=5489):
+        mt = [seed & M64]
+        for i in range(1, self.N):
+            mt.append((6364136223846793005 * (mt[-1] ^ (mt[-1] >> 62)) + i) & M64)
+        self.mt, self.i = mt, self.N
+
+    def _twist(self):
+        mt, N, M = self.mt, self.N, self.M
+        for i in range(N):
+            y = (mt[i] & self.UM) | (mt[(i + 1) % N] & self.LM)
+            mt[i] = mt[(i + M) % N] ^ (y >> 1) ^ (self.A if y & 1 else 0)
+        self.i = 0
+
+    def __call__(self):
+        if self.i >= self.N:
+            self._twist()
+        y = self.mt[self.i]
+        self.i += 1
+        y ^= (y >> 29) & 0x5555555555555555
+        y ^= (y << 17) & 0x71D67FFFEDA60000
+        y ^= (y << 37) & 0xFFF7EEE000000000
+        y ^= y >> 43
+        return y & M64
+
+
+def lemire(gen, n):
+    """std::uniform_int_distribution<int>(0, n-1)(gen) for a 64-bit generator, libstdc++ 11
+    (bits/uniform_int_dist.h:246-268, 302-307): p = x*n; if lo64(p) < n: t = (2^64 - n) mod n, redraw while lo64(p) < t."""
+    p = gen() * n
+    if (p & M64) < n:
+        t = ((1 << 64) - n) % n
+        while (p & M64) < t:
+            p = gen() * n
+    return p >> 64
+
+
+def graph_adjacency(src, dst, lo, n):
+    """Neighbour bitmasks (Python ints) of the graph [lo, lo+n): columns with both endpoints inside, symmetrised."""
+    adj = [0] * n
+    inside = (src >= lo) & (src < lo + n) & (dst >= lo) & (dst < lo + n)
+    for u, v in zip((src[inside] - lo).tolist(), (dst[inside] - lo).tolist()):
+        adj[u] |= 1 << v
+        adj[v] |= 1 << u
+    return adj
+
+
+def _connected(sub, adj):
+    seen, todo = 1 << sub[0], [sub[0]]
+    want = 0
+    for v in sub:
+        want |= 1 << v
+    while todo:
+        u = todo.pop()
+        new = adj[u] & want & ~seen
+        seen |= new
+        while new:
+            w = (new & -new).bit_length() - 1
+            new &= new - 1
+            todo.append(w)
+    return seen == want
+
+
+def connected_subsets_comb(adj, k):
+    """The reference's definition, literally: every k-combination in lexicographic order, kept if connected."""
+    n = len(adj)
+    if k <= 0:
+        return []
+    return [c for c in itertools.combinations(range(n), k) if _connected(c, adj)]
+
+
+def esu_masks(adj, k):
+    """Every connected k-subset as a bitmask, each once, by extension-set search rooted at its minimum vertex
+    (Wernicke 2006): grow sub by w from the extension set; the new extension set adds w's neighbours above the root that
+    are neither in nor adjacent to the current set."""
+    n = len(adj)
+    out = []
+    if k <= 0 or k > n:
+        return out
+    for v in range(n):
+        above = ((1 << n) - 1) & ~((2 << v) - 1)
+        if k == 1:
+            out.append(1 << v)
+            continue
+        stack = [(1 << v, adj[v] & above, adj[v] | (1 << v))]
+        while stack:
+            sub, ext, nb = stack.pop()
+            size = bin(sub).count("1")
+            while ext:
+                w = (ext & -ext).bit_length() - 1
+                ext &= ext - 1
+                if size + 1 == k:
+                    out.append(sub | (1 << w))
+                else:
+                    stack.append((sub | (1 << w), ext | (adj[w] & ~nb & above), nb | adj[w]))
+    return out
+
+
+def _brev64(a):
+    """Bit reversal of a uint64 array."""
+    a = a.astype(np.uint64)
+    for sh, mk in ((1, 0x5555555555555555), (2, 0x3333333333333333), (4, 0x0F0F0F0F0F0F0F0F), (8, 0x00FF00FF00FF00FF),
+                   (16, 0x0000FFFF0000FFFF), (32, 0x00000000FFFFFFFF)):
+        s, m = np.uint64(sh), np.uint64(mk)
+        a = ((a >> s) & m) | ((a & m) << s)
+    return a
+
+
+def sorted_masks(adj, k):
+    """S_g as a uint64 mask array in lexicographic order of the ascending tuples.  For sets of one size that order is the
+    DESCENDING order of the bit-reversed mask: the first vertex where two sets differ is the highest bit of the reversed
+    masks where they differ, and the set holding it comes first."""
+    if len(adj) > 64:
+        raise ValueError("masks hold at most 64 vertices")
+    masks = np.array(esu_masks(adj, k), dtype=np.uint64)
+    return masks[np.argsort(~_brev64(masks), kind="stable")]
+
+
+def mask_tuple(mask):
+    mask = int(mask)
+    return tuple(i for i in range(mask.bit_length()) if mask >> i & 1)
+
+
+def connected_subsets_esu(adj, k):
+    return [mask_tuple(x) for x in sorted_masks(adj, k)]
+
+
+def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, enumerate_fn=None):
+    """The five int64 arrays (nodes [G*m, k], edge_index [2, E], edge_ptr [G*m+1], sample_ptr [G+1], edge_src [E])."""
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    ptr = np.asarray(ptr, dtype=np.int64)
+    src, dst = ei[0], ei[1]
+    G, m = len(ptr) - 1, int(m_per_graph)
+    enum = enumerate_fn or (lambda adj, kk: sorted_masks(adj, kk) if len(adj) <= 64 else connected_subsets_comb(adj, kk))
+    gen = mt19937_64(seed & M64)
+    nodes = np.full((max(G, 0) * m, k), -1, dtype=np.int64)
+    eu, ev, es, eptr = [], [], [], [0]
+    cols = np.arange(src.shape[0], dtype=np.int64)
+    for g in range(G):
+        lo, n = int(ptr[g]), int(ptr[g + 1] - ptr[g])
+        subsets = enum(graph_adjacency(src, dst, lo, n), k) if n >= k else []
+        inside = (src >= lo) & (src < lo + n) & (dst >= lo) & (dst < lo + n)
+        cu, cv, cc = (src[inside] - lo).tolist(), (dst[inside] - lo).tolist(), cols[inside].tolist()
+        for s in range(m):
+            row = g * m + s
+            if len(subsets):
+                sub = subsets[lemire(gen, len(subsets))]
+                sub = sub if isinstance(sub, tuple) else mask_tuple(sub)
+                pos = {v: i for i, v in enumerate(sub)}
+                nodes[row] = [lo + v for v in sub]
+                for u, v, c in zip(cu, cv, cc):
+                    if u in pos and v in pos:
+                        eu.append(pos[u] if mode == "sample" else lo + u)
+                        ev.append(pos[v] if mode == "sample" else lo + v)
+                        es.append(c)
+            eptr.append(len(es))
+    return (nodes, np.array([eu, ev], dtype=np.int64).reshape(2, -1), np.array(eptr, dtype=np.int64),
+            np.arange(max(G, 0) + 1, dtype=np.int64) * m, np.array(es, dtype=np.int64))
+
+
+def draws_blocked(outputs, sizes, block=312):
+    """The draw kernel's cursor logic (ugs_uniform.hip, uni_draw), restated: `outputs` yields the generator's words in blocks of
+    `block`; within a block every pending draw d takes word pos + (d - d0), assuming each draw consumes one word; the first draw
+    whose Lemire step rejects (lo64(x * N) < 2^64 mod N) ends the round: the draws before it stand, its word is consumed and it is
+    retried in the next round.  Must equal [lemire(gen, N) for N in sizes]."""
+    words, pos, res, d0 = [outputs() for _ in range(block)], 0, [], 0
+    while d0 < len(sizes):
+        todo = min(len(sizes) - d0, block - pos)
+        first = todo
+        for i in range(todo):
+            n, x = sizes[d0 + i], words[pos + i]
+            lo = (x * n) & M64
+            if lo < n and lo < ((1 << 64) - n) % n:
+                first = i
+                break
+            res.append((x * n) >> 64)
+        d0 += first
+        pos += first + (1 if first < todo else 0)
+        if pos == block:
+            words, pos = [outputs() for _ in range(block)], 0
+    return res
