@@ -179,7 +179,11 @@ int ugs_plan_fill(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extr
  * of the total in between: d_edge_ptr[row_count] holds it afterwards).  Same outputs as ugs_plan_walk followed by ugs_plan_fill
  * (reference src/sampler.cpp:91-290).  Knowing that nobody reads edge_ptr between the two phases, the step of a batch of small
  * graphs runs in two launches instead of three: the fill kernel scans the per-row counts itself (decoupled look-back over tiles
- * of 32 rows; `UGS_NO_FUSED_SCAN` set = the three-launch form). */
+ * of 32 rows; `UGS_NO_FUSED_SCAN` set = the three-launch form).
+ * Concurrent use: several threads may step, walk and fill through one plan (or through plans that the plan cache shares, e.g. two
+ * ugs_plan_create_batch of the same batch) at the same time, on one stream or on several; the calls are serialised through the
+ * plan's scratch and each gets its own correct outputs.  A step holds the plan's lock from its walk to its fill.  Steps that should
+ * overlap on the device go through a plan and its twin (ugs_plan_twin) on two streams. */
 int ugs_plan_step(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, int64_t row_begin,
                   int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *d_edge_index, int64_t ld,
                   int64_t *d_edge_src);

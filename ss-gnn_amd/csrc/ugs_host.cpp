@@ -505,6 +505,7 @@ struct ugs_plan {
     uint64_t cache_key = 0;
     bool cached = false;
     // lazily grown scratch owned by the plan (serialised by `mu` per call)
+    // invariant: what a walk leaves here is read only by kernels launched under the same hold of `mu`, or after the stg_* check below
     PoolBuf counts, ovf1, ovf2, ovfcnt, scantmp, gws;
     // edges staged by the last walk (UgsWalkArgs::stage) and the call they belong to: a fill of exactly those rows into/from
     // the same nodes buffer expands them; any other fill reads the adjacency rows again
@@ -1783,6 +1784,9 @@ int ugs_plan_info(const ugs_plan *plan, int k, int64_t *num_graphs, int64_t *num
 static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, const uint64_t *d_seed_ptr,
                           int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
                           bool *defer_scan = nullptr, bool poll_total = false);
+static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed,
+                            const uint64_t *d_seed_ptr, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
+                            int64_t *total_edges_host, bool *defer_scan, bool poll_total);
 
 
 int ugs_plan_walk(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, int64_t row_begin,
@@ -1790,12 +1794,9 @@ int ugs_plan_walk(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extr
     return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, total_edges_host);
 }
 
-// defer_scan (ugs_plan_step): where the fill kernel can turn the counts into edge_ptr itself -- first tier S (rows are filled from
-// their adjacency, nothing is staged), no capture in progress -- the scan launch is left out and *defer_scan set.
-static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, const uint64_t *d_seed_ptr,
-                          int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
-                          bool *defer_scan, bool poll_total) {
-    if (defer_scan) *defer_scan = false;
+// the argument checks of a walk; its device made current
+static int walk_check(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t row_begin, int64_t row_count, const int64_t *d_nodes,
+                      const int64_t *d_edge_ptr) {
     if (!plan) return fail(UGS_E_BAD_ARG, "plan is null");
     if (k < 1) return fail(UGS_E_BAD_ARG, "k must be >= 1");
     if (k > UGS_KMAX) return fail(UGS_E_UNSUPPORTED, "k > 32 is not supported by the HIP sampler");
@@ -1804,6 +1805,17 @@ static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int6
         return fail(UGS_E_BAD_ARG, "row range outside [0, num_graphs * m_per_graph)");
     if (row_count > 0 && (!d_nodes || !d_edge_ptr)) return fail(UGS_E_BAD_ARG, "null output pointer");
     HIP_TRY(hipSetDevice(plan->device));
+    return UGS_OK;
+}
+
+// defer_scan (ugs_plan_step): where the fill kernel can turn the counts into edge_ptr itself -- first tier S (rows are filled from
+// their adjacency, nothing is staged), no capture in progress -- the scan launch is left out and *defer_scan set.  The caller then
+// launches that fill without letting go of plan->mu in between (plan_walk_locked).
+static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, const uint64_t *d_seed_ptr,
+                          int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
+                          bool *defer_scan, bool poll_total) {
+    if (defer_scan) *defer_scan = false;
+    if (int rc = walk_check(plan, m_per_graph, k, mode, row_begin, row_count, d_nodes, d_edge_ptr)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (row_count == 0) {
         if (d_edge_ptr) HIP_TRY(hipMemsetAsync(d_edge_ptr, 0, sizeof(int64_t), s));
@@ -1812,7 +1824,19 @@ static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int6
     }
     const TierChoice tc = choose_tier(plan, k);
     std::lock_guard<std::mutex> lk(plan->mu);
+    return plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, d_seed_ptr, row_begin, row_count, s, d_nodes, d_edge_ptr,
+                            total_edges_host, defer_scan, poll_total);
+}
+
+// The walk of rows [row_begin, row_begin + row_count), row_count > 0, arguments checked (walk_check).  Call with plan->mu held and
+// tc = choose_tier(plan, k) taken before the lock (choose_tier takes mu itself).  With *defer_scan set on return the plan's counts
+// and 8-row sums are this walk's only while the caller keeps holding mu: a fill that scans them is launched before it lets go.
+static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed,
+                            const uint64_t *d_seed_ptr, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
+                            int64_t *total_edges_host, bool *defer_scan, bool poll_total) {
+    if (defer_scan) *defer_scan = false;
     if (int rc = plan_enter(plan, s)) return rc;
+    plan->stg_valid = false;                    // before any scratch is regrown: a walk that fails below leaves no staging record behind
     if (int rc = ensure(plan->counts, (size_t)row_count * sizeof(uint32_t), plan->device, plan)) return rc;
     if (int rc = ensure(plan->scantmp, (size_t)ugs_scan_tmp_words(row_count) * sizeof(int64_t), plan->device, plan)) return rc;
     if (int rc = ensure(plan->ovfcnt, 4 * sizeof(uint32_t), plan->device, plan)) return rc;
@@ -1824,7 +1848,6 @@ static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int6
     // edge staging by the walk (tiers with one walk per wave): 512 bytes of scratch per row, bounded
     const int64_t stage_max = [] { const char *e = std::getenv("UGS_STAGE_MAX_MB"); return (int64_t)(e ? std::atoll(e) : 4096) << 20; }();   // read per call (tests toggle it)
     const bool stg = tc.first != UGS_TIER_S && row_count * (int64_t)(UGS_STAGE_ITEMS * sizeof(uint2)) <= stage_max;
-    plan->stg_valid = false;
     if (stg) {
         if (int rc = ensure(plan->stage, (size_t)row_count * UGS_STAGE_ITEMS * sizeof(uint2), plan->device, plan)) return rc;
         if (int rc = ensure(plan->ulist, (size_t)row_count * sizeof(int64_t), plan->device, plan)) return rc;
@@ -1979,14 +2002,21 @@ int ugs_plan_fill(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extr
 
 int ugs_plan_step(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, int64_t row_begin, int64_t row_count,
                   void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *d_edge_index, int64_t ld, int64_t *d_edge_src) {
-    bool deferred = false;
-    if (int rc = plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr,
-                                nullptr, &deferred)) return rc;
-    if (!deferred || row_count <= 0)
-        return ugs_plan_fill(plan, m_per_graph, k, mode, extra_node_offset, row_begin, row_count, stream, d_nodes, d_edge_ptr, d_edge_index, ld, d_edge_src);
+    if (int rc = walk_check(plan, m_per_graph, k, mode, row_begin, row_count, d_nodes, d_edge_ptr)) return rc;
+    if (row_count == 0)                         // edge_ptr[0] = 0, nothing to fill
+        return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, nullptr);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(plan->device));
-    std::lock_guard<std::mutex> lk(plan->mu);
+    const TierChoice tc = choose_tier(plan, k);
+    // one hold of mu from the walk to the fill: the fused fill scans the counts and 8-row sums the walk leaves in the plan's scratch,
+    // which another caller's walk on this plan would overwrite in between
+    std::unique_lock<std::mutex> lk(plan->mu);
+    bool deferred = false;
+    if (int rc = plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, s, d_nodes, d_edge_ptr,
+                                  nullptr, &deferred, false)) return rc;
+    if (!deferred) {                            // the scan ran: the fill reads the plan's scratch only through the staging check
+        lk.unlock();
+        return ugs_plan_fill(plan, m_per_graph, k, mode, extra_node_offset, row_begin, row_count, stream, d_nodes, d_edge_ptr, d_edge_index, ld, d_edge_src);
+    }
     if (int rc = plan_enter(plan, s)) return rc;
     UgsFillArgs a{};
     a.plan = plan->dev;
@@ -2253,12 +2283,12 @@ void free_job(ugs_job *j) {
     delete j;
 }
 
-// second launch of a job's step (see begin_common): ugs_fill_scan into the job's staging, total through the pinned slot of the plan
-int packed_fill(ugs_job *j, int64_t cap3) {
+// second launch of a job's step (see begin_common): ugs_fill_scan into the job's staging, total through the pinned slot of the plan.
+// Call with plan->mu held since the walk whose counts and 8-row sums it scans.
+int packed_fill_locked(ugs_job *j, int64_t cap3) {
     ugs_plan *plan = j->plan;
     hipStream_t s = j->dc.stream;
     int64_t *stg = static_cast<int64_t *>(j->nodes.p) + (j->rows * j->k + j->rows + 1);       // (begin_common sized the buffer for it)
-    std::unique_lock<std::mutex> lk(plan->mu);
     if (int rc = plan_enter(plan, s)) return rc;
     if (!plan->pin_slot) plan->pin_slot = pin_slot_get();
     UgsFillArgs a{};
@@ -2319,10 +2349,18 @@ int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed
         // exceed the bound: the kernel then writes nothing and finish fills the ordinary way.
         const int64_t cap3 = cap3_want;
         const bool want_packed = may_pack;
-        bool deferred = false;
-        rc = plan_walk_impl(plan, m, k, mode, extra, seed, nullptr, 0, j->rows, dc.stream, static_cast<int64_t *>(j->nodes.p), j->d_eptr, &j->total,
-                            want_packed ? &deferred : nullptr, true);
-        if (!rc && deferred) rc = packed_fill(j, cap3);
+        int64_t *d_nodes = static_cast<int64_t *>(j->nodes.p);
+        if (want_packed) {                          // (rows > 0) one hold of mu from the walk to the fill that scans its counts and sums
+            rc = walk_check(plan, m, k, mode, 0, j->rows, d_nodes, j->d_eptr);
+            if (!rc) {
+                std::lock_guard<std::mutex> lk(plan->mu);
+                bool deferred = false;
+                rc = plan_walk_locked(plan, tc0, m, k, mode, extra, seed, nullptr, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, &deferred, true);
+                if (!rc && deferred) rc = packed_fill_locked(j, cap3);
+            }
+        } else {
+            rc = plan_walk_impl(plan, m, k, mode, extra, seed, nullptr, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, nullptr, true);
+        }
     }
     if (rc) { free_job(j); return rc; }
     *job_out = j;
