@@ -21,7 +21,8 @@ def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, epsilo
 
     backend="host" (default): the reference's sequential generator, bit-exact with the reference.
     backend="gpu": the same algorithm on the GPU, one generator per (sample, trial), all samples and trials side by side; same
-    output law (statistical parity), deterministic in (graph, seed); 2 <= k <= 8.  return_order=True (gpu only) appends the
+    output law (statistical parity), deterministic in (graph, seed); 2 <= k <= 32 (the C ABI's limit, UGS_KMAX; beyond k = 7
+    APX-PROB visits the first 720 permutations only, like the reference).  return_order=True (gpu only) appends the
     APX-DD order positions and bucket estimates it used (testing aid)."""
     if backend not in ("host", "gpu"):
         raise RuntimeError("backend must be 'host' or 'gpu'")

@@ -1,8 +1,8 @@
 """GPU: the library called from several host threads at once.  ctypes releases the GIL, so the
 threads really run side by side in the host library: they share the preprocessing LRU, the cached device plans and their
 scratch, the pool and the job streams.  Every test computes its expected tensors first, on the main thread, from a plain
-reference (the CPU oracle, tests/uniform_law.py, or -- for epsilon_uniform_sampler, whose only exact contract is determinism in the
-seed -- the product's own single-threaded result); then 4 to 8 threads start together behind a barrier, draw their calls from
+reference (the CPU oracle, tests/uniform_law.py, or tests/eps_rows.py, the bit-exact restatement of the epsilon_uniform_sampler
+kernels); then 4 to 8 threads start together behind a barrier, draw their calls from
 their own random.Random and compare every result bit for bit.  Mismatches and exceptions are collected, and the main thread
 asserts that there are none and that every thread finished."""
 import os
@@ -194,6 +194,7 @@ def test_mixed_entry_points_at_once(monkeypatch):
     chunks), and two threads whose calls must fail -- k = 33 for ugs_sampler, a 65-vertex graph for uniform_sampler.  Each
     failing thread must read its OWN error text (ugs_last_error is thread-local) while the others keep matching their references."""
     import epsilon_uniform_sampler
+    import eps_rows
     import oracle
     import torch
     import ugs_sampler
@@ -230,10 +231,12 @@ def test_mixed_entry_points_at_once(monkeypatch):
     u_ei, u_ptr = wl.tu_batch(14, 18, 6)
     u_in = (torch.from_numpy(u_ei), torch.from_numpy(u_ptr))
     u_want = {(mode, s): _torch_all(U.sample_batch(u_ei, u_ptr, 40, 4, mode, s)) for mode in ("sample", "global") for s in seeds}
-    # epsilon_uniform_sampler: its single-threaded result
+    # epsilon_uniform_sampler: the restatement of its kernels, which the single-threaded result equals too
     e_ei, e_ptr = wl.tu_batch(16, 22, 6)
     e_in = (torch.from_numpy(e_ei), torch.from_numpy(e_ptr))
-    e_want = {s: tuple(t.clone() for t in epsilon_uniform_sampler.sample_batch(*e_in, 50, 4, "sample", s, 0.2)) for s in seeds}
+    e_want = {s: _torch_all(eps_rows.sample_rows(e_ei, e_ptr, 50, 4, "sample", s, 0.2)) for s in seeds}
+    for s in seeds[:2]:
+        assert all(torch.equal(a, b) for a, b in zip(epsilon_uniform_sampler.sample_batch(*e_in, 50, 4, "sample", s, 0.2), e_want[s]))
     # streamed: 8 graphs x 400 rows = 3200 rows, 7 chunks; the expected totals are primed so that every call streams
     st_ei, st_ptr = wl.tu_batch(25, 40, 8)
     st_in = (torch.from_numpy(st_ei), torch.from_numpy(st_ptr))
