@@ -58,7 +58,7 @@ int ugs_device_count(int *count);
 /* Select the HIP device used by the calling thread's subsequent calls (default: current HIP device). */
 int ugs_set_device(int device);
 
-/* Stream of the calling thread's subsequent JOBS (ugs_sample_*, ugs_sample_batch_*, ugs_eps_*, ugs_uniform_*): `use` != 0 runs their kernels
+/* Stream of the calling thread's subsequent JOBS (ugs_sample_*, ugs_sample_batch_*, ugs_eps_*, ugs_uniform_*, ugs_rwr_*): `use` != 0 runs their kernels
  * and copies on `stream` (a hipStream_t; NULL = the default stream) instead of the library's own non-blocking stream; `use` = 0
  * restores the library's stream.  A caller that hands in DEVICE output buffers obtained from a stream-ordered allocator
  * (torch.empty on torch's current stream) must run the job on that stream: a block the allocator just recycled may still be
@@ -277,6 +277,35 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
                                    ugs_job **job_out, int64_t *total_edges_out);
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device);
+
+/* ---- rwr_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, p_restart): replaces the reference's
+ *      src/samplers/rwr_sampler/src/rwr_sampler.cpp:73-296 (random walk with restart) run with ONE OpenMP thread, its only
+ *      deterministic setting (with more, the seeds and the row order depend on the schedule).
+ *      The law, for each graph g in batch order, vertices [ptr[g], ptr[g+1]), n = ptr[g+1] - ptr[g]:
+ *        1. adjacency (:31-71): columns in column order; a column belongs to the graph with ptr[g] <= u, v < ptr[g+1] (none:
+ *           dropped); adj[u] gets v, then adj[v] gets u, so a loop puts u into adj[u] twice and duplicate columns stay;
+ *        2. RNG (:17-28, :130): one SplitMix64 per graph seeded with seed + g; its draw i (1-based) is
+ *           mix(seed + g + (i + 1) * 0x9e3779b97f4a7c15) mod 2^64; next_int(b) = u64 % b, next_double = (u64 >> 11) * 2^-53;
+ *        3. n < k (n = 0 included): m rows of -1 without edges, no draws;
+ *        4. per sample (:162-190): seed_node = next_int(n); while |chosen| < k and it < 10 n k: draw r; r < p_restart or adj[cur]
+ *           empty: cur = seed_node (one draw); else cur = adj[cur][next_int(|adj[cur]|)] (a second draw); a vertex not seen
+ *           before is appended to chosen.  Fewer than k vertices at the end: a row of -1 without edges, the stream goes on;
+ *        5. a row holds ptr[g] + v for v in chosen order; its edges (:215-247): for u in chosen order, for v in adj[u] order with
+ *           v chosen, (u, v), loops and duplicates included; mode 0 ("sample") numbers them by position in chosen, any other
+ *           mode gives batch ids; edge_src is -1.  sample_ptr = [0, m, 2m, ..., G m].
+ *      The whole computation runs on the device (ugs_rwr.hip): a stable half-edge sort builds the CSR, one workgroup per graph
+ *      evaluates the walk at every draw offset of a window and follows the chain of real starts through it (the draws are a
+ *      function of their index), and the chosen walks are run again for rows and edges.  Bit-exact.
+ *      Same two-phase job protocol and stream rules as ugs_sample_batch_*; finish writes nodes[G*m,k], edge_index[2,total],
+ *      edge_ptr[G*m+1], sample_ptr[G+1], edge_src[total].
+ *      Errors: UGS_E_BAD_ARG for num_graphs < 0 (empty ptr), m < 0, a decreasing ptr, and the reference's checks k >= 1 and
+ *      0 <= p_restart <= 1 (NaN fails); UGS_E_UNSUPPORTED for k > 64, a graph with n >= k and 10 n k > INT_MAX (the reference's
+ *      int limit overflows), 2^30 columns or more, 2^31 - 1 vertices or more.  The library stays usable after any of them. */
+int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                               int64_t num_graphs, int m_per_graph, int k, int mode, uint64_t seed, double p_restart,
+                               ugs_job **job_out, int64_t *total_edges_out);
+int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                int64_t *edge_src, int dst_is_device);
 
 /* ---- apx_ugs_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, epsilon): replaces the reference's
  *      src/samplers/apx_ugs_sampler/src/apx_ugs_sampler.cpp:461-519.  First graph only;

@@ -227,3 +227,33 @@ struct UgsUniCall {
 size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget);
 hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s);
 hipError_t ugs_uniform_fill(const UgsUniCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+
+// ---- rwr_sampler (ugs_rwr.hip): random walk with restart, one SplitMix64 stream per graph, counter-based speculation ----
+#define UGS_RWR_KMAX 64
+struct UgsRwrGraph {
+    int64_t lo;           // ptr[g]
+    int64_t vbase;        // ptr[g] - ptr[0]: first vertex of the graph in the batch's CSR
+    int32_t n;            // vertices
+    int32_t T;            // iteration limit 10 n k of a walk (n >= k >= 1); 0: n < k, m rows of -1 and no draws
+};
+struct UgsRwrCall {
+    int64_t G, E, NV, rows;                  // graphs, columns, batch vertices ptr[G] - ptr[0], G * m rows
+    int32_t m, k, mode, spec;                // mode 0: "sample" (row positions), otherwise batch ids; window = spec * block offsets
+    uint64_t seed;
+    double p;                                // p_restart
+    const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
+    const UgsRwrGraph *graphs;               // [G]
+    void *cub_tmp; size_t cub_bytes;         // hipCUB scratch (ugs_rwr_cub_bytes)
+    uint32_t *hkey, *hkey2;                  // [2E] half-edge 2e + side: its source vertex - ptr[0] (NV: column dropped), before / after the sort
+    int32_t *hval, *hval2;                   // [2E] the half-edge's target, local to its graph; sorted: the CSR targets
+    int32_t *rs;                             // [NV + 1] CSR row starts (rows in (column, side) order of their half-edges)
+    int32_t *parent, *csize;                 // [NV] union-find over the columns, component sizes at the roots
+    uint8_t *doomed;                         // [NV] the vertex's component has fewer than k vertices: every walk seeded there fails
+    int64_t *rstart;                         // [rows] draws of the graph's stream consumed before the row's walk; -1: a row of -1
+    uint32_t *ecount;                        // [rows] edge entries per row
+    int64_t *scan_tmp;                       // ugs_scan_tmp_words(rows)
+    int64_t *nodes, *edge_ptr;               // outputs: [rows, k], [rows + 1]
+};
+size_t ugs_rwr_cub_bytes(int64_t E);
+hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s);
+hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);

@@ -2268,7 +2268,10 @@ struct ugs_job {
     // uniform_sampler path (ugs_uniform.hip): the call's device arrays in one pooled blob; finish runs uni_fill from them
     bool uni = false;
     PoolBuf uni_blob;
-    UgsUniCall uni_c{};
+    UgsUniCall uni_c{};    // rwr_sampler path (ugs_rwr.hip): the same, finish runs rwr_fill
+    bool rwr = false;
+    PoolBuf rwr_blob;
+    UgsRwrCall rwr_c{};
 };
 
 namespace {
@@ -2279,6 +2282,7 @@ void free_job(ugs_job *j) {
     pool_put(j->eps_counts); pool_put(j->eps_scantmp);
     pool_put(j->eps_blob);
     pool_put(j->uni_blob);
+    pool_put(j->rwr_blob);
     plan_unref(j->plan);
     delete j;
 }
@@ -2390,6 +2394,9 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
         } else if (tot > 0 && j->uni) {
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
             HIP_TRY(ugs_uniform_fill(j->uni_c, d_ei, d_es, tot, s));
+        } else if (tot > 0 && j->rwr) {
+            if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
+            HIP_TRY(ugs_rwr_fill(j->rwr_c, d_ei, d_es, tot, s));
         } else if (tot > 0 && !packed) {
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
             if (int r = ugs_plan_fill(j->plan, j->m, j->k, j->mode, j->extra, 0, rows, s, static_cast<const int64_t *>(j->nodes.p),
@@ -2865,6 +2872,88 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device) {
     if (!job || !job->uni) return fail(UGS_E_BAD_ARG, "not a uniform_sampler job");
+    return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
+}
+
+// ---- rwr_sampler.sample_batch (reference src/samplers/rwr_sampler/src/rwr_sampler.cpp, one OpenMP thread) ----
+int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int m_per_graph, int k, int mode, uint64_t seed, double p_restart, ugs_job **job_out,
+                               int64_t *total_edges_out) {
+    if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+    if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
+    if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
+    if (k < 1) return fail(UGS_E_BAD_ARG, "k must be >= 1");
+    if (!(p_restart >= 0.0 && p_restart <= 1.0)) return fail(UGS_E_BAD_ARG, "p_restart in [0,1]");
+    if (k > UGS_RWR_KMAX) return fail(UGS_E_UNSUPPORTED, "rwr_sampler: k must be <= " + std::to_string(UGS_RWR_KMAX));
+    if (num_cols >= ((int64_t)1 << 30)) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^30");
+    const int64_t G = num_graphs, E = num_cols;
+    std::vector<UgsRwrGraph> gd((size_t)G);
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t n = ptr[g + 1] - ptr[g];
+        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
+        if (n >= k && n > (int64_t)INT32_MAX / (10 * (int64_t)k))
+            return fail(UGS_E_UNSUPPORTED, "rwr_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
+                                           " vertices; 10 n k must fit the reference's int iteration limit");
+        UgsRwrGraph &d = gd[(size_t)g];
+        d.lo = ptr[g]; d.vbase = ptr[g] - ptr[0]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX);
+        d.T = n >= k ? (int32_t)(n * k * 10) : 0;
+    }
+    const int64_t NV = G > 0 ? ptr[G] - ptr[0] : 0;
+    if (NV >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: vertices must be < 2^31 - 1");
+    DeviceCtx dc;
+    if (int rc = device_ctx(dc)) return rc;
+    const int64_t rows = G * (int64_t)m_per_graph;
+    // one blob: inputs first (uploaded in one copy), then the scratch of every stage
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
+    const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
+                 o_gd = take((size_t)G * sizeof(UgsRwrGraph)), in_bytes = off;
+    const size_t cub_bytes = ugs_rwr_cub_bytes(E);
+    const size_t o_cub = take(cub_bytes), o_hk = take((size_t)E * 8), o_hk2 = take((size_t)E * 8), o_hv = take((size_t)E * 8),
+                 o_hv2 = take((size_t)E * 8), o_rs = take((size_t)(NV + 1) * 4), o_par = take((size_t)NV * 4), o_cs = take((size_t)NV * 4),
+                 o_dm = take((size_t)NV), o_rst = take((size_t)rows * 8), o_ec = take((size_t)rows * 4),
+                 o_st = take((size_t)ugs_scan_tmp_words(rows) * 8), total = off;
+    std::vector<char> host(in_bytes, 0);
+    for (int64_t e = 0; e < E; ++e) {
+        reinterpret_cast<int64_t *>(host.data() + o_src)[e] = edge_index[e];
+        reinterpret_cast<int64_t *>(host.data() + o_dst)[e] = edge_index[row_stride + e];
+    }
+    std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
+    if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsRwrGraph));
+    auto *j = new ugs_job();
+    j->dc = dc; j->rwr = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G; j->rows = rows;
+    auto bail = [&](int rc) { free_job(j); return rc; };
+    if (int rc = pool_get(total, dc.id, j->rwr_blob)) return bail(rc);
+    if (int rc = pool_get((size_t)(rows * k + rows + 1) * sizeof(int64_t), dc.id, j->nodes)) return bail(rc);
+    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + rows * k;
+    char *b = static_cast<char *>(j->rwr_blob.p);
+    UgsRwrCall &c = j->rwr_c;
+    c.G = G; c.E = E; c.NV = NV; c.rows = rows; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed; c.p = p_restart;
+    // speculation window: room for about 16 draws per wanted walk, 1 to 4 offsets per lane
+    c.spec = (int32_t)std::min<int64_t>(4, std::max<int64_t>(1, ((int64_t)m_per_graph * 16 + 255) / 256));
+    c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
+    c.ptr = reinterpret_cast<const int64_t *>(b + o_ptr); c.graphs = reinterpret_cast<const UgsRwrGraph *>(b + o_gd);
+    c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
+    c.hkey = reinterpret_cast<uint32_t *>(b + o_hk); c.hkey2 = reinterpret_cast<uint32_t *>(b + o_hk2);
+    c.hval = reinterpret_cast<int32_t *>(b + o_hv); c.hval2 = reinterpret_cast<int32_t *>(b + o_hv2);
+    c.rs = reinterpret_cast<int32_t *>(b + o_rs); c.parent = reinterpret_cast<int32_t *>(b + o_par);
+    c.csize = reinterpret_cast<int32_t *>(b + o_cs); c.doomed = reinterpret_cast<uint8_t *>(b + o_dm);
+    c.rstart = reinterpret_cast<int64_t *>(b + o_rst); c.ecount = reinterpret_cast<uint32_t *>(b + o_ec);
+    c.scan_tmp = reinterpret_cast<int64_t *>(b + o_st);
+    c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    hipError_t e = hipMemcpyAsync(b, host.data(), in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (e == hipSuccess) e = ugs_rwr_begin(c, dc.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
+    if (e != hipSuccess) return bail(fail_hip(e, "rwr_sampler pipeline"));
+    *job_out = j;
+    if (total_edges_out) *total_edges_out = j->total;
+    return UGS_OK;
+}
+
+int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                int64_t *edge_src, int dst_is_device) {
+    if (!job || !job->rwr) return fail(UGS_E_BAD_ARG, "not an rwr_sampler job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 

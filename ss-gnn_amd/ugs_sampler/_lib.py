@@ -46,6 +46,9 @@ def _load():
         "ugs_uniform_sample_batch_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                            C.POINTER(vp), i64p],
         "ugs_uniform_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
+        "ugs_rwr_sample_batch_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double,
+                                       C.POINTER(vp), i64p],
+        "ugs_rwr_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
