@@ -307,6 +307,29 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
 int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                 int64_t *edge_src, int dst_is_device);
 
+/* ---- uniform_sampler.sample_graphs / rwr_sampler.sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode[, p_restart]): the
+ *      batched form of the reference trainer's presample loop (gps/experiment.py:379-440), which calls the sampler once per graph
+ *      with seed = cfg.seed + i.  Every graph g has its own generator seeds[g], so the graphs are independent.
+ *      The law: graph g's block of m rows -- nodes rows [g m, (g+1) m), their edge entries, edge_ptr re-based -- equals what
+ *      the matching ugs_*_sample_batch_begin gives for the same edge_index with the one-graph ptr {ptr[g], ptr[g+1]} and
+ *      seed = seeds[g]: node ids are batch ids, edge_src holds batch column positions (uniform; -1 for rwr), columns outside
+ *      the graph's range are dropped, both modes.  sample_ptr = [0, m, 2m, ..., G m].
+ *      A graph whose one-graph call would fail with UGS_E_UNSUPPORTED does not fail this call: its block is m rows of -1 without
+ *      edges, it consumes no draws, and graph_status[g] != 0 (0 for every other graph).  Those graphs are, for uniform, one of
+ *      more than 64 vertices and at least k of them, and one whose own |S_g| exceeds the 2^25 device budget; for rwr, one with
+ *      n >= k and 10 n k > INT_MAX.  graph_status is a host array of num_graphs entries, written by begin.
+ *      Errors of the call as a whole stay call errors: the argument errors and limits of ugs_*_sample_batch_begin (rwr: k > 64),
+ *      and, for uniform, healthy graphs whose connected k-subsets TOGETHER exceed the budget (UGS_E_UNSUPPORTED; split the call).
+ *      The library stays usable after any of them.  Finish with ugs_uniform_sample_batch_finish / ugs_rwr_sample_batch_finish.
+ *      Uniform runs one draw workgroup per graph (its mt19937_64 in LDS) instead of sample_batch's single one; rwr only swaps the
+ *      graph's seed seed + g for seeds[g]. */
+int ugs_uniform_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                    int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, int32_t *graph_status,
+                                    ugs_job **job_out, int64_t *total_edges_out);
+int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, double p_restart,
+                                int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
+
 /* ---- apx_ugs_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, epsilon): replaces the reference's
  *      src/samplers/apx_ugs_sampler/src/apx_ugs_sampler.cpp:461-519.  First graph only;
  *      ptr[0]:ptr[1] is a range of edge COLUMNS (:15-33).  The reference draws everything from ONE sequential

@@ -202,6 +202,8 @@ struct UgsUniCall {
     int64_t G, E, nv, rows, budget;          // graphs, columns, enumerated vertices, G * m rows, mask budget
     int32_t m, k, mode;                      // mode 0: "sample" (row positions), otherwise batch ids
     uint64_t seed;
+    const uint64_t *seeds;                   // [G] per-graph generators (ugs_uniform_sample_graphs_begin); nullptr: one for the call
+    int64_t *gcount;                         // [G] per-graph subset count of the count pass (seeds only; > budget: the graph failed)
     const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
     const UgsUniGraph *graphs;               // [G]
     const int32_t *vgraph;                   // [nv] graph of an enumerated vertex
@@ -218,7 +220,7 @@ struct UgsUniCall {
     const uint64_t *keys_sorted;             // set by ugs_uniform_begin: keys_a or keys_b
     int64_t *gstart, *gsize;                 // [G] first key and |S_g|
     int32_t *nepos, *ne_list;                // [G] position among the graphs with S_g non-empty (-1: empty) / its inverse
-    int32_t *draws;                          // [G * m] index into S_g of each draw
+    int32_t *draws;                          // [G * m] index into S_g of each draw (seeds: draw s of graph g at g * m + s)
     uint64_t *rowmask;                       // [rows] subset of each row (0: a row of -1)
     uint32_t *ecount;                        // [rows] edge entries per row
     int64_t *status;                         // [4] running subset count, over-budget flag
@@ -240,6 +242,7 @@ struct UgsRwrCall {
     int64_t G, E, NV, rows;                  // graphs, columns, batch vertices ptr[G] - ptr[0], G * m rows
     int32_t m, k, mode, spec;                // mode 0: "sample" (row positions), otherwise batch ids; window = spec * block offsets
     uint64_t seed;
+    const uint64_t *seeds;                   // [G] generator of each graph (ugs_rwr_sample_graphs_begin); nullptr: seed + g
     double p;                                // p_restart
     const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
     const UgsRwrGraph *graphs;               // [G]

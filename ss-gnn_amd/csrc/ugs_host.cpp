@@ -2781,25 +2781,33 @@ int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_inde
 }
 
 // ---- uniform_sampler.sample_batch (reference src/samplers/uniform_sampler/src/uniform_sampler.cpp) ----
-int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
-                                   int m_per_graph, int k, int mode, uint64_t seed, ugs_job **job_out, int64_t *total_edges_out) {
+// seeds == nullptr: sample_batch, one generator for the call; otherwise sample_graphs: graph g draws from seeds[g], and a graph whose
+// one-graph call would be refused (more than 64 vertices, |S_g| past the budget) fails alone, graph_status[g] = 1.
+static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                         int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
+                         ugs_job **job_out, int64_t *total_edges_out) {
     if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
+    const bool per_graph = seeds != nullptr;
+    if (per_graph && num_graphs >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
     if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
     if (k < 0) return fail(UGS_E_BAD_ARG, "k must be >= 0");
     if (num_cols >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^31 - 1");
     const int64_t G = num_graphs, E = num_cols;
     std::vector<UgsUniGraph> gd((size_t)G);
+    std::vector<int32_t> too_big(per_graph ? (size_t)G : 0, 0);
     int64_t nv = 0;
     for (int64_t g = 0; g < G; ++g) {
         const int64_t n = ptr[g + 1] - ptr[g];
         if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
-        if (k >= 1 && n >= k && n > 64)
+        const bool over = k >= 1 && n >= k && n > 64;
+        if (over && !per_graph)
             return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
                                            " vertices; graphs of more than 64 vertices (and at least k) are not supported");
+        if (over) too_big[(size_t)g] = 1;                               // per-graph: m rows of -1, no draws
         UgsUniGraph &d = gd[(size_t)g];
         d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = nv;
-        d.enumerable = k >= 1 && n >= k ? 1 : 0;
+        d.enumerable = k >= 1 && n >= k && !over ? 1 : 0;
         if (d.enumerable) nv += n;
     }
     DeviceCtx dc;
@@ -2809,7 +2817,9 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
     const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
-                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), in_bytes = off;
+                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), o_seeds = take(per_graph ? (size_t)G * 8 : 0),
+                 in_bytes = off;
+    const size_t o_gc = take(per_graph ? (size_t)G * 8 : 0);
     const size_t cub_bytes = ugs_uniform_cub_bytes(E, nv, budget);
     const size_t o_cub = take(cub_bytes), o_ck = take((size_t)E * 4), o_ck2 = take((size_t)E * 4), o_cv = take((size_t)E * 4),
                  o_cv2 = take((size_t)E * 4), o_cst = take((size_t)(G + 1) * 8), o_bp = take((size_t)E * 2), o_adj = take((size_t)nv * 8),
@@ -2825,6 +2835,7 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
     }
     std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
     if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsUniGraph));
+    if (per_graph && G > 0) std::memcpy(host.data() + o_seeds, seeds, (size_t)G * 8);
     auto *vg = reinterpret_cast<int32_t *>(host.data() + o_vg);
     for (int64_t g = 0; g < G; ++g)
         if (gd[(size_t)g].enumerable) for (int32_t v = 0; v < gd[(size_t)g].n; ++v) vg[gd[(size_t)g].vbase + v] = (int32_t)g;
@@ -2837,6 +2848,8 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
     char *b = static_cast<char *>(j->uni_blob.p);
     UgsUniCall &c = j->uni_c;
     c.G = G; c.E = E; c.nv = nv; c.rows = rows; c.budget = budget; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
+    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + o_seeds) : nullptr;
+    c.gcount = per_graph ? reinterpret_cast<int64_t *>(b + o_gc) : nullptr;
     c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
     c.ptr = reinterpret_cast<const int64_t *>(b + o_ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + o_gd);
     c.vgraph = reinterpret_cast<const int32_t *>(b + o_vg);
@@ -2857,16 +2870,40 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
     if (e == hipSuccess) e = ugs_uniform_begin(c, dc.stream);
     if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
     int64_t status[4] = {0, 0, 0, 0};
+    std::vector<int64_t> gcount(per_graph && nv > 0 ? (size_t)G : 0, 0);   // per-graph subset counts: read back once, with the total
     e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
+    if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
     if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
+    if (status[1] && per_graph)
+        return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the call's graphs together have " + std::to_string(status[0]) +
+                                            " connected k-subsets, more than the device budget of " + std::to_string(budget) +
+                                            "; split the call"));
     if (status[1])
         return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the batch has more than " + std::to_string(budget) +
                                             " connected k-subsets (the device budget; " + std::to_string(status[0]) + " counted before stopping)"));
+    for (int64_t g = 0; per_graph && g < G; ++g)
+        graph_status[g] = too_big[(size_t)g] || (!gcount.empty() && gd[(size_t)g].enumerable && gcount[(size_t)g] > budget) ? 1 : 0;
     *job_out = j;
     if (total_edges_out) *total_edges_out = j->total;
     return UGS_OK;
+}
+
+int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                                   int m_per_graph, int k, int mode, uint64_t seed, ugs_job **job_out, int64_t *total_edges_out) {
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, seed, nullptr, nullptr, job_out,
+                         total_edges_out);
+}
+
+int ugs_uniform_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                    int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, int32_t *graph_status,
+                                    ugs_job **job_out, int64_t *total_edges_out) {
+    if (num_graphs > 0 && (!seeds || !graph_status)) return fail(UGS_E_BAD_ARG, "sample_graphs needs seeds and graph_status");
+    static const uint64_t no_graphs = 0;                                // num_graphs == 0 still takes the per-graph path
+    int32_t no_status = 0;
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds ? seeds : &no_graphs,
+                         graph_status ? graph_status : &no_status, job_out, total_edges_out);
 }
 
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
@@ -2876,9 +2913,12 @@ int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_
 }
 
 // ---- rwr_sampler.sample_batch (reference src/samplers/rwr_sampler/src/rwr_sampler.cpp, one OpenMP thread) ----
-int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
-                               int m_per_graph, int k, int mode, uint64_t seed, double p_restart, ugs_job **job_out,
-                               int64_t *total_edges_out) {
+// seeds == nullptr: sample_batch, graph g seeded with seed + g; otherwise sample_graphs: graph g seeded with seeds[g], and a graph
+// whose one-graph call would be refused (n >= k and 10 n k > INT_MAX) fails alone, graph_status[g] = 1.
+static int rwr_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                     int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status, double p_restart,
+                     ugs_job **job_out, int64_t *total_edges_out) {
+    const bool per_graph = seeds != nullptr;
     if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
@@ -2887,16 +2927,20 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     if (k > UGS_RWR_KMAX) return fail(UGS_E_UNSUPPORTED, "rwr_sampler: k must be <= " + std::to_string(UGS_RWR_KMAX));
     if (num_cols >= ((int64_t)1 << 30)) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^30");
     const int64_t G = num_graphs, E = num_cols;
+    if (per_graph && G >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
     std::vector<UgsRwrGraph> gd((size_t)G);
+    std::vector<int32_t> too_big(per_graph ? (size_t)G : 0, 0);
     for (int64_t g = 0; g < G; ++g) {
         const int64_t n = ptr[g + 1] - ptr[g];
         if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
-        if (n >= k && n > (int64_t)INT32_MAX / (10 * (int64_t)k))
+        const bool over = n >= k && n > (int64_t)INT32_MAX / (10 * (int64_t)k);
+        if (over && !per_graph)
             return fail(UGS_E_UNSUPPORTED, "rwr_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
                                            " vertices; 10 n k must fit the reference's int iteration limit");
+        if (over) too_big[(size_t)g] = 1;                               // per-graph: T = 0, m rows of -1 and no draws
         UgsRwrGraph &d = gd[(size_t)g];
         d.lo = ptr[g]; d.vbase = ptr[g] - ptr[0]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX);
-        d.T = n >= k ? (int32_t)(n * k * 10) : 0;
+        d.T = n >= k && !over ? (int32_t)(n * k * 10) : 0;
     }
     const int64_t NV = G > 0 ? ptr[G] - ptr[0] : 0;
     if (NV >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: vertices must be < 2^31 - 1");
@@ -2907,7 +2951,7 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
     const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
-                 o_gd = take((size_t)G * sizeof(UgsRwrGraph)), in_bytes = off;
+                 o_gd = take((size_t)G * sizeof(UgsRwrGraph)), o_seeds = take(per_graph ? (size_t)G * 8 : 0), in_bytes = off;
     const size_t cub_bytes = ugs_rwr_cub_bytes(E);
     const size_t o_cub = take(cub_bytes), o_hk = take((size_t)E * 8), o_hk2 = take((size_t)E * 8), o_hv = take((size_t)E * 8),
                  o_hv2 = take((size_t)E * 8), o_rs = take((size_t)(NV + 1) * 4), o_par = take((size_t)NV * 4), o_cs = take((size_t)NV * 4),
@@ -2920,6 +2964,7 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     }
     std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
     if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsRwrGraph));
+    if (per_graph && G > 0) std::memcpy(host.data() + o_seeds, seeds, (size_t)G * 8);
     auto *j = new ugs_job();
     j->dc = dc; j->rwr = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G; j->rows = rows;
     auto bail = [&](int rc) { free_job(j); return rc; };
@@ -2929,6 +2974,7 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     char *b = static_cast<char *>(j->rwr_blob.p);
     UgsRwrCall &c = j->rwr_c;
     c.G = G; c.E = E; c.NV = NV; c.rows = rows; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed; c.p = p_restart;
+    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + o_seeds) : nullptr;
     // speculation window: room for about 16 draws per wanted walk, 1 to 4 offsets per lane
     c.spec = (int32_t)std::min<int64_t>(4, std::max<int64_t>(1, ((int64_t)m_per_graph * 16 + 255) / 256));
     c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
@@ -2946,9 +2992,27 @@ int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
     if (e != hipSuccess) return bail(fail_hip(e, "rwr_sampler pipeline"));
+    for (int64_t g = 0; per_graph && g < G; ++g) graph_status[g] = too_big[(size_t)g];
     *job_out = j;
     if (total_edges_out) *total_edges_out = j->total;
     return UGS_OK;
+}
+
+int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int m_per_graph, int k, int mode, uint64_t seed, double p_restart, ugs_job **job_out,
+                               int64_t *total_edges_out) {
+    return rwr_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, seed, nullptr, nullptr, p_restart, job_out,
+                     total_edges_out);
+}
+
+int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                                int m_per_graph, int k, int mode, const uint64_t *seeds, double p_restart, int32_t *graph_status,
+                                ugs_job **job_out, int64_t *total_edges_out) {
+    if (num_graphs > 0 && (!seeds || !graph_status)) return fail(UGS_E_BAD_ARG, "sample_graphs needs seeds and graph_status");
+    static const uint64_t no_graphs = 0;                                // num_graphs == 0 still takes the per-graph path
+    int32_t no_status = 0;
+    return rwr_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds ? seeds : &no_graphs,
+                     graph_status ? graph_status : &no_status, p_restart, job_out, total_edges_out);
 }
 
 int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,

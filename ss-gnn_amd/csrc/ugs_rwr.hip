@@ -2,6 +2,7 @@
 //
 // Contract: src/samplers/rwr_sampler/src/rwr_sampler.cpp with one OpenMP thread (law stated in include/ugs_mi355.h at
 // ugs_rwr_sample_batch_begin): one SplitMix64 per graph seeded with seed + g, its m walks drawn one after the other from it.
+// ugs_rwr_sample_graphs_begin seeds graph g with seeds[g] instead; global_view is the one place that reads either.
 //
 // The draws are counter-based: draw i (1-based) of graph g is mix(seed + g + (i + 1) * GAMMA).  So the walk that starts after
 // c draws is a function of c alone, and so is L(c), the draws it consumes.  The real starts are the chain c0 = 0,
@@ -68,7 +69,7 @@ struct Chosen {
 struct RwrView {
     const int32_t *rs, *tg;
     const uint8_t *doomed;
-    uint64_t sg;          // seed + g
+    uint64_t sg;          // the graph's generator: seed + g, or seeds[g] in a per-graph-seed call
     double p;
     int32_t n, k, T;
 };
@@ -76,7 +77,7 @@ struct RwrView {
 __device__ __forceinline__ RwrView global_view(const UgsRwrCall &c, int64_t g, const UgsRwrGraph &gd) {
     RwrView w;
     w.rs = c.rs + gd.vbase; w.tg = c.hval2; w.doomed = c.doomed + gd.vbase;
-    w.sg = c.seed + (uint64_t)g; w.p = c.p; w.n = gd.n; w.k = c.k; w.T = gd.T;
+    w.sg = c.seeds ? c.seeds[g] : c.seed + (uint64_t)g; w.p = c.p; w.n = gd.n; w.k = c.k; w.T = gd.T;
     return w;
 }
 

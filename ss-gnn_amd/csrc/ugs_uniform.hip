@@ -5,6 +5,10 @@
 // vertex tuples (:47-80), m draws std::uniform_int_distribution<int>(0, |S_g|-1) from ONE std::mt19937_64(seed) per
 // graph with S_g non-empty (:144, :189), edges = the batch columns inside the row's subset, in column order (:193-236).
 //
+// ugs_uniform_sample_graphs_begin (c.seeds != nullptr) gives every graph its own generator and its own budget: the count pass
+// adds into the graph's counter and stops counting a graph once it is past the budget, uni_cap empties the items of such graphs
+// before the scan, uni_joint flags a call whose healthy graphs together are past it, and uni_draw_graphs replaces uni_draw.
+//
 // Pipeline (one stream, no host round trip until the edge total):
 //   uni_colgraph + radix sort   stable bucket of the batch's columns by graph (key = graph id, ties keep column order)
 //   uni_bucket                  per-graph bucket starts; uni_adj: 64-bit neighbour mask per vertex, local (u, v) per column
@@ -12,6 +16,7 @@
 //   uni_esu<WRITE>              the subsets as sort keys ~brev(mask) at their item's offset
 //   uni_sort_small / segmented  per-root buckets sorted ascending by key (bitonic in LDS; large buckets: rocPRIM)
 //   uni_draw                    one workgroup: mt19937_64 + libstdc++'s Lemire step, draws in blocks of 312
+//   uni_draw_graphs             (per-graph seeds) the same, one workgroup and one generator per graph
 //   uni_rows + scan             rows (node ids) and per-row edge counts -> edge_ptr
 //   uni_fill (finish)           edge_index / edge_src
 #include "ugs_device.h"
@@ -67,8 +72,9 @@ __global__ void uni_adj(UgsUniCall c) {
 
 // Extension-set search (Wernicke 2006) of item (root v, first extension w): every connected k-set whose minimum is v and whose
 // first vertex taken from v's extension set is w, each exactly once.  Stack of (ext, closed neighbourhood, set) per level.
-// COUNT: icount[item] = number of sets (the pass gives up once the call's running total exceeds the budget);
-// WRITE: the sets' keys at ioff[item].
+// COUNT: icount[item] = number of sets (the pass gives up once the call's running total exceeds the budget; with per-graph
+// seeds, once the graph's running total does);
+// WRITE: the sets' keys at ioff[item] (nothing for the items of a graph past its budget: uni_cap gave them no room).
 template <int KM, bool WRITE>
 __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
     const int64_t item = (int64_t)blockIdx.x * UNI_BLOCK + threadIdx.x;
@@ -76,7 +82,11 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
     if (WRITE && c.status[1]) return;                               // over budget: nothing is written, begin reports it
     const int64_t vi = item >> 6;
     const int w0 = (int)(item & 63);
-    const UgsUniGraph gd = c.graphs[c.vgraph[vi]];
+    const int32_t gi = c.vgraph[vi];
+    if (WRITE && c.seeds && c.gcount[gi] > c.budget) return;
+    const UgsUniGraph gd = c.graphs[gi];
+    // running total that bounds the work: the call's, or the graph's with per-graph seeds
+    unsigned long long *const ctr = (unsigned long long *)(c.seeds ? &c.gcount[gi] : &c.status[0]);
     const int v = (int)(vi - gd.vbase);
     const uint64_t *adj = c.adj + gd.vbase;
     const int k = c.k;
@@ -101,10 +111,10 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
                         for (uint64_t e = ext[d]; e; e &= e - 1) out[cnt++] = key_of(sub[d] | (e & (0ull - e)));
                     } else {
                         cnt += (uint64_t)__popcll(ext[d]);
-                        if (cnt - flushed >= 4096) {                // bounded work for calls over the budget
-                            const unsigned long long now = atomicAdd((unsigned long long *)&c.status[0], (unsigned long long)(cnt - flushed)) + (cnt - flushed);
+                        if (cnt - flushed >= 4096) {                // bounded work for calls (graphs) over the budget
+                            const unsigned long long now = atomicAdd(ctr, (unsigned long long)(cnt - flushed)) + (cnt - flushed);
                             flushed = cnt;
-                            if (now > (unsigned long long)c.budget) { c.status[1] = 1; break; }
+                            if (now > (unsigned long long)c.budget) { if (!c.seeds) c.status[1] = 1; break; }
                         }
                     }
                     --d;
@@ -124,10 +134,25 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
     if (!WRITE) {
         c.icount[item] = (uint32_t)(cnt < 0xFFFFFFFFull ? cnt : 0xFFFFFFFFull);
         if (cnt > flushed) {
-            const unsigned long long now = atomicAdd((unsigned long long *)&c.status[0], (unsigned long long)(cnt - flushed)) + (cnt - flushed);
-            if (now > (unsigned long long)c.budget) c.status[1] = 1;
+            const unsigned long long now = atomicAdd(ctr, (unsigned long long)(cnt - flushed)) + (cnt - flushed);
+            if (now > (unsigned long long)c.budget && !c.seeds) c.status[1] = 1;
         }
     }
+}
+
+// per-graph seeds, between the count pass and its scan: the items of a graph past the budget hold no sets (it fails alone)
+__global__ void uni_cap(UgsUniCall c) {
+    const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= c.nv * 64) return;
+    if (c.gcount[c.vgraph[item >> 6]] > c.budget) c.icount[item] = 0;
+}
+
+// per-graph seeds, after the scan: the healthy graphs' sets together; past the budget the call fails as a whole
+__global__ void uni_joint(UgsUniCall c) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int64_t total = c.ioff[c.nv * 64];
+    c.status[0] = total;
+    c.status[1] = total > c.budget ? 1 : 0;
 }
 
 // per root bucket: large ones become segments of the radix sort, the others are empty segments there
@@ -207,11 +232,57 @@ __device__ __forceinline__ uint64_t mt_temper(uint64_t y) {
     return y ^ (y >> 43);
 }
 
-// The call's draws, in order: m per graph with S_g non-empty.  Lanes take the next outputs of the generator block, one per draw,
-// assuming each draw consumes exactly one output; a ballot finds the first draw whose Lemire step rejects (lo64(x * N) < t,
-// t = 2^64 mod N).  The draws before it stand, the rejected output is consumed, and that draw is retried on the next output
-// (the same rule: libstdc++'s `lo64 < N` test only skips computing t).  A rejection has probability t / 2^64 <= N / 2^64 < 2^-32
-// per draw, so no test input reaches that branch; tests/uniform_law.py checks the same cursor logic with a stub generator.
+// std::mt19937_64(seed) ([rand.eng.mers]) and its first twist: the first block of 312 outputs, untempered, in mt
+__device__ void mt_seed(uint64_t *mt, uint64_t seed) {
+    if (threadIdx.x == 0) {
+        uint64_t x = seed;
+        mt[0] = x;
+        for (int i = 1; i < MT_N; ++i) { x = 6364136223846793005ull * (x ^ (x >> 62)) + (uint64_t)i; mt[i] = x; }
+    }
+    __syncthreads();
+    mt_twist(mt);
+}
+
+// `total` draws from the seeded generator in mt, draw d uniform over [0, size_of(d)), into out[d].  Lanes take the next outputs
+// of the generator block, one per draw, assuming each draw consumes exactly one output; a ballot finds the first draw whose Lemire
+// step rejects (lo64(x * N) < t, t = 2^64 mod N).  The draws before it stand, the rejected output is consumed, and that draw is
+// retried on the next output (the same rule: libstdc++'s `lo64 < N` test only skips computing t).  A rejection has probability
+// t / 2^64 <= N / 2^64 < 2^-32 per draw, so no test input reaches that branch; tests/uniform_law.py (draws_blocked) checks the
+// same cursor logic with a stub generator.  Called by all DRAW_BLOCK lanes of a workgroup.
+template <class SizeOf>
+__device__ void mt_draws(uint64_t *mt, int64_t total, SizeOf size_of, int32_t *out, int32_t *s_wave, int *s_first) {
+    const int tid = threadIdx.x;
+    int pos = 0;                                                    // next unused output of the block
+    int64_t d0 = 0;                                                 // next draw
+    while (d0 < total) {
+        const int avail = MT_N - pos;
+        const int64_t todo = total - d0 < avail ? total - d0 : avail;
+        bool reject = false;
+        int32_t r = 0;
+        if (tid < todo) {
+            const int64_t d = d0 + tid;
+            const uint64_t N = size_of(d);
+            const uint64_t x = mt_temper(mt[pos + tid]);
+            const uint64_t lo = x * N;
+            if (lo < N) reject = lo < (0ull - N) % N;
+            r = (int32_t)__umul64hi(x, N);
+        }
+        const unsigned long long bal = __ballot(reject);
+        if ((tid & 63) == 0) s_wave[tid >> 6] = bal ? (tid & ~63) + __ffsll(bal) - 1 : DRAW_BLOCK;
+        __syncthreads();
+        if (tid == 0) { int f = DRAW_BLOCK; for (int wv = 0; wv < DRAW_BLOCK / 64; ++wv) f = min(f, s_wave[wv]); *s_first = f; }
+        __syncthreads();
+        const int first = *s_first;
+        if (tid < todo && tid < first) out[d0 + tid] = r;
+        const int taken = first < todo ? first : (int)todo;
+        d0 += taken;
+        pos += taken + (first < todo ? 1 : 0);                      // a rejected output is consumed, its draw retried
+        __syncthreads();
+        if (pos == MT_N) { mt_twist(mt); pos = 0; }
+    }
+}
+
+// The call's draws, in order: m per graph with S_g non-empty, all from ONE std::mt19937_64(seed) -- one workgroup.
 __global__ __launch_bounds__(DRAW_BLOCK) void uni_draw(UgsUniCall c) {
     __shared__ uint64_t mt[MT_N];
     __shared__ int32_t s_flag[DRAW_BLOCK];
@@ -245,41 +316,22 @@ __global__ __launch_bounds__(DRAW_BLOCK) void uni_draw(UgsUniCall c) {
     }
     const int64_t total = (int64_t)s_ne * c.m;
     if (total == 0) return;
-    if (tid == 0) {                                                 // std::mt19937_64(seed) ([rand.eng.mers])
-        uint64_t x = c.seed;
-        mt[0] = x;
-        for (int i = 1; i < MT_N; ++i) { x = 6364136223846793005ull * (x ^ (x >> 62)) + (uint64_t)i; mt[i] = x; }
-    }
-    __syncthreads();
-    mt_twist(mt);
-    int pos = 0;                                                    // next unused output of the block
-    int64_t d0 = 0;                                                 // next draw
-    while (d0 < total) {
-        const int avail = MT_N - pos;
-        const int64_t todo = total - d0 < avail ? total - d0 : avail;
-        bool reject = false;
-        int32_t r = 0;
-        if (tid < todo) {
-            const int64_t d = d0 + tid;
-            const uint64_t N = (uint64_t)c.gsize[c.ne_list[d / c.m]];
-            const uint64_t x = mt_temper(mt[pos + tid]);
-            const uint64_t lo = x * N;
-            if (lo < N) reject = lo < (0ull - N) % N;
-            r = (int32_t)__umul64hi(x, N);
-        }
-        const unsigned long long bal = __ballot(reject);
-        if ((tid & 63) == 0) s_wave[tid >> 6] = bal ? (tid & ~63) + __ffsll(bal) - 1 : DRAW_BLOCK;
-        __syncthreads();
-        if (tid == 0) { int f = DRAW_BLOCK; for (int wv = 0; wv < DRAW_BLOCK / 64; ++wv) f = min(f, s_wave[wv]); s_first = f; }
-        __syncthreads();
-        const int first = s_first;
-        if (tid < todo && tid < first) c.draws[d0 + tid] = r;
-        const int taken = first < todo ? first : (int)todo;
-        d0 += taken;
-        pos += taken + (first < todo ? 1 : 0);                      // a rejected output is consumed, its draw retried
-        __syncthreads();
-        if (pos == MT_N) { mt_twist(mt); pos = 0; }
-    }
+    mt_seed(mt, c.seed);
+    mt_draws(mt, total, [&](int64_t d) { return (uint64_t)c.gsize[c.ne_list[d / c.m]]; }, c.draws, s_wave, &s_first);
+}
+
+// Per-graph seeds: workgroup g draws graph g's m draws from its own std::mt19937_64(seeds[g]) into draws[g * m ..].  Graphs
+// with S_g empty (n < k, not enumerable, past the budget) leave at once: they consume no draws.
+__global__ __launch_bounds__(DRAW_BLOCK) void uni_draw_graphs(UgsUniCall c) {
+    __shared__ uint64_t mt[MT_N];
+    __shared__ int32_t s_wave[DRAW_BLOCK / 64];
+    __shared__ int s_first;
+    const int64_t g = blockIdx.x;
+    if (c.status[1] || c.m == 0) return;
+    const uint64_t N = (uint64_t)c.gsize[g];
+    if (N == 0) return;
+    mt_seed(mt, c.seeds[g]);
+    mt_draws(mt, (int64_t)c.m, [&](int64_t) { return N; }, c.draws + g * (int64_t)c.m, s_wave, &s_first);
 }
 
 // row b = g * m + s: the drawn subset's vertices ascending (or -1) and its edge count over the graph's column bucket
@@ -289,7 +341,10 @@ __global__ void uni_rows(UgsUniCall c) {
     const int64_t g = row / c.m, s = row - g * c.m;
     int64_t *out = c.nodes + row * c.k;
     uint64_t mask = 0;
-    if (!c.status[1] && c.gsize[g] > 0) mask = mask_of(c.keys_sorted[c.gstart[g] + c.draws[(int64_t)c.nepos[g] * c.m + s]]);
+    if (!c.status[1] && c.gsize[g] > 0) {
+        const int64_t d = c.seeds ? row : (int64_t)c.nepos[g] * c.m + s;   // per-graph seeds: graph g's draws at g * m
+        mask = mask_of(c.keys_sorted[c.gstart[g] + c.draws[d]]);
+    }
     c.rowmask[row] = mask;
     uint32_t cnt = 0;
     if (mask) {
@@ -363,9 +418,12 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s) {
         if ((e = hipMemsetAsync(c.adj, 0, (size_t)c.nv * sizeof(uint64_t), s)) != hipSuccess) return e;
         if (c.E > 0) hipLaunchKernelGGL(uni_adj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         const int64_t items = c.nv * 64;
+        if (c.seeds && (e = hipMemsetAsync(c.gcount, 0, (size_t)c.G * sizeof(int64_t), s)) != hipSuccess) return e;
         if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, false>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         else hipLaunchKernelGGL((uni_esu<64, false>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        if (c.seeds) hipLaunchKernelGGL(uni_cap, dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         if ((e = ugs_launch_scan(c.icount, items, c.ioff, c.scan_tmp, s)) != hipSuccess) return e;
+        if (c.seeds) hipLaunchKernelGGL(uni_joint, dim3(1), dim3(64), 0, s, c);
         if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, true>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         else hipLaunchKernelGGL((uni_esu<64, true>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         // root buckets larger than LDS: rocPRIM's segmented radix sort (the others are empty segments there)
@@ -379,7 +437,8 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s) {
     }
     if (c.G > 0) {
         hipLaunchKernelGGL(uni_graph_sizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
-        hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
+        if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
+        else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
     }
     if (c.rows > 0) hipLaunchKernelGGL(uni_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
     if ((e = hipGetLastError()) != hipSuccess) return e;

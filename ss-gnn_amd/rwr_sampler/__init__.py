@@ -7,14 +7,18 @@ Random walk with restart, bit-exact with the reference run with one OpenMP threa
 SplitMix64 stream per graph, its m walks one after the other.  The walks, rows and edges run in HIP kernels (ugs_rwr.hip); the law
 is stated in include/ugs_mi355.h at ugs_rwr_sample_batch_begin.  k > 64 and graphs whose 10 n k iteration limit overflows the
 reference's int raise RuntimeError.
+
+sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", p_restart=0.2) -> the 5-tuple + failed[G] (bool): graph g
+seeded with seeds[g] instead of seed + g (the presample loop batched; law at ugs_rwr_sample_graphs_begin).
 """
 import ctypes as C
 
 import torch
 
+from ugs_sampler import _graphs
 from ugs_sampler._lib import check, lib, vp
 
-__all__ = ["sample_batch"]
+__all__ = ["sample_batch", "sample_graphs"]
 
 
 def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, p_restart=0.2):
@@ -59,3 +63,20 @@ def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, p_rest
     check(lib.ugs_rwr_sample_batch_finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(),
                                           esrc.data_ptr(), 1 if on_dev else 0))
     return nodes, eidx, eptr, sptr, esrc
+
+
+def sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", p_restart=0.2):
+    """Many one-graph calls in one: graph g's block of m rows equals sample_batch(edge_index, ptr[g:g+2], m_per_graph, k, mode,
+    seeds[g], p_restart) with edge_ptr re-based (node ids are batch ids, edge_src -1).  A graph whose one-graph call would raise
+    (n >= k and 10 n k past the reference's int) gives m rows of -1 and failed[g] = True instead.
+    Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src, failed), on the device of `edge_index`."""
+    out, failed = _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode, p_restart)
+    return out + (failed.to(out[0].device),)
+
+
+def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", p_restart=0.2, device=None):
+    """sample_graphs with `failed` left on the host and the outputs on `device` (PresampleCache.add_many)"""
+    p = C.c_double(float(p_restart))
+    return _graphs.sample_graphs(lambda ei, rs, nc, pt, G, m, kk, md, sd, st, job, tot:
+                                 lib.ugs_rwr_sample_graphs_begin(ei, rs, nc, pt, G, m, kk, md, sd, p, st, job, tot),
+                                 lib.ugs_rwr_sample_batch_finish, edge_index, ptr, m_per_graph, k, seeds, mode, device)

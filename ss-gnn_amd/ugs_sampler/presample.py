@@ -7,49 +7,185 @@ edge_src re-based by the number of batch columns that belong to earlier graphs, 
 with `.item()` per graph and per sample.  Here the cache lives in HBM as flat tensors and a batch is assembled by a handful of
 device gathers; the sizes that decide the output shapes are known on the host from build time, so nothing synchronises.
 
-    cache = PresampleCache(m, k, device="cuda:0")
-    for i, data in enumerate(dataset):                       # start-up, like _setup_presampling
-        cache.add(i, data.edge_index, data.num_nodes, seed=cfg.seed + i)
+    cache = PresampleCache(m, k, device="cuda:0", sampler="rwr")   # "ugs" (default), "uniform" or "rwr": the config's sampler
+    cache.add_many(range(len(dataset)), [(d.edge_index, d.num_nodes) for d in dataset],
+                   [cfg.seed + i for i in range(len(dataset))])    # start-up, like _setup_presampling
     cache.finalize()
     nodes, edge_index, edge_ptr, sample_ptr, edge_src = cache.load(batch.graph_idx, batch.ptr, batch.edge_index)
+
+`add(i, edge_index, num_nodes, seed)` presamples one graph with the sampler's drop-in call, exactly like one iteration of the
+reference's loop; `add_many` leaves the cache exactly as the loop of `add` over its arguments would.  For "uniform" and "rwr" it
+samples the graphs in a few batched calls (uniform_sampler.sample_graphs / rwr_sampler.sample_graphs: one seed per graph), for
+"ugs" it is that loop.  `failed` is the set of indices whose presampling failed.
 
 `load` returns exactly what the reference's `_load_from_presample_cache` stores on the batch -- including its treatment of
 graphs whose presampling failed (m rows of -1 to which ptr[g] is ADDED like to every other row, no edges).
 """
+import numpy as np
 import torch
 
 from . import sample_batch
 
+SAMPLERS = ("ugs", "uniform", "rwr")
+# add_many's call bounds.  Vertices: the uniform count pass keeps 12 B per (root, first extension) item and 64 items per vertex,
+# 768 B per vertex, so 2^17 vertices hold about 100 MB of item arrays (a whole QM9 split would need gigabytes).  Rows: the
+# outputs and per-row scratch of 2^21 rows are about 130 MB at k = 6.  A graph larger than a bound is a call of its own.
+CHUNK_VERTICES = 1 << 17
+CHUNK_ROWS = 1 << 21
+_JOINT_BUDGET = "split the call"       # uniform_sampler: healthy graphs that together exceed the device budget
+
+
+def _drop_in(sampler):
+    if sampler == "uniform":
+        import uniform_sampler
+        return uniform_sampler
+    import rwr_sampler
+    return rwr_sampler
+
 
 class PresampleCache:
-    def __init__(self, m, k, device):
+    def __init__(self, m, k, device, sampler="ugs", p_restart=0.2, chunk_vertices=CHUNK_VERTICES, chunk_rows=CHUNK_ROWS):
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
         self.m, self.k = int(m), int(k)
         self.dev = torch.device(device)
+        self.sampler, self.p_restart = sampler, float(p_restart)
+        self.chunk_vertices, self.chunk_rows = max(int(chunk_vertices), 1), max(int(chunk_rows), 1)
+        self.failed = set()             # indices whose presampling failed
         self._slot = {}                 # graph index -> slot (-1: presampling failed)
-        self._parts = []                # per slot: (nodes [m,k], edge_index [2,E], edge_ptr [m+1], edge_src [E]) on the device
+        # blocks of consecutive slots: (nodes [S*m,k], edge_index [2,E], edge_ptr [S,m+1], edge_src [E], edges per slot [S]) on the device
+        self._parts = []
+        self._nslots = 0
+        self._final = None
+
+    def _call(self, edge_index, num_nodes, seed):
+        ptr = torch.tensor([0, int(num_nodes)], dtype=torch.long)
+        if self.sampler == "ugs":
+            return sample_batch(edge_index.cpu(), ptr, self.m, self.k, mode="sample", seed=int(seed), device=self.dev)
+        mod = _drop_in(self.sampler)
+        ei = edge_index.to(self.dev)    # device in, device out
+        if self.sampler == "rwr":
+            return mod.sample_batch(ei, ptr, self.m, self.k, mode="sample", seed=int(seed), p_restart=self.p_restart)
+        return mod.sample_batch(ei, ptr, self.m, self.k, mode="sample", seed=int(seed))
+
+    def _fail(self, index):
+        self._slot[index] = -1
+        self.failed.add(index)
+
+    def _append(self, indices, ok, nodes, eidx, eptr, esrc, n_edges):
+        base = self._nslots
+        j = 0
+        for i, good in zip(indices, ok):
+            if good:
+                self._slot[i] = base + j
+                self.failed.discard(i)
+                j += 1
+            else:
+                self._fail(i)
+        self._parts.append((nodes, eidx, eptr, esrc, n_edges))
+        self._nslots += j
         self._final = None
 
     def add(self, index, edge_index, num_nodes, seed):
         """Presample one graph (reference: experiment.py:403-430); a sampler error marks the graph as failed, like the reference."""
-        ptr = torch.tensor([0, int(num_nodes)], dtype=torch.long)
         try:
-            nodes, eidx, eptr, _, esrc = sample_batch(edge_index.cpu(), ptr, self.m, self.k, mode="sample", seed=int(seed), device=self.dev)
+            nodes, eidx, eptr, _, esrc = self._call(edge_index, num_nodes, seed)
         except Exception:   # noqa: BLE001  (the reference swallows every exception here)
-            self._slot[int(index)] = -1
+            self._fail(int(index))
             return False
-        self._slot[int(index)] = len(self._parts)
-        self._parts.append((nodes, eidx, eptr, esrc))
-        self._final = None
+        self._append([int(index)], [True], nodes, eidx, eptr.unsqueeze(0), esrc, [int(eidx.size(1))])
         return True
+
+    def add_many(self, indices, graphs, seeds):
+        """Presample many graphs: `graphs` holds (edge_index, num_nodes) per index, `seeds` one seed per index.  Leaves the cache
+        exactly as `for i, (ei, n), s in zip(indices, graphs, seeds): add(i, ei, n, s)` would, failures included."""
+        indices = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
+        graphs = list(graphs)
+        seeds = [int(s) for s in (seeds.tolist() if torch.is_tensor(seeds) else seeds)]
+        if not (len(indices) == len(graphs) == len(seeds)):
+            raise ValueError("indices, graphs and seeds must have the same length")
+        if self.sampler == "ugs":       # a batched ugs form would need per-graph seed bases in the walk kernel
+            for i, (ei, n), s in zip(indices, graphs, seeds):
+                self.add(i, ei, n, s)
+            return
+        run, nv, rows = [], 0, 0        # graphs of the current call, in order
+        for t, (ei, n) in enumerate(graphs):
+            regular = torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.size(0) == 2 and int(n) >= 0
+            if not regular:             # whatever add makes of it, in its place in the order
+                self._batched(run)
+                run, nv, rows = [], 0, 0
+                self.add(indices[t], ei, n, seeds[t])
+                continue
+            n = int(n)
+            if run and (nv + n > self.chunk_vertices or rows + self.m > self.chunk_rows):
+                self._batched(run)
+                run, nv, rows = [], 0, 0
+            run.append((indices[t], ei, n, seeds[t]))
+            nv += n
+            rows += self.m
+        self._batched(run)
+
+    def _batched(self, run):
+        """One sample_graphs call over `run` ([(index, edge_index, n, seed)]): halves a uniform call refused for the joint budget,
+        and falls back to `add` per graph on any other call error."""
+        if not run:
+            return
+        G, m, k = len(run), self.m, self.k
+        n = np.array([g[2] for g in run], np.int64)
+        ptr = np.zeros(G + 1, np.int64)
+        np.cumsum(n, out=ptr[1:])
+        cols = [g[1].detach().cpu().numpy() for g in run]
+        ncol = np.array([c.shape[1] for c in cols], np.int64)
+        col0 = np.zeros(G + 1, np.int64)
+        np.cumsum(ncol, out=col0[1:])
+        ei = np.concatenate(cols, axis=1) if G else np.zeros((2, 0), np.int64)
+        # columns with an endpoint outside [0, n) become (-1, -1): dropped as in the one-graph call, never in a neighbour's range,
+        # and every other column keeps its position
+        gid = np.repeat(np.arange(G, dtype=np.int64), ncol)
+        bad = ((ei < 0) | (ei >= n[gid])).any(axis=0)
+        ei = np.where(bad, -1, ei + ptr[gid])
+        mod = _drop_in(self.sampler)
+        extra = dict(p_restart=self.p_restart) if self.sampler == "rwr" else {}
+        try:
+            (nodes, eidx, eptr, _, esrc), failed = mod._sample_graphs(torch.from_numpy(ei), torch.from_numpy(ptr), m, k,
+                                                                      [g[3] for g in run], "sample",
+                                                                      device=self.dev, **extra)
+        except RuntimeError as e:
+            if self.sampler == "uniform" and G > 1 and _JOINT_BUDGET in str(e):
+                self._batched(run[:G // 2])
+                self._batched(run[G // 2:])
+            else:
+                for i, e_i, n_i, s in run:
+                    self.add(i, e_i, n_i, s)
+            return
+        # back to the one-graph form: local node ids, edge_src local to the graph's own columns (rwr's -1 stays), edge_ptr per graph
+        dev = nodes.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        ptr_d = torch.from_numpy(ptr).to(dev)
+        nodes = torch.where(nodes >= 0, nodes - ptr_d[:G].repeat_interleave(m).unsqueeze(1), nodes)
+        bound = (torch.arange(G + 1, **i64) * m).clamp(max=eptr.numel() - 1)
+        per_graph = eptr.index_select(0, bound).cpu()                       # edge entries before each graph: the one read-back
+        cnt = (per_graph[1:] - per_graph[:-1]).to(dev)
+        total = int(per_graph[-1])
+        seg = torch.repeat_interleave(torch.arange(G, **i64), cnt, output_size=total)
+        esrc = torch.where(esrc >= 0, esrc - torch.from_numpy(col0[:G]).to(dev).index_select(0, seg), esrc)
+        eptr = eptr.index_select(0, ((torch.arange(G, **i64) * m).unsqueeze(1) + torch.arange(m + 1, **i64)).reshape(-1)).reshape(G, m + 1)
+        eptr = eptr - eptr[:, :1]
+        ok = ~failed
+        if not bool(ok.all()):                                            # failed graphs have rows of -1 and no edges
+            keep = torch.nonzero(ok).flatten().to(dev)
+            nodes = nodes.reshape(G, m, k).index_select(0, keep).reshape(keep.numel() * m, k)
+            eptr = eptr.index_select(0, keep)
+        n_edges = (per_graph[1:] - per_graph[:-1])[ok].tolist()
+        self._append([g[0] for g in run], ok.tolist(), nodes, eidx, eptr, esrc, n_edges)
 
     def finalize(self):
         m, k, dev = self.m, self.k, self.dev
-        S = len(self._parts)
         i64 = dict(dtype=torch.int64, device=dev)
         # slot S is the placeholder of failed graphs: m rows of -1, no edges
         self.nodes = torch.cat([p[0] for p in self._parts] + [torch.full((m, k), -1, **i64)], dim=0)                     # [(S+1)*m, k]
-        self.eptr_local = torch.stack([p[2] for p in self._parts] + [torch.zeros(m + 1, **i64)], dim=0)                 # [S+1, m+1]
-        self.n_edges_host = [int(p[1].size(1)) for p in self._parts] + [0]                                              # host, no sync later
+        self.eptr_local = torch.cat([p[2] for p in self._parts] + [torch.zeros(1, m + 1, **i64)], dim=0)                # [S+1, m+1]
+        self.n_edges_host = [c for p in self._parts for c in p[4]] + [0]                                                 # host, no sync later
         self.eidx = torch.cat([p[1] for p in self._parts] + [torch.empty((2, 0), **i64)], dim=1)                         # [2, Etot]
         self.esrc = torch.cat([p[3] for p in self._parts] + [torch.empty((0,), **i64)], dim=0)
         base = [0]

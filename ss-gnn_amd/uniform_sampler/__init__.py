@@ -7,14 +7,19 @@ Exact uniform sampling over every connected k-subset of each graph, bit-exact wi
 ordered and drawn from (std::mt19937_64 + libstdc++'s uniform_int_distribution) in HIP kernels (ugs_uniform.hip).  The law is
 stated in include/ugs_mi355.h at ugs_uniform_sample_batch_begin.  Graphs of more than 64 vertices (with at least k of them)
 raise RuntimeError, as does a batch with more connected k-subsets than the device budget.
+
+sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample") -> the 5-tuple + failed[G] (bool): one call for many
+one-graph calls, graph g drawn from its own std::mt19937_64(seeds[g]) by its own workgroup (the presample loop batched; law at
+ugs_uniform_sample_graphs_begin; a graph sample_batch would refuse fails alone).
 """
 import ctypes as C
 
 import torch
 
+from ugs_sampler import _graphs
 from ugs_sampler._lib import check, lib, vp
 
-__all__ = ["sample_batch"]
+__all__ = ["sample_batch", "sample_graphs"]
 
 
 def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42):
@@ -59,3 +64,19 @@ def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42):
     check(lib.ugs_uniform_sample_batch_finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(),
                                               esrc.data_ptr(), 1 if on_dev else 0))
     return nodes, eidx, eptr, sptr, esrc
+
+
+def sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample"):
+    """Many one-graph calls in one: graph g's block of m rows equals sample_batch(edge_index, ptr[g:g+2], m_per_graph, k, mode,
+    seeds[g]) with edge_ptr re-based (node ids are batch ids, edge_src batch column positions).  A graph whose one-graph call
+    would raise (more than 64 vertices and at least k, more connected k-subsets than the device budget) gives m rows of -1 and
+    failed[g] = True instead; healthy graphs that together exceed the budget raise RuntimeError (split the call).
+    Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src, failed), on the device of `edge_index`."""
+    out, failed = _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode)
+    return out + (failed.to(out[0].device),)
+
+
+def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", device=None):
+    """sample_graphs with `failed` left on the host and the outputs on `device` (PresampleCache.add_many)"""
+    return _graphs.sample_graphs(lib.ugs_uniform_sample_graphs_begin, lib.ugs_uniform_sample_batch_finish, edge_index, ptr,
+                                 m_per_graph, k, seeds, mode, device)

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Presampling a whole dataset with uniform_sampler / rwr_sampler: the reference trainer's loop of one-graph calls
+(PresampleCache.add per graph, gps/experiment.py:379-440) against PresampleCache.add_many (a few sample_graphs calls).
+
+Two synthetic datasets (ugs_workloads.tu_graph, both edge directions stored):
+  proteins  1113 graphs, PROTEINS-like sizes (mean 39 vertices, 1.86 undirected edges per vertex), clipped to 4..64 vertices so
+            that every graph is within uniform_sampler's 64-vertex limit;
+  qm9       20 000 graphs of 9..29 vertices, 1.04 undirected edges per vertex.
+uniform runs at k = 6, m = 64 and rwr at k = 5, m = 50, seeds 42 + i.  Timings are wall time to a synchronised device, after a
+warm-up on the first 64 graphs: add_many the median of three runs, the loop one run; both caches are checked equal (load of every graph) before the numbers are written.
+
+    python tools/presample_bench.py [--only qm9] [--sampler rwr] [--out profiles/presample_bench.json]
+    python tools/presample_bench.py --only qm9 --many-only        # add_many alone, e.g. under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ss-gnn_amd"))
+import ugs_workloads as wl  # noqa: E402
+from ugs_sampler.presample import PresampleCache  # noqa: E402
+
+CONFIGS = {"uniform": dict(k=6, m=64), "rwr": dict(k=5, m=50)}
+
+
+def dataset(name):
+    rng = np.random.default_rng(1113 if name == "proteins" else 20000)
+    if name == "proteins":
+        sizes = np.clip(np.round(rng.gamma(2.2, 39.06 / 2.2, 1113)), 4, 64).astype(int)
+        und = np.round(sizes * 1.86).astype(int)
+    else:
+        sizes = rng.integers(9, 30, 20000)
+        und = np.round(sizes * 1.04).astype(int)
+    return [(torch.from_numpy(wl.tu_graph(int(n), int(e), 7 * i + 1)), int(n)) for i, (n, e) in enumerate(zip(sizes, und))]
+
+
+def sync():
+    torch.cuda.synchronize()
+
+
+def build_loop(cache, graphs, seeds):
+    for i, ((ei, n), s) in enumerate(zip(graphs, seeds)):
+        cache.add(i, ei, n, s)
+
+
+def timed(fn):
+    sync()
+    t0 = time.perf_counter()
+    fn()
+    sync()
+    return time.perf_counter() - t0
+
+
+def same(a, b, G):
+    assert a.failed == b.failed, "failed sets differ"
+    order = list(range(G))
+    ptr = torch.zeros(G + 1, dtype=torch.int64)                  # load's edge_src offsets need the batch: an empty one will do here
+    for x, y in zip(a.load(order, ptr, torch.zeros((2, 0), dtype=torch.int64)), b.load(order, ptr, torch.zeros((2, 0), dtype=torch.int64))):
+        assert torch.equal(x, y), "caches differ"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["proteins", "qm9"])
+    ap.add_argument("--sampler", choices=list(CONFIGS))
+    ap.add_argument("--many-only", action="store_true", help="time add_many alone (no loop, no check, no file)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "presample_bench.json"))
+    a = ap.parse_args()
+    dev = "cuda:0"
+    results = []
+    for dname in [a.only] if a.only else ["proteins", "qm9"]:
+        graphs = dataset(dname)
+        G = len(graphs)
+        seeds = [42 + i for i in range(G)]
+        nv = sum(n for _, n in graphs)
+        for sname in [a.sampler] if a.sampler else list(CONFIGS):
+            cfg = CONFIGS[sname]
+            warm = PresampleCache(cfg["m"], cfg["k"], dev, sampler=sname)
+            warm.add_many(range(64), graphs[:64], seeds[:64])
+            if not a.many_only:
+                build_loop(PresampleCache(cfg["m"], cfg["k"], dev, sampler=sname), graphs[:64], seeds[:64])
+            ts = []
+            for _ in range(3):                                  # median of three fresh caches
+                many = PresampleCache(cfg["m"], cfg["k"], dev, sampler=sname)
+                ts.append(timed(lambda: many.add_many(range(G), graphs, seeds)))
+            t_many = sorted(ts)[1]
+            rec = dict(dataset=dname, sampler=sname, graphs=G, vertices=nv, k=cfg["k"], m=cfg["m"], add_many_s=round(t_many, 4),
+                       add_many_us_per_graph=round(1e6 * t_many / G, 2), failed=len(many.failed))
+            if not a.many_only:
+                loop = PresampleCache(cfg["m"], cfg["k"], dev, sampler=sname)
+                t_loop = timed(lambda: build_loop(loop, graphs, seeds))
+                same(loop, many, G)
+                rec.update(add_loop_s=round(t_loop, 4), add_loop_us_per_graph=round(1e6 * t_loop / G, 2),
+                           speedup=round(t_loop / t_many, 2), caches_equal=True)
+            print(json.dumps(rec), flush=True)
+            results.append(rec)
+    if not a.many_only:
+        meta = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, hip=torch.version.hip,
+                    note="wall time to a synchronised device; add_loop = PresampleCache.add per graph (the reference's loop), "
+                         "add_many = batched sample_graphs calls")
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(dict(meta=meta, results=results), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
