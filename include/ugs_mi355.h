@@ -102,6 +102,24 @@ int ugs_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, i
                             int64_t *sample_ptr, int64_t *edge_src_global, int dst_is_device);
 int ugs_job_cancel(ugs_job *job);
 
+/* ---- ugs_sampler.sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode): sample_batch with one seed per graph -- the batched
+ *      form of the reference trainer's presample loop (gps/experiment.py:379-440: one one-graph call per dataset graph,
+ *      seed = cfg.seed + i).
+ *      The law: the call returns exactly what ugs_sample_batch_begin(edge_index, ptr, m_per_graph, k, mode, seed) returns for the
+ *      same batch, except that row b = g m + i draws from xorshift64*((uint64_t)(int64_t)seeds[g] + i 0x9e3779b97f4a7c15) instead
+ *      of from `seed`.  Everything else is sample_batch's behaviour: the preprocessing LRU visited once per graph in graph order
+ *      (its key ignores k), evictions, graphs of fewer than k vertices (m rows of -1), the three modes, sample_ptr.
+ *      Consequence: graph g's block of m rows -- edge_ptr re-based, and in mode "sample" ptr[g] subtracted from the nodes and
+ *      the graph's first column from edge_src -- equals the one-graph call sample_batch(columns of g, {0, n_g}, m, k, mode,
+ *      seeds[g]) made as the g-th of a sequence of such calls on the same LRU: the reference's sample_batch does the same get / put
+ *      per graph that separate calls do.  That block is therefore what the reference's presample loop caches for graph g.
+ *      seeds: host array of num_graphs C ints (the one-graph call's seed type); must not be NULL when num_graphs > 0.
+ *      Same argument checks and errors as ugs_sample_batch_begin, same job: finish with ugs_sample_batch_finish.  The plan comes
+ *      from ugs_plan_create_batch (LRU replay, device batch pass); no streamed form and no early start. -------------------- */
+int ugs_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                            int64_t num_graphs, int m_per_graph, int k, int mode, const int32_t *seeds, ugs_job **job_out,
+                            int64_t *total_edges_out);
+
 /* The same call (reference src/ugs_sampler_batch_extension.cpp:77-299, same LRU, same results) for LARGE host-visible batches,
  * in one piece: the caller hands over its (pinned) host buffers up front -- nodes[G*m,k], edge_ptr[G*m+1], sample_ptr[G+1],
  * edge_src_global[edge_capacity] and edge_index_out[2*edge_capacity] -- and the rows are sampled in chunks whose results cross

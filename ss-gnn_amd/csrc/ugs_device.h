@@ -98,6 +98,10 @@ struct UgsWalkArgs {
     uint2 *stage;            // [row_count, UGS_STAGE_ITEMS]: x = batch column, y = source local index | target local index << 8
     int64_t *ulist;          // rows (relative) with edges that are NOT staged
     uint32_t *ucount;
+    // per-graph seeds (ugs_sample_graphs_begin; NULL = off): [plan.num_graphs] seed bases (uint64_t)(int64_t)seed_g -- the rows of graph
+    // gi draw from seeds[gi] instead of seed64 / *seed_ptr.  Last member, and read only by the walk kernels' SEEDS instantiations
+    // (ugs_launch_walk picks them when it is set): the kernels of every other call are the code they were without it.
+    const uint64_t *seeds;
 };
 #define UGS_COUNT_STAGED 0x80000000u
 #define UGS_STAGE_ENTRIES 32    /* undirected hits a walk can hold in LDS */

@@ -1782,16 +1782,16 @@ int ugs_plan_info(const ugs_plan *plan, int k, int64_t *num_graphs, int64_t *num
 }
 
 static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, const uint64_t *d_seed_ptr,
-                          int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
+                          const uint64_t *d_seeds, int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
                           bool *defer_scan = nullptr, bool poll_total = false);
 static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed,
-                            const uint64_t *d_seed_ptr, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
+                            const uint64_t *d_seed_ptr, const uint64_t *d_seeds, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
                             int64_t *total_edges_host, bool *defer_scan, bool poll_total);
 
 
 int ugs_plan_walk(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, int64_t row_begin,
                   int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host) {
-    return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, total_edges_host);
+    return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, total_edges_host);
 }
 
 // the argument checks of a walk; its device made current
@@ -1812,7 +1812,7 @@ static int walk_check(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t 
 // their adjacency, nothing is staged), no capture in progress -- the scan launch is left out and *defer_scan set.  The caller then
 // launches that fill without letting go of plan->mu in between (plan_walk_locked).
 static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed, const uint64_t *d_seed_ptr,
-                          int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
+                          const uint64_t *d_seeds, int64_t row_begin, int64_t row_count, void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *total_edges_host,
                           bool *defer_scan, bool poll_total) {
     if (defer_scan) *defer_scan = false;
     if (int rc = walk_check(plan, m_per_graph, k, mode, row_begin, row_count, d_nodes, d_edge_ptr)) return rc;
@@ -1824,7 +1824,7 @@ static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int6
     }
     const TierChoice tc = choose_tier(plan, k);
     std::lock_guard<std::mutex> lk(plan->mu);
-    return plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, d_seed_ptr, row_begin, row_count, s, d_nodes, d_edge_ptr,
+    return plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, d_seed_ptr, d_seeds, row_begin, row_count, s, d_nodes, d_edge_ptr,
                             total_edges_host, defer_scan, poll_total);
 }
 
@@ -1832,7 +1832,7 @@ static int plan_walk_impl(ugs_plan *plan, int m_per_graph, int k, int mode, int6
 // tc = choose_tier(plan, k) taken before the lock (choose_tier takes mu itself).  With *defer_scan set on return the plan's counts
 // and 8-row sums are this walk's only while the caller keeps holding mu: a fill that scans them is launched before it lets go.
 static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_graph, int k, int mode, int64_t extra_node_offset, int seed,
-                            const uint64_t *d_seed_ptr, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
+                            const uint64_t *d_seed_ptr, const uint64_t *d_seeds, int64_t row_begin, int64_t row_count, hipStream_t s, int64_t *d_nodes, int64_t *d_edge_ptr,
                             int64_t *total_edges_host, bool *defer_scan, bool poll_total) {
     if (defer_scan) *defer_scan = false;
     if (int rc = plan_enter(plan, s)) return rc;
@@ -1868,6 +1868,7 @@ static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_grap
     a.extra_node_off = extra_node_offset;
     a.seed64 = (uint64_t)(int64_t)seed;
     a.seed_ptr = d_seed_ptr;
+    a.seeds = d_seeds;
     a.row_begin = row_begin; a.row_count = row_count;
     a.nodes = d_nodes;
     a.counts = static_cast<uint32_t *>(plan->counts.p);
@@ -2004,14 +2005,14 @@ int ugs_plan_step(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extr
                   void *stream, int64_t *d_nodes, int64_t *d_edge_ptr, int64_t *d_edge_index, int64_t ld, int64_t *d_edge_src) {
     if (int rc = walk_check(plan, m_per_graph, k, mode, row_begin, row_count, d_nodes, d_edge_ptr)) return rc;
     if (row_count == 0)                         // edge_ptr[0] = 0, nothing to fill
-        return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, nullptr);
+        return plan_walk_impl(plan, m_per_graph, k, mode, extra_node_offset, seed, nullptr, nullptr, row_begin, row_count, stream, d_nodes, d_edge_ptr, nullptr);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const TierChoice tc = choose_tier(plan, k);
     // one hold of mu from the walk to the fill: the fused fill scans the counts and 8-row sums the walk leaves in the plan's scratch,
     // which another caller's walk on this plan would overwrite in between
     std::unique_lock<std::mutex> lk(plan->mu);
     bool deferred = false;
-    if (int rc = plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, nullptr, row_begin, row_count, s, d_nodes, d_edge_ptr,
+    if (int rc = plan_walk_locked(plan, tc, m_per_graph, k, mode, extra_node_offset, seed, nullptr, nullptr, row_begin, row_count, s, d_nodes, d_edge_ptr,
                                   nullptr, &deferred, false)) return rc;
     if (!deferred) {                            // the scan ran: the fill reads the plan's scratch only through the staging check
         lk.unlock();
@@ -2097,14 +2098,14 @@ int ugs_plan_graph_create(ugs_plan *plan, int m_per_graph, int k, int mode, int6
     if (e != hipSuccess) return bail(fail_hip(e, "graph resources"));
     g->h_seeds[0] = 0;
     // 1. an ordinary step: every scratch buffer of the shadow plan gets its final size before anything is captured
-    if (int rc = plan_walk_impl(sh, m_per_graph, k, mode, extra_node_offset, 0, nullptr, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, nullptr)) return bail(rc);
+    if (int rc = plan_walk_impl(sh, m_per_graph, k, mode, extra_node_offset, 0, nullptr, nullptr, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, nullptr)) return bail(rc);
     if (int rc = ugs_plan_fill(sh, m_per_graph, k, mode, extra_node_offset, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, d_edge_index, ld, d_edge_src)) return bail(rc);
     e = hipStreamSynchronize(g->cs);
     if (e != hipSuccess) return bail(fail_hip(e, "graph warm-up"));
     // 2. the same step captured, reading its seed from d_seed
     e = hipStreamBeginCapture(g->cs, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) return bail(fail_hip(e, "hipStreamBeginCapture"));
-    int rc = plan_walk_impl(sh, m_per_graph, k, mode, extra_node_offset, 0, g->d_seed, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, nullptr);
+    int rc = plan_walk_impl(sh, m_per_graph, k, mode, extra_node_offset, 0, g->d_seed, nullptr, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, nullptr);
     if (!rc) rc = ugs_plan_fill(sh, m_per_graph, k, mode, extra_node_offset, row_begin, row_count, g->cs, d_nodes, d_edge_ptr, d_edge_index, ld, d_edge_src);
     e = hipStreamEndCapture(g->cs, &g->graph);
     if (rc) return bail(rc);
@@ -2260,6 +2261,8 @@ struct ugs_job {
     // batches of small graphs: begin ran walk + fill as one step (scan folded into the fill) into this staging -- edge_index [2, total]
     // and edge_src [total] laid out for the total the kernel found -- and finish only copies out
     bool packed_ok = false;
+    // ugs_sample_graphs_begin: the per-graph seed bases, widened; uploaded on the job's stream to the end of `nodes` (begin_common)
+    std::vector<uint64_t> seeds;
     // epsilon_uniform path
     bool eps = false;
     PoolBuf eps_blob;                  // pooled: hipMalloc/hipFree per call cost milliseconds once the process holds large plans
@@ -2330,7 +2333,9 @@ int packed_fill_locked(ugs_job *j, int64_t cap3) {
     return UGS_OK;
 }
 
-int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed, bool batch, ugs_job **job_out, int64_t *total_out) {
+// seeds (ugs_sample_graphs_begin): plan->G per-graph seeds that replace `seed`; nullptr: one seed for the call
+int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed, bool batch, ugs_job **job_out, int64_t *total_out,
+                 const int32_t *seeds = nullptr) {
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) { plan_unref(plan); return rc; }
     auto *j = new ugs_job();
@@ -2344,7 +2349,18 @@ int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed
     const TierChoice tc0 = choose_tier(plan, k);
     const bool may_pack = k >= 2 && j->rows > 0 && j->rows <= 131072 && tc0.first == UGS_TIER_S && tc0.second < 0 && !tc0.third_G &&
                           cap3_want * (int64_t)sizeof(int64_t) <= ((int64_t)192 << 20) && !debug_on() && std::getenv("UGS_NO_PACKED_STEP") == nullptr;
-    int rc = pool_get((size_t)(node_words + (may_pack ? cap3_want : 0)) * sizeof(int64_t), dc.id, j->nodes);
+    const int64_t out_words = node_words + (may_pack ? cap3_want : 0);          // the seed table, if any, lies behind everything finish copies
+    const int64_t seed_words = seeds ? plan->G : 0;
+    int rc = pool_get((size_t)(out_words + seed_words) * sizeof(int64_t), dc.id, j->nodes);
+    const uint64_t *d_seeds = nullptr;
+    if (!rc && seed_words > 0) {
+        j->seeds.resize((size_t)seed_words);
+        for (int64_t g = 0; g < seed_words; ++g) j->seeds[(size_t)g] = (uint64_t)(int64_t)seeds[g];
+        uint64_t *d = reinterpret_cast<uint64_t *>(static_cast<int64_t *>(j->nodes.p) + out_words);
+        if (hipError_t e = hipMemcpyAsync(d, j->seeds.data(), (size_t)seed_words * sizeof(uint64_t), hipMemcpyHostToDevice, dc.stream); e != hipSuccess)
+            rc = fail_hip(e, "hipMemcpyAsync(seeds)");
+        d_seeds = d;
+    }
     if (!rc) {
         j->d_eptr = static_cast<int64_t *>(j->nodes.p) + j->rows * k;
         // Small batches: every ordered pair of a row's vertices, twice (both directions of a PyG edge are columns, and each column is
@@ -2359,11 +2375,11 @@ int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed
             if (!rc) {
                 std::lock_guard<std::mutex> lk(plan->mu);
                 bool deferred = false;
-                rc = plan_walk_locked(plan, tc0, m, k, mode, extra, seed, nullptr, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, &deferred, true);
+                rc = plan_walk_locked(plan, tc0, m, k, mode, extra, seed, nullptr, d_seeds, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, &deferred, true);
                 if (!rc && deferred) rc = packed_fill_locked(j, cap3);
             }
         } else {
-            rc = plan_walk_impl(plan, m, k, mode, extra, seed, nullptr, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, nullptr, true);
+            rc = plan_walk_impl(plan, m, k, mode, extra, seed, nullptr, d_seeds, 0, j->rows, dc.stream, d_nodes, j->d_eptr, &j->total, nullptr, true);
         }
     }
     if (rc) { free_job(j); return rc; }
@@ -2505,6 +2521,21 @@ int ugs_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_
     return begin_common(plan, m_per_graph, k, mode, 0, seed, true, job_out, total_edges_out);
 }
 
+// sample_batch with one seed per graph: the same plan lookup (LRU replay, device batch pass) and the same job; the seeds go to the
+// device with the job (begin_common).  No early start: presample chunks are far below its threshold.
+int ugs_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                            int m_per_graph, int k, int mode, const int32_t *seeds, ugs_job **job_out, int64_t *total_edges_out) {
+    if (!job_out) return fail(UGS_E_BAD_ARG, "job_out is null");
+    if (mode < 0 || mode > 2) return fail(UGS_E_BAD_MODE, "mode must be one of: 'sample', 'graph', 'global'");
+    if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
+    if (k < 1) return fail(UGS_E_BAD_ARG, "k must be >= 1");
+    if (k > UGS_KMAX) return fail(UGS_E_UNSUPPORTED, "k > 32 is not supported by the HIP sampler");
+    if (num_graphs > 0 && !seeds) return fail(UGS_E_BAD_ARG, "sample_graphs needs one seed per graph");
+    ugs_plan *plan = nullptr;
+    if (int rc = ugs_plan_create_batch(edge_index, row_stride, num_cols, ptr, num_graphs, k, &plan)) return rc;
+    return begin_common(plan, m_per_graph, k, mode, 0, 0, true, job_out, total_edges_out, num_graphs > 0 ? seeds : nullptr);
+}
+
 int ugs_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                             int64_t *edge_src_global, int dst_is_device) {
     if (!job) return fail(UGS_E_BAD_ARG, "job is null");
@@ -2574,7 +2605,7 @@ int stream_rows(ugs_plan *plan, StreamCall &c) {
         const int64_t r0 = ch * chunk, rc_rows = std::min(chunk, rows - r0);
         const bool last = ch + 1 == nchunks;
         int64_t tot = 0;
-        if (int rc = plan_walk_impl(plan, c.m, k, c.mode, c.extra, c.seed, nullptr, r0, rc_rows, s, d_nodes + r0 * k, d_loc, &tot, nullptr, true)) return rc;
+        if (int rc = plan_walk_impl(plan, c.m, k, c.mode, c.extra, c.seed, nullptr, nullptr, r0, rc_rows, s, d_nodes + r0 * k, d_loc, &tot, nullptr, true)) return rc;
         if (base + tot > cap) { *c.total_out = base + tot; return fail(UGS_E_CAPACITY, "edge_capacity too small for this call's edge entries"); }
         if (tot > 0)
             if (int rc = ugs_plan_fill(plan, c.m, k, c.mode, c.extra, r0, rc_rows, s, d_nodes + r0 * k, d_loc, d_ei + base, cap, d_es + base)) return rc;

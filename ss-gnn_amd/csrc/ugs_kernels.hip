@@ -2,6 +2,7 @@
 //
 // What is computed (behavioural contract = the reference `ugs_sampler`, AniruddhaMandal/SS-GNN):
 //   walk kernel : per result row b = g*m + i -- xorshift64* stream seeded seed + i*0x9e3779b97f4a7c15
+//                 (or seeds[g] + i*0x9e3779b97f4a7c15 with a per-graph seed table: the SEEDS instantiations, ugs_sample_graphs_begin)
 //                 (reference include/sampler.hpp:26-36, src/sampler.cpp:160), root draw through the alias table or
 //                 the relaxed viable list (src/sampler.cpp:163-173), k-1 growth steps (rand_grow, src/sampler.cpp:36-85),
 //                 per-row induced-edge COUNT; rows come out as nodes[row,k] (-1 padded)
@@ -1363,7 +1364,7 @@ __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const
 // per CU instead of three).  An 8-lane walk is a chain of LDS round trips of its own order stages; the two L2 round trips per step it
 // saved do not show.  The same copy for the fill kernels (row pointer and (neighbour, column) entries): 12.4 against 12.4 us and 25.5
 // against 25.0 us.  Neither kept.)
-template <int GS, class SP, int MAXPER, bool PAD>
+template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false>
 __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, const UgsWalkArgs &a, int64_t row_rel,
                                         uint32_t *SV /* [UGS_KMAX] group-private */, uint4 *EL /* [UGS_STAGE_ENTRIES] or null */,
                                         uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */) {
@@ -1395,7 +1396,10 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     STAMP_DECL;
     STAMP_BEGIN();
     Rng rng;
-    rng.init((a.seed_ptr ? *a.seed_ptr : a.seed64) + (uint64_t)i * 0x9e3779b97f4a7c15ull);
+    uint64_t seed_base;
+    if constexpr (SEEDS) seed_base = a.seeds[gi];          // one generator base per graph (UgsWalkArgs::seeds)
+    else seed_base = a.seed_ptr ? *a.seed_ptr : a.seed64;
+    rng.init(seed_base + (uint64_t)i * 0x9e3779b97f4a7c15ull);
     // Root draw.  The root record is fetched first and the membership hash is reset while it is in flight; the root's row is
     // requested as soon as the root is known, before the root is entered into the hash and the sample list.
     uint32_t root_vi, root_v;
@@ -1641,7 +1645,7 @@ template <int CAP> struct TierCfg {
 // admits 18 one-wave blocks per CU (5,5,4,4 per SIMD).  With a STATIC split of the rows 18 blocks/CU was slower than 16
 // (10.63 vs 10.43 ms: a launch ended with the waves of the fuller SIMDs); with the shared work counter the extra waves are
 // pure throughput: 8.81 -> 8.51 ms.  Spilling further to reach more waves costs more than it brings (30 % in an early build).
-template <int GS, int CAP, int BLOCK, bool PAD>
+template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false>
 __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 5 : (CAP == 704 ? 3 : (CAP <= 64 || CAP == 1024 || CAP == 1408 ? 2 : 1)))) void ugs_walk_lds(UgsWalkArgs a) {
     using Cfg = TierCfg<CAP>;
     constexpr int GROUPS = BLOCK / GS;
@@ -1689,7 +1693,7 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
             if (end > total) end = total;
             for (; it < end; ++it) {
                 const int64_t row_rel = a.in_list ? a.in_list[it] : it;
-                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD>(ws, g, a, row_rel, SV, EL)) {
+                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS>(ws, g, a, row_rel, SV, EL)) {
                     if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
                 }
             }
@@ -1714,7 +1718,7 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
             for (int64_t it0 = (int64_t)blockIdx.x * GROUPS; it0 < total; it0 += ngroups) {
                 const int64_t it = it0 + gib;
                 uint32_t ne = 0u;
-                if (it < total) (void)do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD>(ws, g, a, it, SV, EL, &ne);
+                if (it < total) (void)do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS>(ws, g, a, it, SV, EL, &ne);
                 uint32_t sum = g.lane == 0 ? ne : 0u;
 #pragma unroll
                 for (int d = GS; d < 64; d <<= 1) sum += __shfl_xor(sum, d, 64);
@@ -1736,7 +1740,7 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
     }
     for (int64_t it = (int64_t)blockIdx.x * GROUPS + gib; it < total; it += ngroups) {
         const int64_t row_rel = a.in_list ? a.in_list[it] : it;
-        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD>(ws, g, a, row_rel, SV, EL)) {
+        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS>(ws, g, a, row_rel, SV, EL)) {
             if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
         }
     }
@@ -1762,6 +1766,7 @@ __global__ __launch_bounds__(256) void ugs_build_prow(UgsPlanDev P, int64_t num_
 }
 
 // last tier: workspace in global memory, one wave per walk, any candidate-set size up to gcap
+template <bool SEEDS>
 __global__ __launch_bounds__(64) void ugs_walk_global(UgsWalkArgs a) {
     __shared__ uint32_t SV[UGS_KMAX];
     Grp<64> g;
@@ -1784,7 +1789,7 @@ __global__ __launch_bounds__(64) void ugs_walk_global(UgsWalkArgs a) {
     const int64_t total = a.in_list ? (int64_t)*a.in_count : a.row_count;
     for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {
         const int64_t row_rel = a.in_list ? a.in_list[it] : it;
-        if (!do_walk<64, GlbSpace, 0, false>(ws, g, a, row_rel, SV, nullptr)) {
+        if (!do_walk<64, GlbSpace, 0, false, SEEDS>(ws, g, a, row_rel, SV, nullptr)) {
             // cannot happen when gcap covers the graph's bound; mark the row so the host can report it
             if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
         }
@@ -2203,7 +2208,11 @@ static hipError_t launch_lds(const UgsWalkArgs &a, int cus, int blocks_per_cu, h
     const int64_t cap = (int64_t)cus * blocks_per_cu;
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    if (kCanPad && a.plan.prow) hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanPad>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
+    const bool pad = kCanPad && a.plan.prow;
+    if (a.seeds) {          // per-graph seeds: instantiations of their own, so that a call without them runs the code it always ran
+        if (pad) hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanPad, true>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, false, true>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
+    } else if (pad) hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanPad>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
     else hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, false>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
     if (info) { info->name = name; info->grid = (int)grid; info->block = BLOCK; info->lds_bytes = GROUPS * TierCfg<CAP>::WORDS * 4; }
     return hipGetLastError();
@@ -2244,7 +2253,8 @@ hipError_t ugs_launch_walk(const UgsWalkArgs &a, int tier, int cus, int share_pe
     default: {
         int64_t grid = a.gws_words_per_group > 0 ? a.gws_groups : 0;
         if (grid < 1) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ugs_walk_global, dim3((unsigned)grid), dim3(64), 0, s, a);
+        if (a.seeds) hipLaunchKernelGGL(ugs_walk_global<true>, dim3((unsigned)grid), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL(ugs_walk_global<false>, dim3((unsigned)grid), dim3(64), 0, s, a);
         if (info) { info->name = "ugs_walk_global"; info->grid = (int)grid; info->block = 64; info->lds_bytes = UGS_KMAX * 4; }
         return hipGetLastError();
     }

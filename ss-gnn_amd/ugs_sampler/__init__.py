@@ -8,6 +8,8 @@ through the C ABI of include/ugs_mi355.h into hand-written HIP kernels; sampling
 Additions that the reference does not have (all optional, keyword-only or separate functions):
   * `device=` on sample / sample_batch: return the tensors on that GPU instead of pinned host memory, so the
     trainer's later `batch.to(device)` (gps/experiment.py:523) moves nothing;
+  * sample_graphs(): sample_batch with one seed per graph -- the trainer's presample loop (one one-graph call per dataset graph)
+    as one call (law: include/ugs_mi355.h at ugs_sample_graphs_begin);
   * clear_cache() / cache_stats(): the process-global preprocessing LRU (reference: UGS_CACHE_SIZE, default 1000);
   * Plan: a batch preprocessed once and kept resident in HBM, sampled repeatedly / over row sub-ranges
     (multi-GPU sharding, see ugs_sampler.distributed).
@@ -20,7 +22,7 @@ import torch
 from ._lib import UGS_E_CAPACITY, check, lib, vp
 
 __version__ = (lib.ugs_version() or b"").decode()
-__all__ = ["sample", "create_preproc", "destroy_preproc", "has_graphlets", "get_preproc_info", "sample_batch",
+__all__ = ["sample", "create_preproc", "destroy_preproc", "has_graphlets", "get_preproc_info", "sample_batch", "sample_graphs",
            "clear_cache", "cache_stats", "preproc_dump", "Plan", "device_count"]
 
 _EDGE_MODES = {"local": 0, "flat": 1, "global": 2}
@@ -267,6 +269,71 @@ def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, *, dev
     check(lib.ugs_sample_batch_finish(job, nodes.data_ptr(), edge_index_t.data_ptr(), edge_ptr.data_ptr(),
                                       sample_ptr.data_ptr(), edge_src.data_ptr(), on_dev))
     return nodes, edge_index_t, edge_ptr, sample_ptr, edge_src
+
+
+def _seed_ints(seeds, G):
+    """seeds (a sequence, or an int64 tensor or integer array) as a contiguous int32 numpy array of length G.  A seed that is no C int
+    raises TypeError naming its graph, as the one-graph call would for that graph."""
+    import numpy as np
+    if torch.is_tensor(seeds):
+        if seeds.dtype != torch.int64:
+            raise RuntimeError("seeds must be an int64 tensor")
+        seeds = seeds.detach().cpu().numpy()
+    if isinstance(seeds, np.ndarray):
+        if seeds.dtype.kind not in "iu":
+            raise TypeError("seeds must be integers")
+        a = seeds.reshape(-1)
+        if a.shape[0] != G:
+            raise RuntimeError(f"seeds must hold one seed per graph ({G}), got {a.shape[0]}")
+        bad = np.nonzero((a < _I32_MIN) | (a > _I32_MAX))[0]
+        if bad.size:
+            raise TypeError(f"seeds[{int(bad[0])}]={int(a[bad[0]])} does not fit a C int")
+        return np.ascontiguousarray(a, dtype=np.int32)
+    seeds = list(seeds)
+    if len(seeds) != G:
+        raise RuntimeError(f"seeds must hold one seed per graph ({G}), got {len(seeds)}")
+    return np.array([_as_c_int(x, f"seeds[{g}]") for g, x in enumerate(seeds)], dtype=np.int32).reshape(-1)
+
+
+def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", device=None):
+    """sample_graphs without `failed` on the outputs' device: ((nodes, edge_index, edge_ptr, sample_ptr, edge_src), failed [G] on
+    the host) -- the form PresampleCache.add_many takes from every sampler."""
+    _check_cpu_i64(edge_index, "edge_index")
+    _check_cpu_i64(ptr, "ptr")
+    if mode not in _BATCH_MODES:
+        raise RuntimeError("mode must be one of: 'sample', 'graph', 'global'")
+    m, k = _as_c_int(m_per_graph, "m_per_graph"), _as_c_int(k, "k")
+    keep, p, stride, e = _edge_index_view(edge_index)
+    ptr_c = ptr.contiguous()
+    G = ptr_c.numel() - 1
+    sd = _seed_ints(seeds, max(G, 0))           # before any work: the LRU is untouched when a seed is refused
+    _select_device(device, jobs=True)
+    job, total = vp(), C.c_int64()
+    check(lib.ugs_sample_graphs_begin(p, stride, e, ptr_c.data_ptr(), G, m, k, _BATCH_MODES[mode], sd.ctypes.data, C.byref(job), C.byref(total)))
+    try:
+        opts, on_dev = _out_opts(device)
+        B = max(G, 0) * m
+        nodes, edge_ptr, edge_index_t, edge_src, sample_ptr = _carve(opts, [(B, k), (B + 1,), (2, total.value), (total.value,), (max(G, 0) + 1,)])
+    except BaseException:
+        lib.ugs_job_cancel(job)
+        raise
+    check(lib.ugs_sample_batch_finish(job, nodes.data_ptr(), edge_index_t.data_ptr(), edge_ptr.data_ptr(),
+                                      sample_ptr.data_ptr(), edge_src.data_ptr(), on_dev))
+    return (nodes, edge_index_t, edge_ptr, sample_ptr, edge_src), torch.zeros(max(G, 0), dtype=torch.bool)
+
+
+def sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", *, device=None):
+    """sample_batch with one seed per graph: row b = g*m + i draws from seeds[g] instead of from one `seed`; everything else -- the
+    preprocessing LRU visited graph by graph, graphs of fewer than k vertices, the three modes -- is sample_batch's.  Graph g's
+    block of m rows, re-based, is the one-graph call sample_batch(columns of g, [0, n_g], m, k, mode, seeds[g]) made as the g-th
+    of a sequence of such calls: the trainer's presample loop in one call (law: include/ugs_mi355.h, ugs_sample_graphs_begin).
+
+    `seeds`: a sequence, an int64 tensor or an integer array of G C ints; one that does not fit raises TypeError naming its graph,
+    before any work.  Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src, failed) like uniform_sampler.sample_graphs and
+    rwr_sampler.sample_graphs -- pinned host tensors, or on `device`.  `failed` [G] is all False: no ugs graph fails on its own
+    today (what sample_batch refuses, it refuses for the whole call)."""
+    out, failed = _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode, device)
+    return out + (failed.to(out[0].device),)
 
 
 class GraphStep:

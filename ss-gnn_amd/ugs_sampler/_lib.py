@@ -32,6 +32,7 @@ def _load():
         "ugs_sample_finish": [vp, vp, vp, vp, vp, C.c_int],
         "ugs_sample_batch_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(vp), i64p],
+        "ugs_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), i64p],
         "ugs_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
         "ugs_job_cancel": [vp],
         "ugs_sample_batch_stream": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,

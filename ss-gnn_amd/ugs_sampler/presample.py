@@ -14,9 +14,8 @@ device gathers; the sizes that decide the output shapes are known on the host fr
     nodes, edge_index, edge_ptr, sample_ptr, edge_src = cache.load(batch.graph_idx, batch.ptr, batch.edge_index)
 
 `add(i, edge_index, num_nodes, seed)` presamples one graph with the sampler's drop-in call, exactly like one iteration of the
-reference's loop; `add_many` leaves the cache exactly as the loop of `add` over its arguments would.  For "uniform" and "rwr" it
-samples the graphs in a few batched calls (uniform_sampler.sample_graphs / rwr_sampler.sample_graphs: one seed per graph), for
-"ugs" it is that loop.  `failed` is the set of indices whose presampling failed.
+reference's loop; `add_many` leaves the cache exactly as the loop of `add` over its arguments would, but samples the graphs in a
+few batched calls (the sampler's sample_graphs: one seed per graph).  `failed` is the set of indices whose presampling failed.
 
 `load` returns exactly what the reference's `_load_from_presample_cache` stores on the batch -- including its treatment of
 graphs whose presampling failed (m rows of -1 to which ptr[g] is ADDED like to every other row, no edges).
@@ -24,7 +23,7 @@ graphs whose presampling failed (m rows of -1 to which ptr[g] is ADDED like to e
 import numpy as np
 import torch
 
-from . import sample_batch
+from . import _I32_MAX, _I32_MIN, sample_batch
 
 SAMPLERS = ("ugs", "uniform", "rwr")
 # add_many's call bounds.  Vertices: the uniform count pass keeps 12 B per (root, first extension) item and 64 items per vertex,
@@ -36,6 +35,9 @@ _JOINT_BUDGET = "split the call"       # uniform_sampler: healthy graphs that to
 
 
 def _drop_in(sampler):
+    if sampler == "ugs":
+        import ugs_sampler
+        return ugs_sampler
     if sampler == "uniform":
         import uniform_sampler
         return uniform_sampler
@@ -104,13 +106,11 @@ class PresampleCache:
         seeds = [int(s) for s in (seeds.tolist() if torch.is_tensor(seeds) else seeds)]
         if not (len(indices) == len(graphs) == len(seeds)):
             raise ValueError("indices, graphs and seeds must have the same length")
-        if self.sampler == "ugs":       # a batched ugs form would need per-graph seed bases in the walk kernel
-            for i, (ei, n), s in zip(indices, graphs, seeds):
-                self.add(i, ei, n, s)
-            return
         run, nv, rows = [], 0, 0        # graphs of the current call, in order
         for t, (ei, n) in enumerate(graphs):
             regular = torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.size(0) == 2 and int(n) >= 0
+            if self.sampler == "ugs":   # its seeds are C ints: the one-graph call refuses any other
+                regular = regular and _I32_MIN <= seeds[t] <= _I32_MAX
             if not regular:             # whatever add makes of it, in its place in the order
                 self._batched(run)
                 run, nv, rows = [], 0, 0
@@ -150,7 +150,7 @@ class PresampleCache:
             (nodes, eidx, eptr, _, esrc), failed = mod._sample_graphs(torch.from_numpy(ei), torch.from_numpy(ptr), m, k,
                                                                       [g[3] for g in run], "sample",
                                                                       device=self.dev, **extra)
-        except RuntimeError as e:
+        except (RuntimeError, TypeError) as e:
             if self.sampler == "uniform" and G > 1 and _JOINT_BUDGET in str(e):
                 self._batched(run[:G // 2])
                 self._batched(run[G // 2:])
