@@ -1318,12 +1318,64 @@ __device__ __forceinline__ bool scan_prow(const Work<SP> &ws, const Grp<64> &g, 
 // (Round 4 also measured item ranks by COUNTING -- every item sets bit cr of its source's word in LDS, a rank is the population of
 // the smaller sources' words plus the lower bits of its own: ~170 instructions fewer per walk, but three more LDS round trips at
 // the very end of the walk: 5.06 against 4.94 ms per 1M walks, not kept.)
+//
+// Rows of at most kFlushFast hits without a self hit -- a sample that is a tree has k - 1 -- take the fast path: ONE ITEM per lane
+// inside DPP row 0.  Lane l < 8 holds hit l as es -> ei, lane 8 + l its mirror ei -> es (do_walk loads the hit into both).  Every
+// column then sits in lanes l and l + 8 of the row, so the rotations by 1..7 show a lane each OTHER hit's column exactly once:
+// seven compares give the column rank, whatever the width of a column.  The item key (source index, column rank) is a small
+// number; fifteen rotations of it count the smaller keys = the item's place in the row.  Without a self hit no two items tie.
+// No v_readlane, no scalar loop; only the once-written key registers are read through DPP.
+constexpr uint32_t kFlushFast = 8u;
+// Number of the keys 1..N lanes round the lane's DPP row that are smaller than its own.  By hand: a subtraction takes the rotated key as
+// its DPP operand (gfx950 has no DPP form of the compares), its borrow says "smaller" and the carry add counts it -- two vector
+// instructions per rotation and the two wait states gfx950 wants between a vector write of VCC and a vector read of it.  (The compiler's version of the plain C++ moves every rotated key into a register of
+// its own first, sinks the compares under the storing lanes' mask and widens the sum to the 64-bit address: 5 per rotation.)
+#define UGS_ROR_LT(R) "v_sub_co_u32_dpp %1, vcc, %2, %2 row_ror:" #R " row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\tv_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n\t"
+template <int N> __device__ __forceinline__ uint32_t ror_count_less(uint32_t key) {
+    static_assert(N == 7 || N == 15, "half a DPP row or all of it");
+    uint32_t n, diff;
+    if constexpr (N == 7)        // (the leading v_mov and s_nop: the key may have been written by the instruction before)
+        asm("v_mov_b32 %0, 0\n\ts_nop 0\n\t" UGS_ROR_LT(1) UGS_ROR_LT(2) UGS_ROR_LT(3) UGS_ROR_LT(4) UGS_ROR_LT(5) UGS_ROR_LT(6) UGS_ROR_LT(7)
+            : "=&v"(n), "=&v"(diff) : "v"(key) : "vcc");
+    else
+        asm("v_mov_b32 %0, 0\n\ts_nop 0\n\t" UGS_ROR_LT(1) UGS_ROR_LT(2) UGS_ROR_LT(3) UGS_ROR_LT(4) UGS_ROR_LT(5) UGS_ROR_LT(6) UGS_ROR_LT(7)
+            UGS_ROR_LT(8) UGS_ROR_LT(9) UGS_ROR_LT(10) UGS_ROR_LT(11) UGS_ROR_LT(12) UGS_ROR_LT(13) UGS_ROR_LT(14) UGS_ROR_LT(15)
+            : "=&v"(n), "=&v"(diff) : "v"(key) : "vcc");
+    return n;
+}
+#undef UGS_ROR_LT
+__device__ __forceinline__ uint32_t flush_hit_lane(uint32_t ne, uint32_t lane) { return ne <= kFlushFast ? (lane & 7u) : lane; }
+__device__ __forceinline__ bool flush_has_hit(uint32_t ne, uint32_t lane) {
+    return ne <= kFlushFast ? (lane < 16u && (lane & 7u) < ne) : lane < ne;
+}
+
 __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const uint32_t *SV, uint32_t k, uint4 en, uint32_t ecol, uint2 *out) {
     const uint32_t lane = (uint32_t)g.lane;
-    const bool mine = lane < ne;
     uint32_t ei = 0u;
-    for (uint32_t j = 0; j < k; ++j) ei = (SV[j] == en.y) ? j : ei;
+    if (k <= 8u) {
+        // straight-line, from the top: words of SV past the sample are stale, but a hit's member is in the sample and the sample's
+        // vertices are distinct, so its own compare comes later and has the last word (two vector instructions per word, no loop)
+        const uint4 s0 = reinterpret_cast<const uint4 *>(SV)[0], s1 = reinterpret_cast<const uint4 *>(SV)[1];
+        ei = (s1.w == en.y) ? 7u : ei; ei = (s1.z == en.y) ? 6u : ei; ei = (s1.y == en.y) ? 5u : ei; ei = (s1.x == en.y) ? 4u : ei;
+        ei = (s0.w == en.y) ? 3u : ei; ei = (s0.z == en.y) ? 2u : ei; ei = (s0.y == en.y) ? 1u : ei; ei = (s0.x == en.y) ? 0u : ei;
+    } else {
+        for (uint32_t j = 0; j < k; ++j) ei = (SV[j] == en.y) ? j : ei;
+    }
     const uint32_t es = en.z;
+    if (__builtin_expect(ne <= kFlushFast, 1)) {
+        const bool have = lane < 16u && (lane & 7u) < ne;
+        if (__builtin_expect(!g.any(have && ei == es), 1)) {
+            const uint32_t col = have ? ecol : 0xFFFFFFFFu;                     // (a column is a non-negative int32)
+            const uint32_t cr = ror_count_less<7>(col);
+            const bool fwd = lane < 8u;
+            const uint32_t src = fwd ? es : ei, dst = fwd ? ei : es;
+            const uint32_t key = have ? src * 8u + cr : 0xFFFFFFFFu;
+            const uint32_t rank = ror_count_less<15>(key);
+            if (have) out[rank] = make_uint2(ecol, src | (dst << 8));
+            return;
+        }
+    }
+    const bool mine = lane < ne;        // (a row of <= 8 hits with a self hit: lanes 8.. hold copies that `mine` masks out)
     uint32_t cr = 0u;
     const uint32_t ecol_s = mine ? ecol : 0xFFFFFFFFu;
     if (g.any(mine && ei == es)) {
@@ -1608,7 +1660,8 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     uint32_t ecol = 0u;
     if constexpr (STG) {
         flush = sc.on && nedges != 0u && sc.ne <= UGS_STAGE_ENTRIES;
-                if (flush && (uint32_t)g.lane < sc.ne) { en = sc.EL[g.lane]; ecol = (uint32_t)P.adjf[en.x].y; }
+        // (rows of at most 8 hits: lanes l and 8 + l both take hit l, see stage_flush)
+        if (flush && flush_has_hit(sc.ne, (uint32_t)g.lane)) { en = sc.EL[flush_hit_lane(sc.ne, (uint32_t)g.lane)]; ecol = (uint32_t)P.adjf[en.x].y; }
     }
     // nodes row: growth order, -1 padded (reference src/sampler.cpp:205-216, src/ugs_sampler_batch_extension.cpp:188-196)
     const int64_t off = gd.node_lo + a.extra_node_off;

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64, 5) void probe_draw(uint32_t *out, const uint32_
 __global__ __launch_bounds__(64, 5) void probe_flush(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel, const int2 *adjf, uint2 *stage) {
     PROBE_PRE
     uint4 en = make_uint4(0, 0, 0, 0); uint32_t ecol = 0;
-    if (threadIdx.x < c) { en = pw.EL[threadIdx.x]; ecol = (uint32_t)adjf[en.x].y; }
+    if (flush_has_hit(c, threadIdx.x)) { en = pw.EL[flush_hit_lane(c, threadIdx.x)]; ecol = (uint32_t)adjf[en.x].y; }
     stage_flush(c, g, pw.SV, rsel, en, ecol, stage);
     out[threadIdx.x] = lds[(threadIdx.x + c) & 63];
 }
