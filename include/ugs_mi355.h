@@ -154,8 +154,18 @@ int ugs_cache_stats(int64_t *size, int64_t *hits, int64_t *misses);
  * 8(f) N4): one pass over edge_index + ptr replaces the reference's per-graph slicing (src/ugs_sampler_batch_extension.cpp:41-75),
  * hashing (include/cache.hpp:81-109) and CSR construction (src/preproc.cpp:32-86); the host replays the LRU on the G keys that
  * come back.  Counters since process start: plans built that way / calls that took the general (host) path instead
- * (UGS_DEVICE_BATCH=0, non-monotone ptr, a graph with more than 2048 vertices or 1000 columns). */
+ * (UGS_DEVICE_BATCH=0, non-monotone ptr, a graph with more than 2048 vertices or more columns than the limit below). */
 int ugs_batch_pass_stats(int64_t *device_plans, int64_t *general_path);
+/* Columns per graph up to which the pass applies.  Default 1000: up to there the reference's LRU key covers a graph's whole content;
+ * beyond, it hashes every (columns / 500)-th column only (include/cache.hpp:100-107).  A caller whose graphs are larger raises the
+ * limit, to 8192 at most: the pass then runs the large form of its kernels, which compute that strided key plus a 128-bit content
+ * fingerprint, and accepts a cached graph only if n, nnz and the fingerprint agree -- two different graphs sharing a key send the
+ * batch to the general path, which samples from the cached graph as the reference does.  Results never depend on the limit.
+ * Process-wide and atomic; calls in flight keep the value they started with.  Outside 1000 ... 8192: UGS_E_BAD_ARG, value kept.
+ * previous_out may be NULL.  Initial value: UGS_BATCH_PASS_MAX_COLS in the environment, read at first use (out of range = ignored,
+ * reported under UGS_DEBUG=1). */
+int ugs_set_batch_pass_max_cols(int64_t cols, int64_t *previous_out);
+int64_t ugs_batch_pass_max_cols(void);
 
 /* ---- device-resident plans: the batch (or single graph) preprocessed once and kept in HBM, sampled many times,
  *      optionally over a sub-range of the G*m result rows (multi-GPU sharding: row b = g*m + i depends only on

@@ -17,10 +17,21 @@
 //                   entries in COLUMN order (u's row then v's row per column, both entries of a self loop) written straight into
 //                   the plan's arrays: rowptr (absolute), adj = (w, rank(w)), adjf = (w, batch column)
 //
-// The host then sees G keys (16 bytes per graph come back), replays the LRU on them and points each graph's descriptor at the
+// The host then sees G keys (36 bytes per graph come back), replays the LRU on them and points each graph's descriptor at the
 // root records its cached preprocessing left in HBM (ugs_host.cpp: device_batch_plan).  A key covers the whole content of a
 // graph of at most 1000 columns (cache.hpp:100 samples longer ones), so a cached graph with the same key HAS this CSR; graphs
 // beyond the limits below send the whole batch down the host path.
+//
+// Two forms of ugs_bp_build and ugs_bp_roots, by a template parameter for the column capacity of their LDS arrays, chosen per
+// launch by the limit in force (ugs_set_batch_pass_max_cols):
+//   capacity 1000  the pass as it always was: every launch while the limit stands at its default (same registers, LDS and
+//                  occupancy as before the large form existed: DESIGN.md section 9 N4);
+//   capacity 8192  the large form, for callers whose graphs have more than 1000 columns (COCO-SP: ~2.7 k).  Same algorithm with
+//                  larger arrays (120 KB of LDS: one block per CU, a batch has tens of graphs), and for a graph above 1000
+//                  columns the reference's STRIDED key -- columns 0, s, 2s, ... with s = columns / 500 -- plus a 128-bit
+//                  fingerprint of the whole content (ugs_device.h: ugs_fp_add), 16 more bytes per graph to the host.  The host,
+//                  not the kernel, compares it with the cached graph's: two different graphs may share a strided key, the
+//                  reference then samples from the cached one, and only the general path reproduces that.
 #include "ugs_device.h"
 #include <cstdlib>
 
@@ -84,6 +95,9 @@ struct BpBuild {
     unsigned long long *done;
     unsigned long long done_target;
     uint32_t *h_done;
+    // the large form only (CAP > 1000): the limit in force and where the content fingerprints go (two words per graph, pinned)
+    unsigned long long *h_fp;
+    uint32_t max_cols;
 };
 
 // every thread of the block calls this at the end of the kernel; the block's writes to pinned host memory are fenced by their writers
@@ -95,19 +109,25 @@ __device__ __forceinline__ void bp_signal_done(unsigned long long *done, unsigne
     }
 }
 
-constexpr int kBpMaxCols = UGS_BATCH_PASS_MAX_COLS, kBpMaxN = UGS_BATCH_PASS_MAX_N;
+constexpr int kBpMaxCols = UGS_BATCH_PASS_MAX_COLS, kBpColsCeil = UGS_BATCH_PASS_COLS_CEIL, kBpMaxN = UGS_BATCH_PASS_MAX_N;
 constexpr int kBpMaskChunks = 512;                         // per wave: batches of up to 131 072 columns keep their ballots
 
-template <bool FUSED>
+// CAP: column capacity of the block's LDS arrays.  kBpMaxCols is the pass as it always was (every call while the limit stands at its
+// default); kBpColsCeil is the large form, launched when the caller has raised the limit (ugs_set_batch_pass_max_cols): 120 KB of
+// LDS, one block per CU -- a batch has tens of graphs -- the strided key and the content fingerprint for graphs above 1000 columns.
+template <bool FUSED, int CAP>
 __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
-    __shared__ uint16_t LU[kBpMaxCols], LV[kBpMaxCols];
-    __shared__ int32_t LC[kBpMaxCols];                       // batch column of local column t
+    constexpr bool LARGE = CAP > kBpMaxCols;
+    __shared__ uint16_t LU[CAP], LV[CAP];
+    __shared__ int32_t LC[CAP];                              // batch column of local column t
     __shared__ uint16_t DEG[kBpMaxN], RNK[kBpMaxN];
     __shared__ uint32_t RP[kBpMaxN + 1], CUR[kBpMaxN];
     __shared__ unsigned long long MSK[kBpMaxN];
     __shared__ uint32_t wsum[kBpBlock / 64];
     __shared__ uint32_t run_sh, cstart_sh;
     __shared__ unsigned long long MKS[FUSED ? kBpBlock / 64 : 1][FUSED ? kBpMaskChunks : 1];   // FUSED: which lanes of which chunk hold a column of this graph
+    __shared__ unsigned long long fp_sh[LARGE ? 2 : 1];
+    const uint32_t lim = LARGE ? (a.max_cols < (uint32_t)CAP ? a.max_cols : (uint32_t)CAP) : (uint32_t)CAP;   // the limit in force
     const int g = (int)blockIdx.x;
     const int64_t lo = a.ptr[g], n64 = a.ptr[g + 1] - lo;
     if (n64 <= 0 || n64 < a.k) {                                  // degenerate: rows of -1, nothing to build, never looked up
@@ -116,7 +136,7 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
     }
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     uint32_t cn = FUSED ? 0u : a.cnt[g];
-    if (n64 > kBpMaxN || cn > (uint32_t)kBpMaxCols) { if (tid == 0) *a.h_flag = a.epoch; return; }
+    if (n64 > kBpMaxN || cn > lim) { if (tid == 0) *a.h_flag = a.epoch; return; }
     const int n = (int)n64;
     if (tid == 0) run_sh = 0u;
     __syncthreads();
@@ -152,7 +172,7 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
         uint32_t off = 0, tot = 0;
         for (int i = 0; i < kBpBlock / 64; ++i) { if (i < wv) off += wsum[i]; tot += wsum[i]; }
         if (tid == 0) run_sh = tot;
-        if (tot <= (uint32_t)kBpMaxCols)
+        if (tot <= lim)
             for (uint32_t c = 0; c < nchunk; ++c) {
                 uint64_t mk;
                 int64_t su = 0, sv = 0;
@@ -193,7 +213,7 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
     }
     if constexpr (FUSED) {
         cn = run_sh;
-        if (cn > (uint32_t)kBpMaxCols) { if (tid == 0) *a.h_flag = a.epoch; return; }
+        if (cn > lim) { if (tid == 0) *a.h_flag = a.epoch; return; }
     }
     // the graph's place in adj / adjf, and what the host needs of it
     if (tid == 0) {
@@ -201,19 +221,35 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
         a.h_cnt[g] = cn;
         a.h_jminc[g] = cn ? 0xFFFFFFFFu - (uint32_t)LC[0] : 0u;
         a.h_jmax[g] = cn ? (uint32_t)LC[cn - 1] : 0u;
+        if constexpr (LARGE) ugs_fp_seed((unsigned long long)n, (unsigned long long)cn, fp_sh[0], fp_sh[1]);
     }
     __syncthreads();
-    // 2. the LRU key (reference include/cache.hpp:81-109; all columns: cn <= 1000 on this path): one lane, while the others count degrees
+    // 1b. above 1000 columns the key below samples the columns: the content fingerprint the host compares with the cached graph's
+    //     (ugs_device.h: ugs_fp_add) -- sums, so every thread adds its columns, a wave folds its lanes, one LDS atomic per wave and word
+    if constexpr (LARGE) {
+        if (cn > (uint32_t)kBpMaxCols) {                          // block-uniform
+            unsigned long long fa = 0ull, fb = 0ull;
+            for (uint32_t t = tid; t < cn; t += kBpBlock) ugs_fp_add(t, LU[t], LV[t], fa, fb);
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) { fa += __shfl_down(fa, s, 64); fb += __shfl_down(fb, s, 64); }
+            if (lane == 0) { atomicAdd(&fp_sh[0], fa); atomicAdd(&fp_sh[1], fb); }
+        }
+    }
+    // 2. the LRU key (reference include/cache.hpp:81-109): one lane, while the others count degrees.  Up to 1000 columns it covers
+    //    them all; above (large form only) the reference hashes columns 0, s, 2s, ... with s = cn / 500 -- at most 1000 of them, so
+    //    the chain is no longer than the longest one below the limit
     if (wv == kBpBlock / 64 - 1) {   // the whole LAST wave (the vertex loops below start with the first) with wave-uniform values: the chain of
                                      // 64-bit multiplies runs on the scalar unit
         const unsigned long long prime = 1099511628211ull;
         unsigned long long h = 14695981039346656037ull;
         h = (h ^ (unsigned long long)n) * prime;
         h = (h ^ (unsigned long long)cn) * prime;
-        for (uint32_t t0 = 0; t0 < cn; t0 += 64) {       // 64 columns per LDS round trip, then lane by lane out of registers (v_readlane)
-            const uint32_t tl = t0 + (uint32_t)lane < cn ? t0 + (uint32_t)lane : 0u;
+        const uint32_t st = (LARGE && cn > (uint32_t)kBpMaxCols) ? cn / 500u : 1u;
+        const uint32_t ns = LARGE ? (cn + st - 1u) / st : cn;                  // hashed columns
+        for (uint32_t t0 = 0; t0 < ns; t0 += 64) {       // 64 columns per LDS round trip, then lane by lane out of registers (v_readlane)
+            const uint32_t tl = t0 + (uint32_t)lane < ns ? (t0 + (uint32_t)lane) * st : 0u;
             const int mu = (int)LU[tl], mv = (int)LV[tl];
-            const uint32_t cnt64 = cn - t0 < 64u ? cn - t0 : 64u;
+            const uint32_t cnt64 = ns - t0 < 64u ? ns - t0 : 64u;
             for (uint32_t i = 0; i < cnt64; ++i) {
                 const uint32_t uu = (uint32_t)__builtin_amdgcn_readlane(mu, (int)i), vv = (uint32_t)__builtin_amdgcn_readlane(mv, (int)i);
                 h = (h ^ (unsigned long long)uu) * prime;
@@ -229,6 +265,7 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
     for (uint32_t t = tid; t < cn; t += kBpBlock) { atomicAdd(&CUR[LU[t]], 1u); atomicAdd(&CUR[LV[t]], 1u); }
     __syncthreads();
     for (int x = tid; x < n; x += kBpBlock) DEG[x] = (uint16_t)CUR[x];
+    if constexpr (LARGE) if (tid == 0 && cn > (uint32_t)kBpMaxCols) { a.h_fp[2 * g] = fp_sh[0]; a.h_fp[2 * g + 1] = fp_sh[1]; }   // (fenced with the block's signal)
     __syncthreads();
     // 4. row pointer (exclusive scan of the degrees) and the maximum degree
     {
@@ -291,9 +328,9 @@ __device__ __forceinline__ void bp_build_graph(const BpBuild &a) {
     }
 }
 
-template <bool FUSED>
+template <bool FUSED, int CAP>
 __global__ __launch_bounds__(kBpBlock) void ugs_bp_build(BpBuild a) {
-    bp_build_graph<FUSED>(a);
+    bp_build_graph<FUSED, CAP>(a);
     bp_signal_done(a.done, a.done_target, a.h_done, a.epoch);
 }
 
@@ -326,10 +363,12 @@ struct BpRoots {
 
 constexpr int kBrMaxN = UGS_BATCH_ROOTS_MAX_N;
 
+// CAP as in ugs_bp_build: NBR is the only column-sized array (RP as uint16_t holds 2 * 8192)
+template <int CAP>
 __global__ __launch_bounds__(kBpBlock) void ugs_bp_roots(BpRoots a) {
     __shared__ double P[kBrMaxN];                                  // bucket weight -> scaled weight -> acceptance probability, in place
     __shared__ uint16_t ORD[kBrMaxN], RNK[kBrMaxN], SDEG[kBrMaxN], ALI[kBrMaxN], LO[kBrMaxN], HI[kBrMaxN];
-    __shared__ uint16_t RP[kBrMaxN + 1], NBR[2 * kBpMaxCols];
+    __shared__ uint16_t RP[kBrMaxN + 1], NBR[2 * CAP];
     __shared__ uint16_t LIST[kBpBlock][UGS_KMAX];                  // per thread: the vertices its root has reached
     __shared__ UgsBpMissIn mi_sh;
     __shared__ unsigned long long s2_sh;
@@ -464,13 +503,14 @@ __global__ __launch_bounds__(kBpBlock) void ugs_bp_roots(BpRoots a) {
 
 hipError_t ugs_launch_batch_roots(const int64_t *d_ptr, const int64_t *d_rstart, const int64_t *d_rowptr, const int2 *d_adj, const int32_t *d_vrank,
                                   const UgsBpMissIn *h_in, UgsBpMissOut *h_out, int64_t misses, int k, UgsRootRec *d_roots, int2 *d_via,
-                                  unsigned long long *d_done, unsigned long long done_base, uint32_t *h_done, uint32_t epoch, hipStream_t s) {
+                                  unsigned long long *d_done, unsigned long long done_base, uint32_t *h_done, uint32_t epoch, int64_t max_cols, hipStream_t s) {
     if (misses <= 0) return hipSuccess;
     BpRoots a{};
     a.ptr = d_ptr; a.rstart = d_rstart; a.rowptr = d_rowptr; a.adj = d_adj; a.vrank = d_vrank; a.in = h_in; a.out = h_out;
     a.roots = d_roots; a.via = d_via; a.k = k;
     a.done = d_done; a.done_target = done_base + (unsigned long long)misses; a.h_done = h_done; a.epoch = epoch;
-    hipLaunchKernelGGL(ugs_bp_roots, dim3((unsigned)misses), dim3(kBpBlock), 0, s, a);
+    if (max_cols > kBpMaxCols) hipLaunchKernelGGL(ugs_bp_roots<kBpColsCeil>, dim3((unsigned)misses), dim3(kBpBlock), 0, s, a);
+    else hipLaunchKernelGGL(ugs_bp_roots<kBpMaxCols>, dim3((unsigned)misses), dim3(kBpBlock), 0, s, a);
     return hipGetLastError();
 }
 
@@ -482,19 +522,22 @@ int64_t ugs_batch_pass_fused_work() {
 hipError_t ugs_launch_batch_pass(const int64_t *d_src, const int64_t *d_dst, int64_t E, const int64_t *d_ptr, int64_t G, int k,
                                  int32_t *d_owner, uint32_t *d_cnt_jminc_jmax /* [3G], two-kernel variant only */, const int64_t *d_rstart,
                                  int64_t *d_rowptr, int2 *d_adj, int2 *d_adjf, int32_t *d_vrank, unsigned long long *d_bump, unsigned long long bump_base,
-                                 uint32_t epoch, void *h_back /* pinned: keys[G] u64 | cnt[G] | jminc[G] | jmax[G] | flag | done */,
-                                 unsigned long long *d_done, unsigned long long done_base, hipStream_t s) {
+                                 uint32_t epoch, void *h_back /* pinned: keys[G] u64 | fp[2G] u64 | cnt[G] | jminc[G] | jmax[G] | flag | done */,
+                                 unsigned long long *d_done, unsigned long long done_base, int64_t max_cols, hipStream_t s) {
     if (G <= 0) return hipSuccess;
     BpBuild a{};
     a.src = d_src; a.dst = d_dst; a.ptr = d_ptr; a.G = G; a.E = E; a.rstart = d_rstart; a.k = k; a.rowptr = d_rowptr; a.adj = d_adj; a.adjf = d_adjf;
     a.vrank = d_vrank;
     a.bump = d_bump; a.bump_base = bump_base; a.epoch = epoch;
     a.h_keys = static_cast<unsigned long long *>(h_back);
-    a.h_cnt = reinterpret_cast<uint32_t *>(a.h_keys + G); a.h_jminc = a.h_cnt + G; a.h_jmax = a.h_jminc + G; a.h_flag = a.h_jmax + G;
+    a.h_fp = a.h_keys + G; a.max_cols = (uint32_t)max_cols;
+    const bool large = max_cols > kBpMaxCols;                 // the limit in force picks the form: at its default every launch is the pass as it was
+    a.h_cnt = reinterpret_cast<uint32_t *>(a.h_keys + 3 * G); a.h_jminc = a.h_cnt + G; a.h_jmax = a.h_jminc + G; a.h_flag = a.h_jmax + G;
     a.h_done = a.h_flag + 1;
     a.done = d_done; a.done_target = done_base + (unsigned long long)G;
     if (G * E <= ugs_batch_pass_fused_work()) {            // every block scans every column: no assign launch, no memset, no atomics
-        hipLaunchKernelGGL(ugs_bp_build<true>, dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
+        if (large) hipLaunchKernelGGL((ugs_bp_build<true, kBpColsCeil>), dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
+        else hipLaunchKernelGGL((ugs_bp_build<true, kBpMaxCols>), dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
         return hipGetLastError();
     }
     uint32_t *d_cnt = d_cnt_jminc_jmax, *d_jminc = d_cnt + G, *d_jmax = d_jminc + G;
@@ -502,6 +545,7 @@ hipError_t ugs_launch_batch_pass(const int64_t *d_src, const int64_t *d_dst, int
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ugs_bp_assign, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, d_src, d_dst, E, d_ptr, G, d_owner, d_cnt, d_jminc, d_jmax);
     a.owner = d_owner; a.cnt = d_cnt; a.jminc = d_jminc; a.jmax = d_jmax;
-    hipLaunchKernelGGL(ugs_bp_build<false>, dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
+    if (large) hipLaunchKernelGGL((ugs_bp_build<false, kBpColsCeil>), dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
+    else hipLaunchKernelGGL((ugs_bp_build<false, kBpMaxCols>), dim3((unsigned)G), dim3(kBpBlock), 0, s, a);
     return hipGetLastError();
 }

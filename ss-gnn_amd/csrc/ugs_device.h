@@ -167,20 +167,42 @@ hipError_t ugs_launch_collate_unpack(const void *d_msgs, int world, int64_t msg_
 hipError_t ugs_launch_rebase_edge_ptr(const int64_t *in, int64_t *out, int64_t n, int64_t base, hipStream_t s);
 // device batch pass (ugs_batch.hip): slicing, LRU keys and CSR of a batch of small graphs; limits per graph of that path
 #define UGS_BATCH_PASS_MAX_COLS 1000   /* a key covers every column up to here (reference include/cache.hpp:100 samples longer graphs) */
+#define UGS_BATCH_PASS_COLS_CEIL 8192  /* the limit a caller may raise it to (ugs_set_batch_pass_max_cols): the large form of the pass's kernels */
 #define UGS_BATCH_PASS_MAX_N 2048
 #define UGS_BATCH_PASS_FUSED_WORK (4ll << 20)   /* G * E up to here: the build kernel slices the batch itself (one launch) */
 int64_t ugs_batch_pass_fused_work();             /* the limit in force: UGS_BP_FUSED_WORK overrides it (testing aid: 0 = always two kernels) */
 hipError_t ugs_launch_batch_pass(const int64_t *d_src, const int64_t *d_dst, int64_t E, const int64_t *d_ptr, int64_t G, int k,
                                  int32_t *d_owner, uint32_t *d_cnt_jminc_jmax, const int64_t *d_rstart, int64_t *d_rowptr, int2 *d_adj,
                                  int2 *d_adjf, int32_t *d_vrank, unsigned long long *d_bump, unsigned long long bump_base, uint32_t epoch, void *h_back,
-                                 unsigned long long *d_done, unsigned long long done_base, hipStream_t s);
+                                 unsigned long long *d_done, unsigned long long done_base, int64_t max_cols, hipStream_t s);
+/* what the pass hands back per call, in pinned host memory: keys[G] u64 | fp[2G] u64 | cnt[G] | jminc[G] | jmax[G] u32 | flag | done u32 */
+#define UGS_BP_BACK_CNT(G) ((size_t)(G) * 24)
+#define UGS_BP_BACK_FLAG(G) ((size_t)(G) * 36)
+#define UGS_BP_BACK_BYTES(G) ((size_t)(G) * 36 + 16)
+// Content fingerprint of a graph of more than UGS_BATCH_PASS_MAX_COLS columns -- there the reference's key samples the columns
+// (include/cache.hpp:100-107), so equal keys no longer mean equal graphs.  128 bits over (n, #columns, every renumbered column
+// with its position): two 64-bit sums of a mix of (t, u, v), so any thread may add any column; the build kernel and the host
+// (ugs_host.cpp: graph_fingerprint) compute the same value.
+__host__ __device__ inline unsigned long long ugs_fp_mix(unsigned long long x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+    return x;
+}
+__host__ __device__ inline void ugs_fp_seed(unsigned long long n, unsigned long long cols, unsigned long long &a, unsigned long long &b) {
+    a = ugs_fp_mix(n * 0x9e3779b97f4a7c15ull + cols);
+    b = ugs_fp_mix(cols * 0xc2b2ae3d27d4eb4full + n);
+}
+__host__ __device__ inline void ugs_fp_add(unsigned long long t, unsigned long long u, unsigned long long v, unsigned long long &a, unsigned long long &b) {
+    const unsigned long long ht = ugs_fp_mix(t + 0x9e3779b97f4a7c15ull), p = (u << 32) | (v & 0xffffffffull);
+    a += ugs_fp_mix(p ^ ht);
+    b += ugs_fp_mix(p * 0xc2b2ae3d27d4eb4full + ((ht >> 7) | (ht << 57)));
+}
 // graphs of a device-built plan the LRU does not know (cold path): the rest of their preprocessing on the device (ugs_bp_roots)
 #define UGS_BATCH_ROOTS_MAX_N 1024     /* larger unknown graphs are preprocessed on the host, as before */
 struct UgsBpMissIn { int32_t g; int32_t pad; int64_t roots_off; int64_t via_off; };           // arena offsets (elements) reserved by the host
 struct UgsBpMissOut { int32_t level, n_viable, nonzero, max_deg; double Z, sb_deg; };
 hipError_t ugs_launch_batch_roots(const int64_t *d_ptr, const int64_t *d_rstart, const int64_t *d_rowptr, const int2 *d_adj, const int32_t *d_vrank,
                                   const UgsBpMissIn *h_in, UgsBpMissOut *h_out, int64_t misses, int k, UgsRootRec *d_roots, int2 *d_via,
-                                  unsigned long long *d_done, unsigned long long done_base, uint32_t *h_done, uint32_t epoch, hipStream_t s);
+                                  unsigned long long *d_done, unsigned long long done_base, uint32_t *h_done, uint32_t epoch, int64_t max_cols, hipStream_t s);
 // h_total / h_flag (pinned host memory, or NULL): the kernel also hands the total to the host and signals with `epoch`
 hipError_t ugs_launch_scan(const uint32_t *counts, int64_t rows, int64_t *edge_ptr, int64_t *block_tmp, hipStream_t s, int64_t *h_total = nullptr,
                            uint32_t *h_flag = nullptr, uint32_t epoch = 0);

@@ -94,6 +94,9 @@ struct Graph {
     int64_t stub_lo = 0;              //       the batch's node offset of the graph -- what completion needs, dropped afterwards
     int64_t max_deg = 0;
     double sb_deg = 0.0;              // size-biased mean CSR degree (sum d^2 / sum d)
+    // content fingerprint (graph_fingerprint), set only for graphs of more than 1000 columns: there the LRU key samples the
+    // columns, and the device batch pass accepts a cached graph as the one it has just built only if this agrees too
+    uint64_t fp_a = 0, fp_b = 0;
     std::mutex plan_mu;
     ugs_plan *plan = nullptr;         // device-resident copy for the handle API, built on first sample()
     std::mutex pre_mu;
@@ -272,6 +275,15 @@ void complete_on_host(Graph &G) {
     G.host_ready = true;
 }
 
+// What the large form of ugs_bp_build computes for a graph of more than 1000 columns (ugs_device.h: ugs_fp_add), in plain C++:
+// covers n, the number of columns and every renumbered column with its position.
+void graph_fingerprint(const int64_t *u, const int64_t *v, int64_t cols, int64_t n, uint64_t &fa, uint64_t &fb) {
+    unsigned long long a, b;
+    ugs_fp_seed((unsigned long long)n, (unsigned long long)cols, a, b);
+    for (int64_t t = 0; t < cols; ++t) ugs_fp_add((unsigned long long)t, (unsigned long long)u[t], (unsigned long long)v[t], a, b);
+    fa = a; fb = b;
+}
+
 int preprocess_on_device(Graph &G, const int64_t *src, const int64_t *dst, int64_t E, int k, bool &done);   // below, after the device helpers
 
 int make_graph(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int k, std::shared_ptr<Graph> &out) {
@@ -280,6 +292,7 @@ int make_graph(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int
     auto G = std::make_shared<Graph>();
     G->n = n;
     G->k_built = k;
+    if (E > UGS_BATCH_PASS_MAX_COLS) graph_fingerprint(src, dst, E, n, G->fp_a, G->fp_b);
     bool on_device = false;
     if (int rc = preprocess_on_device(*G, src, dst, E, k, on_device)) return rc;
     if (!on_device) {
@@ -1055,15 +1068,20 @@ int plan_leave(ugs_plan *plan, hipStream_t s) {
 // A call with a batch that was not seen before as a whole -- in a training loop: every shuffled mini-batch, a new combination
 // of graphs the LRU already knows -- no longer walks the columns on the host.  edge_index and ptr are uploaded, one device pass
 // slices the batch, computes every graph's LRU key (the reference's FNV-1a, include/cache.hpp:81-109) and writes the plan's
-// rowptr / adj / adjf straight into HBM in the reference's CSR order (src/preproc.cpp:32-86); 16 bytes per graph come back.
+// rowptr / adj / adjf straight into HBM in the reference's CSR order (src/preproc.cpp:32-86); 36 bytes per graph come back.
 // The host replays the LRU on those keys (same lookups, same order, same eviction as the general path) and points every
 // graph's descriptor at the root records its cached preprocessing keeps in the device's arena.  Only a graph the LRU does not
 // know is sliced and preprocessed on the host (its column span comes back with its key), once.
 //
 // Applicable when ptr is non-decreasing (disjoint node ranges) and every graph has at most UGS_BATCH_PASS_MAX_N vertices and
-// UGS_BATCH_PASS_MAX_COLS columns -- up to there the key covers a graph's whole content, so a cached graph with the same key
-// has exactly the CSR the pass has just built (beyond, the reference's key samples the columns and the general path below
-// reproduces what it then does: it samples from the CACHED graph).  Everything else takes the general path.
+// at most as many columns as the limit in force: UGS_BATCH_PASS_MAX_COLS (1000) unless the caller has raised it, up to
+// UGS_BATCH_PASS_COLS_CEIL (ugs_set_batch_pass_max_cols, or UGS_BATCH_PASS_MAX_COLS in the environment).  Up to 1000 columns
+// the key covers a graph's whole content, so a cached graph with the same key has exactly the CSR the pass has just built.
+// Beyond, the reference's key samples the columns (include/cache.hpp:100-107): two different graphs can share a key, and the
+// reference then samples from the CACHED graph.  The large form of the pass computes that strided key and, beside it, a
+// 128-bit fingerprint of the whole content; a cached graph is accepted only if n, nnz and the fingerprint all agree with what
+// the pass has built -- then it IS that graph -- and anything else sends the batch to the general path below, which does what
+// the reference does.  With the limit at its default a batch holding such a graph takes the general path, as it always did.
 // UGS_DEVICE_BATCH=0 switches the pass off, =1 forces it wherever it applies (see device_batch_mode).
 // ---------------------------------------------------------------------------------------------------------------
 struct RootArena {
@@ -1201,6 +1219,22 @@ hipError_t wait_signal(const volatile uint32_t *word, uint32_t want, hipStream_t
 }
 std::atomic<int64_t> g_bp_plans{0}, g_bp_fallbacks{0};     // plans built by the device pass / calls it handed to the general path
 
+// Columns per graph up to which the pass applies: process-wide, read once per call (a call in flight keeps what it started with).
+// First use takes UGS_BATCH_PASS_MAX_COLS from the environment; out of range = ignored.
+std::atomic<int64_t> g_bp_max_cols{UGS_BATCH_PASS_MAX_COLS};
+int64_t batch_pass_max_cols() {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const char *e = std::getenv("UGS_BATCH_PASS_MAX_COLS");
+        if (!e || !*e) return;
+        char *end = nullptr;
+        const long long v = std::strtoll(e, &end, 10);
+        if (end && *end == 0 && v >= UGS_BATCH_PASS_MAX_COLS && v <= UGS_BATCH_PASS_COLS_CEIL) g_bp_max_cols.store(v);
+        else if (debug_on()) std::fprintf(stderr, "[UGS INFO] UGS_BATCH_PASS_MAX_COLS=%s ignored: must be %d ... %d\n", e, UGS_BATCH_PASS_MAX_COLS, UGS_BATCH_PASS_COLS_CEIL);
+    });
+    return g_bp_max_cols.load();
+}
+
 // Returns UGS_OK with *plan_out set, kBatchNotApplicable (the caller takes the general path; the LRU has not been touched, or
 // its counters have been put back), or an error.
 int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const int64_t *ptr, int64_t G, int k, const DeviceCtx &dc,
@@ -1208,10 +1242,11 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
     if (G <= 0 || E <= 0 || G > ((int64_t)1 << 20) || E >= ((int64_t)1 << 24)) return kBatchNotApplicable;
     RootArena *ar = arena_of(dc.id);
     if (!ar) return kBatchNotApplicable;
+    const int64_t max_cols = batch_pass_max_cols();                     // the limit in force for this call
     std::lock_guard<std::mutex> call_lk(ar->call_mu);
-    // pinned staging, one buffer: [src E | dst E | ptr G+1 | rstart G] goes up in ONE copy, [keys G | cnt G | jminc G | jmax G | flag] comes
-    // back in one, two descriptor slots go up behind the LRU replay
-    const size_t up_words = (size_t)(2 * E + 2 * G + 1), back_bytes = (size_t)G * 20 + 16, desc_bytes = (size_t)G * sizeof(UgsGraphDesc);
+    // pinned staging, one buffer: [src E | dst E | ptr G+1 | rstart G] goes up in ONE copy, [keys G | fingerprints 2G | cnt G | jminc G |
+    // jmax G | flag] comes back in one, two descriptor slots go up behind the LRU replay
+    const size_t up_words = (size_t)(2 * E + 2 * G + 1), back_bytes = UGS_BP_BACK_BYTES(G), desc_bytes = (size_t)G * sizeof(UgsGraphDesc);
     const size_t miss_bytes = (size_t)G * (sizeof(UgsBpMissIn) + sizeof(UgsBpMissOut)) + 16;
     const size_t st_back = align_up(up_words * 8), st_desc = align_up(st_back + back_bytes), st_miss = align_up(st_desc + 2 * align_up(desc_bytes)),
                  st_total = align_up(st_miss + miss_bytes);
@@ -1253,19 +1288,19 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
     hipStream_t s = dc.stream;
     Lap lap;
     auto *d_src = reinterpret_cast<int64_t *>(base + o_up), *d_dst = d_src + E, *d_ptr = d_dst + E;
-    // what comes back is written by the kernel straight into the pinned staging (keys[G] u64 | cnt[G] | jminc[G] | jmax[G] | flag): no
+    // what comes back is written by the kernel straight into the pinned staging (keys[G] u64 | fp[2G] u64 | cnt[G] | jminc[G] | jmax[G] | flag): no
     // copy command behind the kernel, the host waits for the stream only
     char *h_back = static_cast<char *>(ar->pinned) + st_back;
     const uint32_t epoch = ++ar->epoch ? ar->epoch : ++ar->epoch;       // never 0
-    *reinterpret_cast<volatile uint32_t *>(h_back + (size_t)G * 20) = 0u;
-    *reinterpret_cast<volatile uint32_t *>(h_back + (size_t)G * 20 + 4) = 0u;     // the completion word: the staging's layout moves with E and G, so the
+    *reinterpret_cast<volatile uint32_t *>(h_back + UGS_BP_BACK_FLAG(G)) = 0u;
+    *reinterpret_cast<volatile uint32_t *>(h_back + UGS_BP_BACK_FLAG(G) + 4) = 0u;     // the completion word: the staging's layout moves with E and G, so the
                                                                                    // word may hold anything an earlier call left there -- e.g. a column count equal to this epoch
     hipError_t e = hipMemcpyAsync(d_src, hostv, up_words * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = ugs_launch_batch_pass(d_src, d_dst, E, d_ptr, G, k, reinterpret_cast<int32_t *>(base + o_owner), reinterpret_cast<uint32_t *>(base + o_cnt),
                                                    d_ptr + (G + 1), reinterpret_cast<int64_t *>(base + o_row), reinterpret_cast<int2 *>(base + o_adj),
                                                    reinterpret_cast<int2 *>(base + o_adjf), reinterpret_cast<int32_t *>(base + o_vrank), ar->d_bump, ar->bump_host,
-                                                   epoch, h_back, ar->d_bump + 1, ar->done_host, s);
-    if (e == hipSuccess) e = wait_signal(reinterpret_cast<volatile uint32_t *>(h_back + (size_t)G * 20 + 4), epoch, s);
+                                                   epoch, h_back, ar->d_bump + 1, ar->done_host, max_cols, s);
+    if (e == hipSuccess) e = wait_signal(reinterpret_cast<volatile uint32_t *>(h_back + UGS_BP_BACK_FLAG(G) + 4), epoch, s);
     if (e != hipSuccess) {       // the counters' values are unknown now: start again from zero
         (void)hipDeviceSynchronize();
         (void)hipMemset(ar->d_bump, 0, 16); ar->bump_host = 0; ar->done_host = 0;
@@ -1274,7 +1309,14 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
     ar->done_host += (unsigned long long)G;
     const double t_pass = lap();
     const auto *h_keys = reinterpret_cast<const unsigned long long *>(h_back);
-    const auto *h_cnt = reinterpret_cast<const uint32_t *>(h_back + (size_t)G * 8), *h_jminc = h_cnt + G, *h_jmax = h_jminc + G;
+    const auto *h_fp = h_keys + G;                                      // two words per graph, written for graphs of more than 1000 columns only
+    const auto *h_cnt = reinterpret_cast<const uint32_t *>(h_back + UGS_BP_BACK_CNT(G)), *h_jminc = h_cnt + G, *h_jmax = h_jminc + G;
+    // Is the cached graph `c` the graph the pass has just built as graph g?  Up to 1000 columns the key covers the content (n and nnz
+    // guard a 64-bit collision); above, the key samples the columns and the fingerprint decides.
+    auto same_graph = [&](const Graph &c, int64_t g, int64_t n) {
+        if (c.n != n || c.nnz != 2 * (int64_t)h_cnt[g]) return false;
+        return h_cnt[g] <= (uint32_t)UGS_BATCH_PASS_MAX_COLS || (c.fp_a == (uint64_t)h_fp[2 * g] && c.fp_b == (uint64_t)h_fp[2 * g + 1]);
+    };
     {   // the counter moved by twice the columns of the graphs that got as far as their allocation: re-derive it from what came back
         unsigned long long used = 0;
         for (int64_t g = 0; g < G; ++g) used += 2ull * h_cnt[g];
@@ -1343,6 +1385,7 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
             }
             gr = std::make_shared<Graph>();
             gr->n = n; gr->nnz = 2 * (int64_t)h_cnt[g]; gr->k_built = k; gr->host_ready = false; gr->stub_lo = lo;
+            if (h_cnt[g] > (uint32_t)UGS_BATCH_PASS_MAX_COLS) { gr->fp_a = (uint64_t)h_fp[2 * g]; gr->fp_b = (uint64_t)h_fp[2 * g + 1]; }
             if (h_cnt[g]) {                                              // its span of the columns, kept until some host path needs the arrays
                 const int64_t j0 = (int64_t)(0xFFFFFFFFu - h_jminc[g]), j1 = (int64_t)h_jmax[g] + 1;
                 gr->stub_cols.resize((size_t)(2 * (j1 - j0)));
@@ -1366,7 +1409,7 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
             bool mine = false;
             for (size_t i = 0; i < pend.size() && !mine; ++i) if (pend[i].gr.get() == gr.get()) { pend_of[(size_t)g] = (int32_t)i; mine = true; }
             if (mine) {
-                if (gr->n != n || gr->nnz != 2 * (int64_t)h_cnt[g]) return give_up();
+                if (!same_graph(*gr, g, n)) return give_up();             // (above 1000 columns: two graphs of this batch sharing a strided key)
                 touched.emplace_back(key, handle);
                 graphs[(size_t)g] = gr;
                 continue;
@@ -1386,7 +1429,7 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
             if (lru().put(key, handle, ev)) evicted.push_back(ev);
             inserted.emplace_back(key, handle);
         }
-        if (gr->n != n || gr->nnz != 2 * (int64_t)h_cnt[g]) return give_up();   // a 64-bit key collision: let the general path do what the reference does
+        if (!same_graph(*gr, g, n)) return give_up();                    // a key collision (64-bit, or of the strided key): let the general path do what the reference does
         Graph::DevRoots dr{};
         if (int rc = graph_dev_roots(*gr, dc.id, ar, s, dr)) { if (rc == UGS_E_UNSUPPORTED) return give_up(); give_up(); return rc; }
         d.n = (int32_t)n; d.level = gr->level; d.n_viable = (int32_t)gr->n_viable;
@@ -1403,7 +1446,7 @@ int device_batch_plan(const int64_t *src, const int64_t *dst, int64_t E, const i
         *reinterpret_cast<volatile uint32_t *>(h_rdone) = 0u;
         e = ugs_launch_batch_roots(d_ptr, d_ptr + (G + 1), reinterpret_cast<const int64_t *>(base + o_row), reinterpret_cast<const int2 *>(base + o_adj),
                                    reinterpret_cast<const int32_t *>(base + o_vrank), h_in, h_out, (int64_t)pend.size(), k, ar->roots, ar->via,
-                                   ar->d_bump + 1, ar->done_host, h_rdone, epoch, s);
+                                   ar->d_bump + 1, ar->done_host, h_rdone, epoch, max_cols, s);
         if (e == hipSuccess) e = wait_signal(h_rdone, epoch, s);
         if (e != hipSuccess) {
             (void)hipDeviceSynchronize();
@@ -1557,6 +1600,17 @@ int ugs_cache_clear(void) {
     batch_index_clear();
     return UGS_OK;
 }
+
+int ugs_set_batch_pass_max_cols(int64_t cols, int64_t *previous_out) {
+    const int64_t cur = batch_pass_max_cols();                          // the environment's value first, so that it cannot overwrite this one later
+    if (cols < UGS_BATCH_PASS_MAX_COLS || cols > UGS_BATCH_PASS_COLS_CEIL)
+        return fail(UGS_E_BAD_ARG, "batch pass column limit must be " + std::to_string(UGS_BATCH_PASS_MAX_COLS) + " ... " + std::to_string(UGS_BATCH_PASS_COLS_CEIL) +
+                                       " (got " + std::to_string(cols) + ", still " + std::to_string(cur) + ")");
+    const int64_t prev = g_bp_max_cols.exchange(cols);
+    if (previous_out) *previous_out = prev;
+    return UGS_OK;
+}
+int64_t ugs_batch_pass_max_cols(void) { return batch_pass_max_cols(); }
 
 int ugs_batch_pass_stats(int64_t *device_plans, int64_t *general_path) {
     if (device_plans) *device_plans = g_bp_plans.load();

@@ -393,6 +393,22 @@ def batch_pass_stats():
     return {"device_plans": a.value, "general_path": b.value}
 
 
+def batch_pass_max_cols():
+    """Columns per graph up to which the device batch pass applies (default 1000, or UGS_BATCH_PASS_MAX_COLS from the environment)."""
+    return int(lib.ugs_batch_pass_max_cols())
+
+
+def set_batch_pass_max_cols(cols):
+    """Raise (or restore) the per-graph column limit of the device batch pass, 1000 ... 8192; returns the previous value.
+
+    Above 1000 columns the reference's LRU key samples a graph's columns; with the limit raised the pass computes that key and a
+    content fingerprint on the device, so batches of larger graphs (COCO-SP: ~2.7 k columns) no longer slice, hash and preprocess
+    on the host.  Process-wide; results are the same at every setting.  RuntimeError outside the range, the value is kept."""
+    prev = C.c_int64()
+    check(lib.ugs_set_batch_pass_max_cols(int(cols), C.byref(prev)))
+    return prev.value
+
+
 def cache_stats():
     s, h, m = C.c_int64(), C.c_int64(), C.c_int64()
     check(lib.ugs_cache_stats(C.byref(s), C.byref(h), C.byref(m)))

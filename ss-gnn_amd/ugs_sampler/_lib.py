@@ -57,6 +57,7 @@ def _load():
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
+        "ugs_set_batch_pass_max_cols": [C.c_int64, i64p],
         "ugs_plan_create_batch": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.POINTER(vp)],
         "ugs_plan_create_handle": [C.c_int64, C.POINTER(vp)],
         "ugs_plan_release": [vp],
@@ -80,7 +81,9 @@ def _load():
         fn = getattr(L, name)          # AttributeError here = the library does not export what the header declares
         fn.argtypes = argtypes
         fn.restype = C.c_int
-    return L, sorted(list(sig) + ["ugs_last_error", "ugs_version"])
+    L.ugs_batch_pass_max_cols.argtypes = []
+    L.ugs_batch_pass_max_cols.restype = C.c_int64
+    return L, sorted(list(sig) + ["ugs_last_error", "ugs_version", "ugs_batch_pass_max_cols"])
 
 
 lib, EXPORTS = _load()

@@ -14,6 +14,7 @@ TU_SHAPES = {
     "c2_mutag_b1024": (18, 20, 4, 32, 32),
     "c3_proteins_b8192": (39, 73, 6, 32, 256),
     "c4_qm9_b65536": (18, 19, 5, 32, 2048),
+    "c6_cocosp_b3200": (477, 1347, 8, 32, 100),       # LRGB COCO-SP-shaped: ~2.7 k columns per graph, above the default limit of the device batch pass
 }
 
 

@@ -7,13 +7,16 @@ Three synthetic datasets (ugs_workloads.tu_graph, both edge directions stored):
             that every graph is within uniform_sampler's 64-vertex limit;
   qm9       20 000 graphs of 9..29 vertices, 1.04 undirected edges per vertex;
   cocosp    2 000 graphs of tu_graph(477, 1347), the COCO-SP shape (ugs only, at k = 8, m = 100: every graph is over the device
-            batch pass's 1000-column limit, so each is preprocessed on the host).
+            batch pass's default 1000-column limit, so each is preprocessed on the host).  --large-pass times add_many a second
+            time with the limit raised to 8192 (ugs_sampler.set_batch_pass_max_cols), the two settings' runs taking turns, checks
+            the two caches equal and writes profiles/presample_bench_large_pass.json.
 ugs and uniform run at k = 6, m = 64 and rwr at k = 5, m = 50, seeds 42 + i; ugs starts every timed build from an empty
 preprocessing LRU (clear_cache: what the trainer's start-up sees).  Timings are wall time to a synchronised device, after a
 warm-up on the first 64 graphs: add_many the median of three runs, the loop one run; both caches are checked equal (load of every graph) before the numbers are written.
 
     python tools/presample_bench.py [--only qm9] [--sampler rwr] [--out profiles/presample_bench.json]
     python tools/presample_bench.py --only qm9 --many-only        # add_many alone, e.g. under rocprofv3 --kernel-trace --stats
+    python tools/presample_bench.py --large-pass                   # cocosp, add_many at limit 1000 and 8192
 """
 import argparse
 import json
@@ -75,13 +78,53 @@ def same(a, b, G):
         assert torch.equal(x, y), "caches differ"
 
 
+def large_pass(out):
+    """cocosp / ugs: add_many with the batch pass's column limit at 1000 and at 8192, three fresh caches each, alternating"""
+    import ugs_sampler
+    dev = "cuda:0"
+    graphs = dataset("cocosp")
+    G = len(graphs)
+    seeds = [42 + i for i in range(G)]
+    ts, caches = {1000: [], 8192: []}, {}
+    try:
+        for lim in ts:
+            ugs_sampler.set_batch_pass_max_cols(lim)
+            PresampleCache(COCOSP["m"], COCOSP["k"], dev, sampler="ugs").add_many(range(64), graphs[:64], seeds[:64])      # warm-up
+        for _ in range(3):
+            for lim in ts:
+                ugs_sampler.set_batch_pass_max_cols(lim)
+                many = PresampleCache(COCOSP["m"], COCOSP["k"], dev, sampler="ugs")
+                s0 = ugs_sampler.batch_pass_stats()
+                ts[lim].append(timed(lambda: many.add_many(range(G), graphs, seeds), "ugs"))
+                s1 = ugs_sampler.batch_pass_stats()
+                caches[lim] = (many, {k: s1[k] - s0[k] for k in s1})
+    finally:
+        ugs_sampler.set_batch_pass_max_cols(1000)
+    same(caches[1000][0], caches[8192][0], G)
+    rec = dict(dataset="cocosp", sampler="ugs", graphs=G, k=COCOSP["k"], m=COCOSP["m"], caches_equal=True)
+    for lim, v in ts.items():
+        rec[f"limit_{lim}"] = dict(add_many_s=round(sorted(v)[1], 4), add_many_runs_s=[round(t, 4) for t in v],
+                                   add_many_us_per_graph=round(1e6 * sorted(v)[1] / G, 2), batch_pass_stats_delta=caches[lim][1])
+    rec["speedup_of_the_raised_limit"] = round(sorted(ts[1000])[1] / sorted(ts[8192])[1], 2)
+    print(json.dumps(rec), flush=True)
+    meta = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, hip=torch.version.hip,
+                note="wall time to a synchronised device, empty preprocessing LRU before every run; medians of three runs per setting, alternated")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(meta=meta, results=[rec]), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=list(DATASETS))
     ap.add_argument("--sampler", choices=list(CONFIGS))
     ap.add_argument("--many-only", action="store_true", help="time add_many alone (no loop, no check, no file)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "presample_bench.json"))
+    ap.add_argument("--large-pass", action="store_true", help="cocosp only: add_many at column limit 1000 and 8192 of the device batch pass")
+    ap.add_argument("--large-pass-out", default=os.path.join(ROOT, "profiles", "presample_bench_large_pass.json"))
     a = ap.parse_args()
+    if a.large_pass:
+        return large_pass(a.large_pass_out)
     dev = "cuda:0"
     results = []
     for dname in [a.only] if a.only else list(DATASETS):
