@@ -988,8 +988,10 @@ __device__ __forceinline__ void stage_hits(StageCtx &sc, const Grp<GS> &g, bool 
 // for in a LATER block than its compare is rebuilt by the compiler from a 0/1 vector (v_cndmask + v_cmp_ne and a wait-state filler
 // between them); a mask taken on the spot is the compare's own result, stays in scalar registers, and comes back as a lane
 // predicate for free (inverse ballot: the mask goes straight into EXEC).
+// SON: the launch is known to stage (do_walk's UNI instantiation), so the mask needs no AND with `onm`.
+template <bool SON = false>
 __device__ __forceinline__ void stage_hits_mask(StageCtx &sc, const Grp<64> &g, uint64_t im, uint32_t w, uint32_t p, uint32_t size) {
-    im &= sc.onm;
+    if constexpr (!SON) im &= sc.onm;
     if (!im) return;
     const uint32_t slot = sc.ne + g.below(im);
     if (__builtin_amdgcn_inverse_ballot_w64(im) && slot < UGS_STAGE_ENTRIES) sc.EL[slot] = make_uint4(p, w, size - 1u, 0u);
@@ -1111,12 +1113,26 @@ __device__ __forceinline__ void probe_find_lds_v(const uint32_t *HK, uint32_t hm
         : "vcc", "memory");
 }
 
+// A chunk that holds a vertex more than once (both directions of an edge, a multi-edge): of the lanes holding it the lowest one
+// inserted it, the others met its fresh key (`dupm`).  Returns the first-occurrence mask.  Rare: behind an unlikely branch, so the
+// compiler places the loop behind the kernel's end and the chunk's straight path pays one untaken branch for it.
+__device__ __forceinline__ uint64_t first_of_repeated(const Grp<64> &g, uint32_t w, uint64_t insm, uint64_t dupm) {
+    uint64_t fm = insm;
+    while (dupm) {
+        const uint32_t wi = g.bcast(w, __builtin_ctzll(dupm));
+        const uint64_t grp = __ballot(w == wi);                   // (a vertex has one rank: its lanes are candidates all or none)
+        fm = (fm & ~grp) | (grp & (0ull - grp));
+        dupm &= ~grp;
+    }
+    return fm;
+}
+
 // One chunk of an adjacency row: lane holds entry e (neighbour, rank) at CSR position p (a plan has < 2^31 entries); lanes
 // without an entry hold kNoEntry, whose rank -1 fails the suffix filter, so `cand` is one signed compare (ranks are < 2^30).
 // (their vertex number, all ones, equals no vertex: a test `w == some candidate` needs no `cand &&` in front)
 #define UGS_NO_ENTRY make_int2(-1, -1)
 // GUARD = false: the caller has checked that the whole row fits (candidates and table entries), so the per-chunk tests are left out.
-template <int GS, class SP, bool ADD, bool STG, bool GUARD = true>
+template <int GS, class SP, bool ADD, bool STG, bool GUARD = true, bool SON = false>
 __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g, uint32_t v, uint32_t root_vi, uint32_t size, uint32_t &c,
                                            uint32_t &hcount, uint32_t &ecount, StageCtx &sc, int2 e, uint32_t p) {
     const uint32_t w = (uint32_t)e.x;
@@ -1133,22 +1149,21 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
             STAMP_SUB_BEGIN();
             slot = probe_insert_lds(ws.HK, ws.hmask, slot, step, w, seen, e.y, root_vi);
             STAMP_SUB_END_OF(1, 6);
+            // What a lane's probe ended on, read off `seen` with one signed compare each: kEmpty (-1) = this lane inserted; a found key
+            // carries w (< 2^30) and at most one flag -- kInS makes the word negative (and not -1), kFresh makes it >= 2^30; a lane that
+            // is no candidate keeps kKeyMask, below 2^30.  (Three compares; the masked-equality form took three more vector
+            // instructions and a literal each.)
             const uint64_t insm = __ballot(seen == kEmpty);                                     // inserted by this lane
-            const uint64_t im = __ballot((seen & (kKeyMask | kInS)) == (w | kInS));             // found, and a member of the sample
-            uint64_t dupm = __ballot((seen & (kKeyMask | kFresh)) == (w | kFresh));             // found, and inserted by this very chunk
+            const uint64_t im = __ballot((int)seen < -1);                                       // found, and a member of the sample
+            const uint64_t dupm = __ballot((int)seen >= (int)kFresh);                           // found, and inserted by this very chunk
             SP::sync();
             // first occurrences (see below): the inserting lanes, except that a vertex repeated inside the chunk is represented by
-            // the LOWEST lane holding it
+            // the LOWEST lane holding it.  No repeated vertex is the rule: that path carries `insm` itself and no loop set-up.
             uint64_t fm = insm;
-            while (dupm) {
-                const uint32_t wi = g.bcast(w, __builtin_ctzll(dupm));
-                const uint64_t grp = __ballot(w == wi);           // (a vertex has one rank: its lanes are candidates all or none)
-                fm = (fm & ~grp) | (grp & (0ull - grp));
-                dupm &= ~grp;
-            }
+            if (__builtin_expect(dupm != 0ull, 0)) fm = first_of_repeated(g, w, insm, dupm);
             if (__builtin_amdgcn_inverse_ballot_w64(insm)) ws.HK[slot] = w;                      // the chunk is over for this key: drop kFresh
             ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;         // per lane, summed over the wave at the end of the walk
-            if constexpr (STG) stage_hits_mask(sc, g, im, w, p, size);
+            if constexpr (STG) stage_hits_mask<SON>(sc, g, im, w, p, size);
             const uint32_t nnew = (uint32_t)__popcll(fm);
             if constexpr (GUARD) { if (c + nnew > ws.cap) return false; }
             if (__builtin_amdgcn_inverse_ballot_w64(fm)) ws.D[c + g.below(fm)] = w;
@@ -1158,9 +1173,9 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
         } else {
             uint32_t seen = kEmpty;
             probe_find_lds(ws.HK, ws.hmask, slot, step, w, seen, e.y, root_vi);
-            const uint64_t im = __ballot((seen & (kKeyMask | kInS)) == (w | kInS));             // kEmpty (no candidate, or not seen) matches no vertex
+            const uint64_t im = __ballot((int)seen < -1);             // a found key with kInS; kEmpty (-1: no candidate, or not seen) is not below -1
             ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;
-            if constexpr (STG) stage_hits_mask(sc, g, im, w, p, size);
+            if constexpr (STG) stage_hits_mask<SON>(sc, g, im, w, p, size);
         }
         return true;
     } else
@@ -1267,7 +1282,7 @@ __device__ __forceinline__ int2 load_prow(const UgsPlanDev &P, int64_t vrow, int
     return e;
 }
 
-template <class SP, bool ADD, bool STG>
+template <class SP, bool ADD, bool STG, bool SON = false>
 __device__ __forceinline__ bool scan_prow(const Work<SP> &ws, const Grp<64> &g, const UgsPlanDev &P, uint32_t v,
                                           uint32_t root_vi, uint32_t size, uint32_t &c, uint32_t &hcount,
                                           uint32_t &ecount, int2 e0, int64_t vrow, StageCtx &sc) {
@@ -1283,27 +1298,36 @@ __device__ __forceinline__ bool scan_prow(const Work<SP> &ws, const Grp<64> &g, 
     // others take the guarded chunks, so the walks a tier hands on are exactly those it handed on before
     // (`n0 != 0` is tested on an opaque scalar copy in each path: shared between the two, the compiler carries the condition through
     // a vector register -- v_cndmask, v_cmp_ne, s_and, s_cbranch_vccnz)
+    // The row that fits its block is the rule, the tail in adj[] and the guarded chunks the exceptions: both are marked unlikely, so
+    // that the straight path from here to the end of the row's one chunk falls through its branches and carries neither the tail
+    // loop's bounds nor the flags that merge the paths.
     uint32_t n0a = n0, n0b = n0;
     asm volatile("" : "+s"(n0a));
     asm volatile("" : "+s"(n0b));
-    if (ADD && hcount + deg <= ws.hlimit && c + deg <= ws.cap) {
-        if (n0a) scan_chunk<64, SP, ADD, STG, false>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e0, start + (uint32_t)g.lane - 1u);
+    if constexpr (ADD) {
+        if (__builtin_expect(hcount + deg <= ws.hlimit && c + deg <= ws.cap, 1)) {
+            if (n0a) scan_chunk<64, SP, true, STG, false, SON>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e0, start + (uint32_t)g.lane - 1u);
+            if (__builtin_expect(deg > inl, 0)) {
+                const uint32_t r1 = start + deg;
+                for (uint32_t base = start + inl; base < r1; base += 64) {
+                    const uint32_t p = base + (uint32_t)g.lane;
+                    int2 e = UGS_NO_ENTRY;
+                    if (p < r1) e = P.adj[p];
+                    scan_chunk<64, SP, true, STG, false, SON>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e, p);
+                }
+            }
+            return true;
+        }
+    }
+    if (n0b && !scan_chunk<64, SP, ADD, STG, true, SON>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e0, start + (uint32_t)g.lane - 1u)) return false;
+    if (__builtin_expect(deg > inl, 0)) {
         const uint32_t r1 = start + deg;
         for (uint32_t base = start + inl; base < r1; base += 64) {
             const uint32_t p = base + (uint32_t)g.lane;
             int2 e = UGS_NO_ENTRY;
             if (p < r1) e = P.adj[p];
-            scan_chunk<64, SP, ADD, STG, false>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e, p);
+            if (!scan_chunk<64, SP, ADD, STG, true, SON>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e, p)) return false;
         }
-        return true;
-    }
-    if (n0b && !scan_chunk<64, SP, ADD, STG>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e0, start + (uint32_t)g.lane - 1u)) return false;
-    const uint32_t r1 = start + deg;
-    for (uint32_t base = start + inl; base < r1; base += 64) {
-        const uint32_t p = base + (uint32_t)g.lane;
-        int2 e = UGS_NO_ENTRY;
-        if (p < r1) e = P.adj[p];
-        if (!scan_chunk<64, SP, ADD, STG>(ws, g, v, root_vi, size, c, hcount, ecount, sc, e, p)) return false;
     }
     return true;
 }
@@ -1416,17 +1440,22 @@ __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const
 // per CU instead of three).  An 8-lane walk is a chain of LDS round trips of its own order stages; the two L2 round trips per step it
 // saved do not show.  The same copy for the fill kernels (row pointer and (neighbour, column) entries): 12.4 against 12.4 us and 25.5
 // against 25.0 us.  Neither kept.)
-template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false>
+// UNI: facts that hold for a whole launch, fixed at compile time the way SEEDS is (the launcher picks the instantiation): the plan is ONE
+// graph (no row -> graph division), the walk stages its hits (no `onm` mask ANDed into every chunk's hit mask), and the rows are
+// taken by index (no list of handed-on rows).  Only the 448-candidate tier with padded rows has such an instantiation.
+template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false>
 __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, const UgsWalkArgs &a, int64_t row_rel,
                                         uint32_t *SV /* [UGS_KMAX] group-private */, uint4 *EL /* [UGS_STAGE_ENTRIES] or null */,
                                         uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */) {
 
     static_assert(!PAD || GS == 64, "padded rows are read by a whole wave");
+    static_assert(!UNI || (PAD && !SEEDS && sizeof(typename SP::TW) == 4), "UNI: one graph, one seed, padded rows, staging on");
     const Grp<GS> &g = g_;
     constexpr bool STG = GS == 64 && sizeof(typename SP::TW) == 4;             // one walk per wave, LDS workspace
     StageCtx sc;
     sc.EL = EL; sc.ne = 0u; sc.on = STG && a.stage != nullptr && EL != nullptr; sc.onm = 0ull;
-    if constexpr (STG) {      // (opaque, or the compiler turns `hits & onm` back into two tests)
+    if constexpr (UNI) { sc.on = true; sc.onm = ~0ull; }
+    else if constexpr (STG) {      // (opaque, or the compiler turns `hits & onm` back into two tests)
         uint32_t on32 = g.uni(sc.on ? 1u : 0u);
         asm volatile("" : "+s"(on32));
         sc.onm = 0ull - (uint64_t)on32;
@@ -1434,7 +1463,7 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     const UgsPlanDev &P = a.plan;
     const int64_t row = a.row_begin + row_rel;
     int64_t gi, i;
-    if (P.num_graphs == 1) { gi = 0; i = row; }
+    if (UNI || P.num_graphs == 1) { gi = 0; i = row; }
     else { gi = row / a.m; i = row - gi * a.m; }
     const UgsGraphDesc gd = P.graphs[gi];
     const int k = a.k;
@@ -1525,10 +1554,10 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
 #endif
         bool ok;
         if (step < k - 1) {                                                   // the last vertex adds no candidates
-            if constexpr (PAD) ok = scan_prow<SP, true, STG>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
+            if constexpr (PAD) ok = scan_prow<SP, true, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
             else ok = scan_row<GS, SP, true, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
         } else {
-            if constexpr (PAD) ok = scan_prow<SP, false, STG>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
+            if constexpr (PAD) ok = scan_prow<SP, false, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
             else ok = scan_row<GS, SP, false, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
         }
         STAMP_END(1);
@@ -1669,7 +1698,7 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     // one word per row: the edge-entry count and, in its top bit, whether the row's items are staged (one store instead of two)
     if (g.lane == 0) a.counts[row_rel] = nedges | (flush ? UGS_COUNT_STAGED : 0u);
     if (nedges_out) *nedges_out = nedges;
-    if (a.stage) {                                                               // staging is on for this call
+    if (UNI || a.stage) {                                                        // staging is on for this call
         if constexpr (STG) { if (flush) stage_flush(sc.ne, g, SV, (uint32_t)k, en, ecol, a.stage + row_rel * UGS_STAGE_ITEMS); }
         if (g.lane == 0 && !flush && nedges != 0u) a.ulist[atomicAdd(a.ucount, 1u)] = row_rel;
     }
@@ -1698,7 +1727,7 @@ template <int CAP> struct TierCfg {
 // admits 18 one-wave blocks per CU (5,5,4,4 per SIMD).  With a STATIC split of the rows 18 blocks/CU was slower than 16
 // (10.63 vs 10.43 ms: a launch ended with the waves of the fuller SIMDs); with the shared work counter the extra waves are
 // pure throughput: 8.81 -> 8.51 ms.  Spilling further to reach more waves costs more than it brings (30 % in an early build).
-template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false>
+template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false, bool UNI = false>
 __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 5 : (CAP == 704 ? 3 : (CAP <= 64 || CAP == 1024 || CAP == 1408 ? 2 : 1)))) void ugs_walk_lds(UgsWalkArgs a) {
     using Cfg = TierCfg<CAP>;
     constexpr int GROUPS = BLOCK / GS;
@@ -1726,7 +1755,7 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
     ws.ST = stamps;
     struct Flush { unsigned long long *st; __device__ ~Flush() { __syncthreads(); if (threadIdx.x < 32) atomicAdd(&ugs_stamp_buffer[threadIdx.x], st[threadIdx.x]); } } flush_{stamps};
 #endif
-    const int64_t total = a.in_list ? (int64_t)*a.in_count : a.row_count;
+    const int64_t total = (!UNI && a.in_list) ? (int64_t)*a.in_count : a.row_count;
     const int64_t ngroups = (int64_t)gridDim.x * GROUPS;
     // Work distribution.  Dynamic (a.work_next, launches with many more walks than resident groups): chunks of UGS_WORK_CHUNK
     // consecutive items, the first chunk by group index, every further one from a device counter (one round trip per chunk: a
@@ -1745,8 +1774,8 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         while (it < total) {
             if (end > total) end = total;
             for (; it < end; ++it) {
-                const int64_t row_rel = a.in_list ? a.in_list[it] : it;
-                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS>(ws, g, a, row_rel, SV, EL)) {
+                const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
+                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI>(ws, g, a, row_rel, SV, EL)) {
                     if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
                 }
             }
@@ -1792,8 +1821,8 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         }
     }
     for (int64_t it = (int64_t)blockIdx.x * GROUPS + gib; it < total; it += ngroups) {
-        const int64_t row_rel = a.in_list ? a.in_list[it] : it;
-        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS>(ws, g, a, row_rel, SV, EL)) {
+        const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
+        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI>(ws, g, a, row_rel, SV, EL)) {
             if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
         }
     }
@@ -2262,6 +2291,15 @@ static hipError_t launch_lds(const UgsWalkArgs &a, int cus, int blocks_per_cu, h
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
     const bool pad = kCanPad && a.plan.prow;
+    // the launch-uniform facts of do_walk's UNI instantiation (the flagship shape: one large graph, one seed, staged hits)
+    constexpr bool kCanUni = GS == 64 && CAP == 448;
+    if constexpr (kCanUni) {
+        if (pad && !a.seeds && a.stage && a.plan.num_graphs == 1 && !a.in_list) {
+            hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanUni, false, kCanUni>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
+            if (info) { info->name = name; info->grid = (int)grid; info->block = BLOCK; info->lds_bytes = GROUPS * TierCfg<CAP>::WORDS * 4; }
+            return hipGetLastError();
+        }
+    }
     if (a.seeds) {          // per-graph seeds: instantiations of their own, so that a call without them runs the code it always ran
         if (pad) hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanPad, true>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
         else hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, false, true>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);

@@ -40,12 +40,12 @@ template <int STAGE, int NJ, bool REG = true> __global__ __launch_bounds__(64, 5
     else p = stage_final<64, NJ>(pw.ws, g, pw.ws.ORD + C::OOLD, C::NOLD, c, C::B, C::M, C::S, rsel);
     out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + p.w + p.q;
 }
-template <bool ADD> __global__ __launch_bounds__(64, 5) void probe_chunk(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel, const int2 *adj, uint2 *stage) {
+template <bool ADD, bool GUARD = true, bool SON = false> __global__ __launch_bounds__(64, 5) void probe_chunk(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel, const int2 *adj, uint2 *stage) {
     PROBE_PRE
     StageCtx sc; sc.EL = pw.EL; sc.ne = rsel & 3; sc.on = stage != nullptr; { uint32_t on32 = (uint32_t)__builtin_amdgcn_readfirstlane(sc.on ? 1 : 0); asm volatile("" : "+s"(on32)); sc.onm = 0ull - (uint64_t)on32; }
     uint32_t hcount = c + 3, ecount = rsel >> 8, cc = c;
     int2 e = UGS_NO_ENTRY; if (threadIdx.x < 40) e = adj[threadIdx.x];
-    const bool ok = scan_chunk<64, LdsSpace, ADD, true>(pw.ws, g, rsel, c >> 3, 3, cc, hcount, ecount, sc, e, threadIdx.x + 1000u);
+    const bool ok = scan_chunk<64, LdsSpace, ADD, true, GUARD, SON>(pw.ws, g, rsel, c >> 3, 3, cc, hcount, ecount, sc, e, threadIdx.x + 1000u);
     out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + cc + hcount + ecount + sc.ne + (ok ? 1u : 0u);
 }
 __global__ __launch_bounds__(64, 5) void probe_draw(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel) {
@@ -81,4 +81,8 @@ template __global__ void probe_matlds<3, 3>(uint32_t *, const uint32_t *, uint32
 template __global__ void probe_matlds<4, 5>(uint32_t *, const uint32_t *, uint32_t, uint32_t);
 template __global__ void probe_chunk<true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
 template __global__ void probe_chunk<false>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk<true, false>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk<false, false>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk<true, false, true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk<false, false, true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
 }  // namespace
