@@ -296,8 +296,15 @@ int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_inde
  *      (never all C(n, k)), per-root sort into lexicographic order, one-workgroup mt19937_64, rows and edges.  Bit-exact.
  *      Same two-phase job protocol and stream rules as ugs_sample_batch_*; finish writes nodes[G*m,k], edge_index[2,total],
  *      edge_ptr[G*m+1], sample_ptr[G+1], edge_src[total].
+ *      Representation.  A graph of at most 64 vertices holds a set as a 64-bit mask (sort key: the bit-reversed mask,
+ *      complemented).  A WIDE graph -- more than 64 vertices -- holds it as its ascending tuple t packed big-endian in fields of
+ *      b = bit length of n - 1 bits: key = sum of t[i] << (b (k - 1 - i)).  Ascending keys are the reference's order and the root is
+ *      the first field, so sorting, draws and rows are shared by both forms; the law above is the same.  A graph takes the wide form
+ *      when 64 < n <= the limit in force (ugs_uniform_set_max_vertices, default 64: no graph does), 1 <= k <= 8 and k b <= 64:
+ *      n <= 1024 up to k = 6, n <= 512 at k = 7, n <= 256 at k = 8.
  *      Errors: UGS_E_BAD_ARG for num_graphs < 0 (empty ptr), m < 0, k < 0, a decreasing ptr (the reference aborts on the last
- *      three); UGS_E_UNSUPPORTED for a graph of more than 64 vertices with at least k vertices, and for a call with more than
+ *      three); UGS_E_UNSUPPORTED for a graph with at least k vertices that has more than 64 and either more than the limit in
+ *      force or a k outside the rule above (the message names the graph, the limit and the rule), and for a call with more than
  *      2^25 connected k-subsets in all (the device budget; it also keeps every |S_g| within the reference's int).
  *      The library stays usable after any of them. */
 int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
@@ -305,6 +312,17 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
                                    ugs_job **job_out, int64_t *total_edges_out);
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device);
+/* Vertices per graph up to which ugs_uniform_* enumerates.  Default 64: every call behaves as it did before the wide form existed.
+ * A caller whose graphs are larger (PROTEINS, IMDB-BINARY) raises it, to 1024 at most, once at start-up; nothing raises it
+ * implicitly.  Results for graphs of at most 64 vertices never depend on it, and a call without wide graphs allocates and launches
+ * nothing more.  Process-wide, under a mutex; a call reads it once.  Outside 64 ... 1024: UGS_E_BAD_ARG, value kept.  previous
+ * may be NULL.  Initial value: UGS_UNIFORM_MAX_VERTICES in the environment, read at first use (invalid = ignored, reported under
+ * UGS_DEBUG=1). */
+int ugs_uniform_set_max_vertices(int n, int *previous);
+int ugs_uniform_max_vertices(void);
+/* Testing and measurement aid: graphs of up to this many vertices take the mask form (0 ... 64, default 64).  Below 64, smaller
+ * graphs whose k fits the wide rule go through the wide kernels instead and give the same tensors; with 0 every such graph does. */
+int ugs_uniform_set_mask_vertices(int n, int *previous);
 
 /* ---- rwr_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, p_restart): replaces the reference's
  *      src/samplers/rwr_sampler/src/rwr_sampler.cpp:73-296 (random walk with restart) run with ONE OpenMP thread, its only
@@ -344,7 +362,7 @@ int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_inde
  *      the graph's range are dropped, both modes.  sample_ptr = [0, m, 2m, ..., G m].
  *      A graph whose one-graph call would fail with UGS_E_UNSUPPORTED does not fail this call: its block is m rows of -1 without
  *      edges, it consumes no draws, and graph_status[g] != 0 (0 for every other graph).  Those graphs are, for uniform, one of
- *      more than 64 vertices and at least k of them, and one whose own |S_g| exceeds the 2^25 device budget; for rwr, one with
+ *      at least k vertices that ugs_uniform_sample_batch_begin refuses for its size (above), and one whose own |S_g| exceeds the 2^25 device budget; for rwr, one with
  *      n >= k and 10 n k > INT_MAX.  graph_status is a host array of num_graphs entries, written by begin.
  *      Errors of the call as a whole stay call errors: the argument errors and limits of ugs_*_sample_batch_begin (rwr: k > 64),
  *      and, for uniform, healthy graphs whose connected k-subsets TOGETHER exceed the budget (UGS_E_UNSUPPORTED; split the call).

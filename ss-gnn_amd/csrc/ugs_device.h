@@ -216,13 +216,14 @@ uint32_t ugs_chain_at_least(int64_t c, int *index_out);
 uint32_t ugs_chain_value(int idx);
 int64_t ugs_ord_words(int stages);
 
-// ---- uniform_sampler (ugs_uniform.hip): exact uniform connected k-subgraph sampling, graphs of at most 64 vertices ----
+// ---- uniform_sampler (ugs_uniform.hip): exact uniform connected k-subgraph sampling; graphs of at most 64 vertices as 64-bit
+//      masks, graphs of up to UGS_UNI_WIDE_MAX_N vertices (opt-in: ugs_uniform_set_max_vertices) as packed tuples ----
 #define UGS_UNI_BUDGET ((int64_t)1 << 25)    /* connected k-subsets (64-bit masks) one call may hold on the device */
 struct UgsUniGraph {
     int64_t lo;           // ptr[g]
     int64_t vbase;        // first entry of this graph in the enumerated vertices (adj, items >> 6)
     int32_t n;            // vertices
-    int32_t enumerable;   // 1 <= k <= n <= 64: its subsets are enumerated; otherwise S_g is empty
+    int32_t enumerable;   // 1: 1 <= k <= n <= 64, its subsets are enumerated as masks; 2: the wide form (UgsUniWide); 0: S_g is empty
 };
 struct UgsUniCall {
     int64_t G, E, nv, rows, budget;          // graphs, columns, enumerated vertices, G * m rows, mask budget
@@ -252,9 +253,25 @@ struct UgsUniCall {
     int64_t *status;                         // [4] running subset count, over-budget flag
     int64_t *nodes, *edge_ptr;               // outputs: [rows, k], [rows + 1]
 };
+// The wide graphs of a call (more than 64 vertices, or every graph the mask threshold sends here).  A set's sort key is its ascending
+// tuple packed big-endian in fields of b = bit length of n - 1 bits (k <= 8, k b <= 64): ascending keys = the reference's order, the
+// root is the first field.  The enumerated vertices of the mask graphs come first, [0, nv_mask), those of the wide graphs after them,
+// [nv_mask, nv); a wide root has 64 items as a mask root has: item j holds the sets whose first extension vertex is the root's
+// (j + 64 i)-th higher neighbour, so ioff[vi * 64] bounds the root bucket of either form.
+#define UGS_UNI_WIDE_MAX_N 1024
+#define UGS_UNI_WIDE_MAX_K 8
+struct UgsUniWide {
+    int64_t nv_mask;                         // enumerated vertices of the mask graphs (== nv: the call has no wide graph)
+    int64_t adj_words;                       // words of wadj
+    const int64_t *wbase;                    // [G] first word of graph g's bitmap in wadj; -1: not a wide graph
+    uint64_t *wadj;                          // per wide graph n rows of W = ceil(n / 64) words: the neighbours of each vertex (no self bits)
+    uint32_t *wpair;                         // [E] local endpoints u | v << 16 of a sorted column (wide graphs)
+    int64_t *gsize_mask;                     // [G] gsize with the wide graphs at 0: what the mask form's row kernel sees
+    uint64_t *rowkey;                        // [rows] key of a wide graph's row
+};
 size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget);
-hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s);
-hipError_t ugs_uniform_fill(const UgsUniCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
+hipError_t ugs_uniform_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 
 // ---- rwr_sampler (ugs_rwr.hip): random walk with restart, one SplitMix64 stream per graph, counter-based speculation ----
 #define UGS_RWR_KMAX 64

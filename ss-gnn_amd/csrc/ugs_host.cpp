@@ -2325,7 +2325,9 @@ struct ugs_job {
     // uniform_sampler path (ugs_uniform.hip): the call's device arrays in one pooled blob; finish runs uni_fill from them
     bool uni = false;
     PoolBuf uni_blob;
-    UgsUniCall uni_c{};    // rwr_sampler path (ugs_rwr.hip): the same, finish runs rwr_fill
+    UgsUniCall uni_c{};
+    UgsUniWide uni_w{};    // the call's wide graphs (none: nv_mask == nv)
+    // rwr_sampler path (ugs_rwr.hip): the same, finish runs rwr_fill
     bool rwr = false;
     PoolBuf rwr_blob;
     UgsRwrCall rwr_c{};
@@ -2463,7 +2465,7 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
             HIP_TRY(ugs_eps_launch(l, 1, j->dc.cus, s));
         } else if (tot > 0 && j->uni) {
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
-            HIP_TRY(ugs_uniform_fill(j->uni_c, d_ei, d_es, tot, s));
+            HIP_TRY(ugs_uniform_fill(j->uni_c, j->uni_w, d_ei, d_es, tot, s));
         } else if (tot > 0 && j->rwr) {
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
             HIP_TRY(ugs_rwr_fill(j->rwr_c, d_ei, d_es, tot, s));
@@ -2866,8 +2868,55 @@ int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_inde
 }
 
 // ---- uniform_sampler.sample_batch (reference src/samplers/uniform_sampler/src/uniform_sampler.cpp) ----
+// Vertices per graph up to which the sampler enumerates (64: masks only; above: the wide form) and up to which a graph takes the
+// mask form (testing aid).  Process-wide; a call reads both once.  First use takes UGS_UNIFORM_MAX_VERTICES from the environment.
+static std::mutex g_uni_limit_mu;
+static int g_uni_max_vertices = 64, g_uni_mask_vertices = 64;
+static void uniform_limits(int *max_vertices, int *mask_vertices) {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const char *e = std::getenv("UGS_UNIFORM_MAX_VERTICES");
+        if (!e || !*e) return;
+        char *end = nullptr;
+        const long long v = std::strtoll(e, &end, 10);
+        if (end && *end == 0 && v >= 64 && v <= UGS_UNI_WIDE_MAX_N) g_uni_max_vertices = (int)v;
+        else if (debug_on()) std::fprintf(stderr, "[UGS INFO] UGS_UNIFORM_MAX_VERTICES=%s ignored: must be 64 ... %d\n", e, UGS_UNI_WIDE_MAX_N);
+    });
+    std::lock_guard<std::mutex> lk(g_uni_limit_mu);
+    if (max_vertices) *max_vertices = g_uni_max_vertices;
+    if (mask_vertices) *mask_vertices = g_uni_mask_vertices;
+}
+
+int ugs_uniform_set_max_vertices(int n, int *previous) {
+    int cur = 0;
+    uniform_limits(&cur, nullptr);                                      // the environment's value first, so that it cannot overwrite this one later
+    if (n < 64 || n > UGS_UNI_WIDE_MAX_N)
+        return fail(UGS_E_BAD_ARG, "uniform_sampler vertex limit must be 64 ... " + std::to_string(UGS_UNI_WIDE_MAX_N) + " (got " + std::to_string(n) +
+                                       ", still " + std::to_string(cur) + ")");
+    std::lock_guard<std::mutex> lk(g_uni_limit_mu);
+    if (previous) *previous = g_uni_max_vertices;
+    g_uni_max_vertices = n;
+    return UGS_OK;
+}
+int ugs_uniform_max_vertices(void) {
+    int cur = 0;
+    uniform_limits(&cur, nullptr);
+    return cur;
+}
+int ugs_uniform_set_mask_vertices(int n, int *previous) {
+    int cur = 0;
+    uniform_limits(nullptr, &cur);
+    if (n < 0 || n > 64)
+        return fail(UGS_E_BAD_ARG, "uniform_sampler mask threshold must be 0 ... 64 (got " + std::to_string(n) + ", still " + std::to_string(cur) + ")");
+    std::lock_guard<std::mutex> lk(g_uni_limit_mu);
+    if (previous) *previous = g_uni_mask_vertices;
+    g_uni_mask_vertices = n;
+    return UGS_OK;
+}
+
 // seeds == nullptr: sample_batch, one generator for the call; otherwise sample_graphs: graph g draws from seeds[g], and a graph whose
-// one-graph call would be refused (more than 64 vertices, |S_g| past the budget) fails alone, graph_status[g] = 1.
+// one-graph call would be refused (more vertices than the limit in force or than its k allows, |S_g| past the budget) fails alone,
+// graph_status[g] = 1.
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
                          ugs_job **job_out, int64_t *total_edges_out) {
@@ -2879,21 +2928,44 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     if (k < 0) return fail(UGS_E_BAD_ARG, "k must be >= 0");
     if (num_cols >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^31 - 1");
     const int64_t G = num_graphs, E = num_cols;
+    int max_vertices = 64, mask_vertices = 64;                          // the limits in force for this call
+    uniform_limits(&max_vertices, &mask_vertices);
     std::vector<UgsUniGraph> gd((size_t)G);
     std::vector<int32_t> too_big(per_graph ? (size_t)G : 0, 0);
-    int64_t nv = 0;
+    int64_t nv = 0, nv_wide = 0, adj_words = 0;
     for (int64_t g = 0; g < G; ++g) {
         const int64_t n = ptr[g + 1] - ptr[g];
         if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
-        const bool over = k >= 1 && n >= k && n > 64;
-        if (over && !per_graph)
+        const bool wanted = k >= 1 && n >= k;
+        int b = 1;                                                      // field width of the wide key: bit length of n - 1
+        while (b < 62 && ((int64_t)1 << b) < n) ++b;
+        const bool key_fits = k <= UGS_UNI_WIDE_MAX_K && (int64_t)k * b <= 64;
+        const bool over = wanted && n > 64 && (n > max_vertices || !key_fits);
+        if (over && !per_graph) {
+            if (n > max_vertices)
+                return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
+                                               " vertices; graphs of more than " + std::to_string(max_vertices) +
+                                               " vertices (and at least k) are not supported");
             return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
-                                           " vertices; graphs of more than 64 vertices (and at least k) are not supported");
+                                           " vertices; a graph of more than 64 vertices (limit in force: " + std::to_string(max_vertices) +
+                                           ") needs k <= 8 and k * b <= 64, b = the bit length of n - 1 (here k = " + std::to_string(k) +
+                                           ", b = " + std::to_string(b) + ")");
+        }
         if (over) too_big[(size_t)g] = 1;                               // per-graph: m rows of -1, no draws
         UgsUniGraph &d = gd[(size_t)g];
-        d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = nv;
-        d.enumerable = k >= 1 && n >= k && !over ? 1 : 0;
-        if (d.enumerable) nv += n;
+        d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = 0;
+        d.enumerable = !wanted || over ? 0 : n > 64 || (n > mask_vertices && key_fits) ? 2 : 1;
+        if (d.enumerable == 1) { d.vbase = nv; nv += n; }
+        if (d.enumerable == 2) nv_wide += n;
+    }
+    // the enumerated vertices: the mask graphs' first, the wide graphs' after them
+    const int64_t nv_mask = nv;
+    std::vector<int64_t> wbase(nv_wide > 0 ? (size_t)G : 0, -1);
+    for (int64_t g = 0; nv_wide > 0 && g < G; ++g) {
+        UgsUniGraph &d = gd[(size_t)g];
+        if (d.enumerable != 2) continue;
+        d.vbase = nv; nv += d.n;
+        wbase[(size_t)g] = adj_words; adj_words += (int64_t)d.n * ((d.n + 63) / 64);
     }
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
@@ -2902,8 +2974,11 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
     const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
-                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), o_seeds = take(per_graph ? (size_t)G * 8 : 0),
-                 in_bytes = off;
+                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), o_seeds = take(per_graph ? (size_t)G * 8 : 0);
+    const bool wide = nv_wide > 0;                                      // a call without wide graphs allocates nothing for them
+    const size_t o_wb = wide ? take((size_t)G * 8) : 0, in_bytes = off;
+    const size_t o_wadj = wide ? take((size_t)adj_words * 8) : 0, o_wp = wide ? take((size_t)E * 4) : 0, o_gzm = wide ? take((size_t)G * 8) : 0,
+                 o_rk = wide ? take((size_t)rows * 8) : 0;
     const size_t o_gc = take(per_graph ? (size_t)G * 8 : 0);
     const size_t cub_bytes = ugs_uniform_cub_bytes(E, nv, budget);
     const size_t o_cub = take(cub_bytes), o_ck = take((size_t)E * 4), o_ck2 = take((size_t)E * 4), o_cv = take((size_t)E * 4),
@@ -2921,6 +2996,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
     if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsUniGraph));
     if (per_graph && G > 0) std::memcpy(host.data() + o_seeds, seeds, (size_t)G * 8);
+    if (wide) std::memcpy(host.data() + o_wb, wbase.data(), (size_t)G * 8);
     auto *vg = reinterpret_cast<int32_t *>(host.data() + o_vg);
     for (int64_t g = 0; g < G; ++g)
         if (gd[(size_t)g].enumerable) for (int32_t v = 0; v < gd[(size_t)g].n; ++v) vg[gd[(size_t)g].vbase + v] = (int32_t)g;
@@ -2951,8 +3027,15 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     c.draws = reinterpret_cast<int32_t *>(b + o_dr); c.rowmask = reinterpret_cast<uint64_t *>(b + o_rm);
     c.ecount = reinterpret_cast<uint32_t *>(b + o_ec); c.status = reinterpret_cast<int64_t *>(b + o_status);
     c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    UgsUniWide &w = j->uni_w;
+    w.nv_mask = nv_mask; w.adj_words = adj_words;
+    if (wide) {
+        w.wbase = reinterpret_cast<const int64_t *>(b + o_wb); w.wadj = reinterpret_cast<uint64_t *>(b + o_wadj);
+        w.wpair = reinterpret_cast<uint32_t *>(b + o_wp); w.gsize_mask = reinterpret_cast<int64_t *>(b + o_gzm);
+        w.rowkey = reinterpret_cast<uint64_t *>(b + o_rk);
+    }
     hipError_t e = hipMemcpyAsync(b, host.data(), in_bytes, hipMemcpyHostToDevice, dc.stream);
-    if (e == hipSuccess) e = ugs_uniform_begin(c, dc.stream);
+    if (e == hipSuccess) e = ugs_uniform_begin(c, w, dc.stream);
     if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
     int64_t status[4] = {0, 0, 0, 0};
     std::vector<int64_t> gcount(per_graph && nv > 0 ? (size_t)G : 0, 0);   // per-graph subset counts: read back once, with the total

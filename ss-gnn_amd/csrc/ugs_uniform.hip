@@ -19,6 +19,13 @@
 //   uni_draw_graphs             (per-graph seeds) the same, one workgroup and one generator per graph
 //   uni_rows + scan             rows (node ids) and per-row edge counts -> edge_ptr
 //   uni_fill (finish)           edge_index / edge_src
+//
+// Wide graphs (UgsUniWide: more than 64 vertices, up to the limit of ugs_uniform_set_max_vertices) keep every stage's place and
+// the shared ones (scan, sorts, sizes, draws) as they are; their keys are packed ascending tuples, which sort into the same order:
+//   uni_wadj                    bitmap of W = ceil(n / 64) words per vertex, local (u, v) per column in 16 + 16 bits
+//   uni_wesu<COUNT / WRITE>     the same search, one 16-lane group (a DPP row) per item, lane l holding word l of every set
+//   uni_wrows / uni_wfill       the tuple decoded from the key; the mask form's kernels see these graphs as empty
+// A call without wide graphs launches none of these.
 #include "ugs_device.h"
 
 #include <hipcub/hipcub.hpp>
@@ -61,7 +68,7 @@ __global__ void uni_adj(UgsUniCall c) {
     const uint32_t g = c.ckey2[p];
     if (g >= (uint32_t)c.G) return;
     const UgsUniGraph gd = c.graphs[g];
-    if (!gd.enumerable) return;
+    if (gd.enumerable != 1) return;                                 // wide graphs: uni_wadj
     const int64_t col = c.cval2[p];
     const int u = (int)(c.src[col] - gd.lo), v = (int)(c.dst[col] - gd.lo);
     c.bpair[p] = (uint16_t)(u | (v << 8));
@@ -385,6 +392,229 @@ __global__ void uni_fill(UgsUniCall c, int64_t *edge_index, int64_t *edge_src, i
     }
 }
 
+// ---- wide graphs: a vertex set is W <= 16 words, one per lane of a 16-lane group (one DPP row; four items per wave) ----
+constexpr int WIDE_LANES = 16;
+constexpr int WIDE_GROUPS = UNI_BLOCK / WIDE_LANES;
+
+__device__ __forceinline__ int field_bits(int n) { int b = 1; while (b < 16 && (1 << b) < n) ++b; return b; }   // bit length of n - 1, at least 1
+
+// inclusive sum over the lanes of a row at and below this one
+__device__ __forceinline__ uint32_t row_scan(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);   // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);   // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);   // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);   // row_shr:8
+    return x;
+}
+
+__global__ void uni_wadj(UgsUniCall c, UgsUniWide wd) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= c.E) return;
+    const uint32_t g = c.ckey2[p];
+    if (g >= (uint32_t)c.G) return;
+    const int64_t base = wd.wbase[g];
+    if (base < 0) return;
+    const UgsUniGraph gd = c.graphs[g];
+    const int64_t col = c.cval2[p];
+    const int u = (int)(c.src[col] - gd.lo), v = (int)(c.dst[col] - gd.lo);   // both inside [0, n): uni_colgraph checked the range
+    wd.wpair[p] = (uint32_t)u | ((uint32_t)v << 16);
+    if (u == v) return;
+    const int W = (gd.n + 63) >> 6;
+    atomicOr((unsigned long long *)&wd.wadj[base + (int64_t)u * W + (v >> 6)], 1ull << (v & 63));
+    atomicOr((unsigned long long *)&wd.wadj[base + (int64_t)v * W + (u >> 6)], 1ull << (u & 63));
+}
+
+// what one group carries through the search of its item
+struct WGroup {
+    const uint64_t *adj;          // the graph's bitmap rows
+    int W, l, gshift, b, k;       // words per row, this lane's word, first lane of the group in the wave, field width, set size
+    uint64_t abv;                 // this lane's word of the vertices above the root
+    uint64_t *out;                // WRITE: the item's next key
+    uint32_t cnt, flushed;        // COUNT: this lane's sets, and how many of them it has added to the running total
+    unsigned long long *ctr;      // the running total that bounds the work (the call's, or the graph's with per-graph seeds)
+    int64_t budget;
+    int64_t *status;              // the call's over-budget flag, nullptr with per-graph seeds
+    bool stop;                    // the running total is past the budget: leave (group-uniform)
+};
+
+__device__ __forceinline__ uint32_t group_ballot(const WGroup &x, bool p) { return (uint32_t)(__ballot(p) >> x.gshift) & 0xFFFFu; }
+
+// the lowest vertex of the set `ext` (one word per lane), removed from it; -1: the set is empty.  Group-uniform.
+__device__ __forceinline__ int group_take(const WGroup &x, uint64_t &ext) {
+    const uint32_t bits = group_ballot(x, ext != 0);
+    if (!bits) return -1;
+    const int l0 = __ffs(bits) - 1;
+    const int f = __shfl(__ffsll((unsigned long long)ext) - 1, l0, WIDE_LANES);
+    if (x.l == l0) ext &= ext - 1;
+    return l0 * 64 + f;
+}
+
+// the ascending tuple `key` of D fields with vertex w put in its place
+template <int D>
+__device__ __forceinline__ uint64_t key_with(uint64_t key, uint32_t w, int b) {
+    const uint64_t fm = (1ull << b) - 1;
+    int above = 0;                                                  // fields greater than w: the lowest ones
+#pragma unroll
+    for (int i = 0; i < D; ++i) above += (uint32_t)((key >> (i * b)) & fm) > w ? 1 : 0;
+    const int sh = above * b;                                       // <= D b <= 56
+    const uint64_t hi = key >> sh;
+    return (sh + b >= 64 ? 0ull : hi << (sh + b)) | ((uint64_t)w << sh) | (key & ((1ull << sh) - 1));
+}
+
+// the set has D = k - 1 vertices: every member of ext completes one
+template <int D, bool WRITE>
+__device__ __forceinline__ void wide_last(WGroup &x, uint64_t ext, uint64_t key) {
+    const uint32_t pc = (uint32_t)__popcll(ext);
+    if (WRITE) {
+        const uint32_t incl = row_scan(pc);
+        const uint32_t tot = (uint32_t)__shfl((int)incl, WIDE_LANES - 1, WIDE_LANES);
+        uint64_t *o = x.out + (incl - pc);
+        for (uint64_t e = ext; e; e &= e - 1) *o++ = key_with<D>(key, (uint32_t)(x.l * 64 + __ffsll((unsigned long long)e) - 1), x.b);
+        x.out += tot;
+    } else {
+        x.cnt += pc;
+        bool over = false;
+        if (x.cnt - x.flushed >= 4096 / WIDE_LANES) {               // the group flushes at least every 4096 sets
+            const unsigned long long add = x.cnt - x.flushed;
+            over = atomicAdd(x.ctr, add) + add > (unsigned long long)x.budget;
+            x.flushed = x.cnt;
+            if (over && x.status) x.status[1] = 1;
+        }
+        if (group_ballot(x, over)) x.stop = true;
+    }
+}
+
+// the set has D vertices (ascending in key), ext its extension set, nb its closed neighbourhood
+template <int D, bool WRITE>
+__device__ __forceinline__ void wide_level(WGroup &x, uint64_t ext, uint64_t nb, uint64_t key) {
+    if (D == x.k - 1) { wide_last<D, WRITE>(x, ext, key); return; }
+    if constexpr (D < UGS_UNI_WIDE_MAX_K - 1) {
+        while (!x.stop) {
+            const int w = group_take(x, ext);
+            if (w < 0) break;
+            const uint64_t aw = x.l < x.W ? x.adj[(int64_t)w * x.W + x.l] : 0ull;
+            wide_level<D + 1, WRITE>(x, ext | (aw & ~nb & x.abv), nb | aw, key_with<D>(key, (uint32_t)w, x.b));
+        }
+    }
+}
+
+// uni_esu for the items of the wide roots: item (root v, j) = the sets with minimum v whose first vertex taken from v's extension
+// set is its (j + 64 i)-th member, i = 0, 1, ...  Counts, offsets, budget and bounded work as in uni_esu.
+template <bool WRITE>
+__global__ __launch_bounds__(UNI_BLOCK) void uni_wesu(UgsUniCall c, UgsUniWide wd) {
+    const int64_t item = wd.nv_mask * 64 + (int64_t)blockIdx.x * WIDE_GROUPS + (threadIdx.x / WIDE_LANES);
+    if (item >= c.nv * 64) return;
+    if (WRITE && c.status[1]) return;
+    const int64_t vi = item >> 6;
+    const int slot = (int)(item & 63);
+    const int32_t gi = c.vgraph[vi];
+    if (WRITE && c.seeds && c.gcount[gi] > c.budget) return;
+    const UgsUniGraph gd = c.graphs[gi];
+    const int v = (int)(vi - gd.vbase), vw = v >> 6;
+    WGroup x;
+    x.adj = wd.wadj + wd.wbase[gi];
+    x.W = (gd.n + 63) >> 6; x.l = threadIdx.x & (WIDE_LANES - 1); x.gshift = threadIdx.x & 63 & ~(WIDE_LANES - 1);
+    x.b = field_bits(gd.n); x.k = c.k;
+    x.abv = x.l < vw ? 0ull : x.l == vw ? above_mask(v & 63) : ~0ull;
+    x.out = WRITE ? c.keys_a + c.ioff[item] : nullptr;
+    x.cnt = 0; x.flushed = 0;
+    x.ctr = (unsigned long long *)(c.seeds ? &c.gcount[gi] : &c.status[0]);
+    x.budget = c.budget; x.status = c.seeds ? nullptr : c.status; x.stop = false;
+    const uint64_t av = x.l < x.W ? x.adj[(int64_t)v * x.W + x.l] : 0ull;
+    const uint64_t ext1 = av & x.abv;
+    const uint64_t nb1 = av | (x.l == vw ? 1ull << (v & 63) : 0ull);
+    if (x.k == 1) {
+        if (slot == 0 && x.l == 0) { if (WRITE) x.out[0] = (uint64_t)v; else x.cnt = 1; }
+    } else if (x.k == 2) {
+        if (slot == 0) wide_last<1, WRITE>(x, ext1, (uint64_t)v);
+    } else {
+        const uint32_t pc = (uint32_t)__popcll(ext1), incl = row_scan(pc), excl = incl - pc;
+        const uint32_t deg = (uint32_t)__shfl((int)incl, WIDE_LANES - 1, WIDE_LANES);
+        for (uint32_t r = (uint32_t)slot; r < deg && !x.stop; r += 64) {
+            const bool holds = excl <= r && r < incl;               // this lane's word holds the r-th member
+            int f = 0;
+            if (holds) {
+                uint64_t t = ext1;
+                for (uint32_t i = r - excl; i > 0; --i) t &= t - 1;
+                f = __ffsll((unsigned long long)t) - 1;
+            }
+            const int l0 = __ffs(group_ballot(x, holds)) - 1;
+            f = __shfl(f, l0, WIDE_LANES);
+            const int w = l0 * 64 + f;
+            const uint64_t aw = x.l < x.W ? x.adj[(int64_t)w * x.W + x.l] : 0ull;
+            const uint64_t later = x.l < l0 ? 0ull : x.l == l0 ? above_mask(f) : ~0ull;   // the members of ext1 after w
+            wide_level<2, WRITE>(x, (ext1 & later) | (aw & ~nb1 & x.abv), nb1 | aw, ((uint64_t)v << x.b) | (uint64_t)w);
+        }
+    }
+    if (!WRITE) {
+        const uint32_t tot = row_scan(x.cnt), rest = row_scan(x.cnt - x.flushed);
+        if (x.l == WIDE_LANES - 1) {
+            c.icount[item] = tot;
+            if (rest) {
+                const unsigned long long now = atomicAdd(x.ctr, (unsigned long long)rest) + rest;
+                if (now > (unsigned long long)c.budget && !c.seeds) c.status[1] = 1;
+            }
+        }
+    }
+}
+
+// what uni_rows sees: the wide graphs hold nothing (it writes their rows as -1, uni_wrows writes them again)
+__global__ void uni_wsizes(UgsUniCall c, UgsUniWide wd) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= c.G) return;
+    wd.gsize_mask[g] = wd.wbase[g] >= 0 ? 0 : c.gsize[g];
+}
+
+// position of local vertex u in the tuple `key` of k fields; -1: not a member
+__device__ __forceinline__ int tuple_pos(uint64_t key, int k, int b, uint32_t u) {
+    const uint64_t fm = (1ull << b) - 1;
+    for (int j = 0; j < k; ++j) if ((uint32_t)((key >> (b * (k - 1 - j))) & fm) == u) return j;
+    return -1;
+}
+
+__device__ __forceinline__ bool wide_row_valid(const UgsUniCall &c, int64_t g) { return !c.status[1] && c.gsize[g] > 0; }
+
+// uni_rows for the rows of the wide graphs (a row is valid by its graph, not by its key: {0} at k = 1 has key 0)
+__global__ void uni_wrows(UgsUniCall c, UgsUniWide wd) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = row / c.m, s = row - g * c.m;
+    if (wd.wbase[g] < 0 || !wide_row_valid(c, g)) return;           // uni_rows has written the row of -1
+    const UgsUniGraph gd = c.graphs[g];
+    const int k = c.k, b = field_bits(gd.n);
+    const int64_t d = c.seeds ? row : (int64_t)c.nepos[g] * c.m + s;
+    const uint64_t key = c.keys_sorted[c.gstart[g] + c.draws[d]];
+    wd.rowkey[row] = key;
+    int64_t *out = c.nodes + row * k;
+    for (int j = 0; j < k; ++j) out[j] = gd.lo + (int64_t)((key >> (b * (k - 1 - j))) & ((1ull << b) - 1));
+    uint32_t cnt = 0;
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = wd.wpair[p];
+        cnt += tuple_pos(key, k, b, uv & 0xFFFFu) >= 0 && tuple_pos(key, k, b, uv >> 16) >= 0 ? 1u : 0u;
+    }
+    c.ecount[row] = cnt;
+}
+
+__global__ void uni_wfill(UgsUniCall c, UgsUniWide wd, int64_t *edge_index, int64_t *edge_src, int64_t ld) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = row / c.m;
+    if (wd.wbase[g] < 0 || !wide_row_valid(c, g)) return;
+    const UgsUniGraph gd = c.graphs[g];
+    const int k = c.k, b = field_bits(gd.n);
+    const uint64_t key = wd.rowkey[row];
+    int64_t w = c.edge_ptr[row];
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = wd.wpair[p];
+        const int pu = tuple_pos(key, k, b, uv & 0xFFFFu), pv = tuple_pos(key, k, b, uv >> 16);
+        if (pu < 0 || pv < 0) continue;
+        edge_index[w] = c.mode == 0 ? pu : gd.lo + (int64_t)(uv & 0xFFFFu);
+        edge_index[ld + w] = c.mode == 0 ? pv : gd.lo + (int64_t)(uv >> 16);
+        edge_src[w] = c.cval2[p];
+        ++w;
+    }
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace
@@ -401,7 +631,11 @@ size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget) {
     return a > b ? a : b;
 }
 
-hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s) {
+hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) {
+    const int64_t nv_wide = c.nv - w.nv_mask;                                  // 0: the call runs the mask form's launches only
+    UgsUniCall cm = c;                                                         // the mask form's view: its own roots, its own graphs' sizes
+    cm.nv = w.nv_mask;
+    if (nv_wide > 0) cm.gsize = w.gsize_mask;
     hipError_t e = hipMemsetAsync(c.status, 0, 4 * sizeof(int64_t), s);
     if (e != hipSuccess) return e;
     int bits = 1;
@@ -417,15 +651,25 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s) {
     if (c.nv > 0) {
         if ((e = hipMemsetAsync(c.adj, 0, (size_t)c.nv * sizeof(uint64_t), s)) != hipSuccess) return e;
         if (c.E > 0) hipLaunchKernelGGL(uni_adj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
-        const int64_t items = c.nv * 64;
+        if (nv_wide > 0) {
+            if ((e = hipMemsetAsync(w.wadj, 0, (size_t)w.adj_words * sizeof(uint64_t), s)) != hipSuccess) return e;
+            if (c.E > 0) hipLaunchKernelGGL(uni_wadj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
+        }
+        const int64_t items = c.nv * 64, mitems = cm.nv * 64, witems = nv_wide * 64;
         if (c.seeds && (e = hipMemsetAsync(c.gcount, 0, (size_t)c.G * sizeof(int64_t), s)) != hipSuccess) return e;
-        if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, false>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
-        else hipLaunchKernelGGL((uni_esu<64, false>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        if (mitems > 0) {
+            if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
+            else hipLaunchKernelGGL((uni_esu<64, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
+        }
+        if (witems > 0) hipLaunchKernelGGL((uni_wesu<false>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), 0, s, c, w);
         if (c.seeds) hipLaunchKernelGGL(uni_cap, dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         if ((e = ugs_launch_scan(c.icount, items, c.ioff, c.scan_tmp, s)) != hipSuccess) return e;
         if (c.seeds) hipLaunchKernelGGL(uni_joint, dim3(1), dim3(64), 0, s, c);
-        if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, true>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
-        else hipLaunchKernelGGL((uni_esu<64, true>), dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        if (mitems > 0) {
+            if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, true>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
+            else hipLaunchKernelGGL((uni_esu<64, true>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
+        }
+        if (witems > 0) hipLaunchKernelGGL((uni_wesu<true>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), 0, s, c, w);
         // root buckets larger than LDS: rocPRIM's segmented radix sort (the others are empty segments there)
         hipLaunchKernelGGL(uni_segments, dim3(blocks(c.nv, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         hipcub::DoubleBuffer<uint64_t> keys(c.keys_a, c.keys_b);
@@ -437,16 +681,20 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, hipStream_t s) {
     }
     if (c.G > 0) {
         hipLaunchKernelGGL(uni_graph_sizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        if (nv_wide > 0) hipLaunchKernelGGL(uni_wsizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
         if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
         else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
     }
-    if (c.rows > 0) hipLaunchKernelGGL(uni_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+    cm.keys_sorted = c.keys_sorted;
+    if (c.rows > 0) hipLaunchKernelGGL(uni_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
+    if (c.rows > 0 && nv_wide > 0) hipLaunchKernelGGL(uni_wrows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ugs_launch_scan(c.ecount, c.rows, c.edge_ptr, c.scan_tmp, s);
 }
 
-hipError_t ugs_uniform_fill(const UgsUniCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {
+hipError_t ugs_uniform_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {
     if (c.rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(uni_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, edge_index, edge_src, ld);
+    if (c.nv > w.nv_mask) hipLaunchKernelGGL(uni_wfill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w, edge_index, edge_src, ld);
     return hipGetLastError();
 }

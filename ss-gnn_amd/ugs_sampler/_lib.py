@@ -58,6 +58,8 @@ def _load():
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
         "ugs_set_batch_pass_max_cols": [C.c_int64, i64p],
+        "ugs_uniform_set_max_vertices": [C.c_int, C.POINTER(C.c_int)],
+        "ugs_uniform_set_mask_vertices": [C.c_int, C.POINTER(C.c_int)],
         "ugs_plan_create_batch": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.POINTER(vp)],
         "ugs_plan_create_handle": [C.c_int64, C.POINTER(vp)],
         "ugs_plan_release": [vp],
@@ -83,7 +85,9 @@ def _load():
         fn.restype = C.c_int
     L.ugs_batch_pass_max_cols.argtypes = []
     L.ugs_batch_pass_max_cols.restype = C.c_int64
-    return L, sorted(list(sig) + ["ugs_last_error", "ugs_version", "ugs_batch_pass_max_cols"])
+    L.ugs_uniform_max_vertices.argtypes = []
+    L.ugs_uniform_max_vertices.restype = C.c_int
+    return L, sorted(list(sig) + ["ugs_last_error", "ugs_version", "ugs_batch_pass_max_cols", "ugs_uniform_max_vertices"])
 
 
 lib, EXPORTS = _load()
