@@ -395,6 +395,36 @@ int ugs_apx_gpu_sample_batch(const int64_t *edge_index, int64_t row_stride, int6
                              int m_per_graph, int k, uint64_t seed, double epsilon, int64_t *samples_out, int64_t *num_samples_out,
                              int32_t *order_pos_out, double *est_out, int64_t order_capacity);
 
+/* ---- ugs_sampler.wl: Weisfeiler-Lehman graph hashes and vocabulary ids of sampled subgraphs (ugs_wl.hip) -- replaces the host loop
+ *      of the reference's SS-GNN-WL consumer (src/gps/gps/models/ss_gnn_wl.py:210-247, src/gps/gps/utils/wl_vocab.py:21-67), which
+ *      builds one networkx.Graph per sample, gives every vertex the attribute str(degree) and calls
+ *      weisfeiler_lehman_graph_hash(G, node_attr='attr', iterations).  The digests are those of networkx 3.4.2, bit for bit.
+ *      The law, for row i of nodes [rows, k] (any values) with the entries [edge_ptr[i], edge_ptr[i+1]) of edge_index:
+ *        1. n = number of entries >= 0 in the row; the graph has the vertices 0 .. n-1;
+ *        2. every entry e contributes the undirected edge {edge_index[0,e], edge_index[1,e]}: duplicates and reversed copies collapse,
+ *           a loop (u,u) makes u its own neighbour once and counts 2 towards its degree (networkx.Graph);
+ *        3. n = 0: status 1, no digest (the reference answers "unknown id" for such a row);
+ *        4. an endpoint outside [0, n), or an edge_ptr range that is no range of [0, num_cols]: status 2, no digest.  THE ONE
+ *           DEVIATION: the reference catches the KeyError networkx raises there and hashes a fallback string
+ *           "deg_<sum>_edges_<count>"; no sampler of this library produces such a row in mode "sample";
+ *        5. otherwise status 0 and: label[u] = str(deg u) in decimal; for t = 1 .. iterations:
+ *           msg[u] = label[u] + "".join(sorted(label[v] for v in N(u))) -- Python STRING order, "10" < "2" --,
+ *           label'[u] = blake2b(msg[u], digest_size=16).hexdigest() (unkeyed BLAKE2b, RFC 7693; 32 lowercase hex characters), and
+ *           sorted(Counter(label').items()) is appended to a list `items`; the result is
+ *           blake2b(str(tuple(items)), digest_size=16): items print as ('<32 hex>', <count>), joined by ", " inside one pair of
+ *           parentheses, a single item gets a trailing comma "(('..', 2),)", iterations = 0 hashes "()".
+ *      digest [rows, 2] uint64: bytes 0-7 and 8-15 of the digest as big-endian numbers (the hex string is "%016x%016x" of the two),
+ *      zero where status != 0; status [rows] int32.  All pointers are DEVICE pointers.  1 <= k <= 32, 0 <= iterations <= 8, otherwise
+ *      UGS_E_UNSUPPORTED.  Node-feature labels (the reference's use_node_features_in_wl: md5 of feature bytes) are not covered.
+ *      One launch on the calling thread's stream (ugs_set_stream), no allocation, no synchronisation with the host. */
+int ugs_wl_hash(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, uint64_t *d_digest, int32_t *d_status);
+/* Vocabulary ids of digests (hash_to_id, wl_vocab.py:205-216): d_keys [vocab_size, 2] holds the vocabulary's digests in the form
+ * above, ascending as 128-bit numbers and distinct, d_ids [vocab_size] their ids.  ids_out[i] = the id of digest i, or unknown_id
+ * when it is not in the table or status[i] != 0.  Same stream rule; one launch, no allocation, no synchronisation. */
+int ugs_wl_lookup(const uint64_t *d_digest, const int32_t *d_status, int64_t rows, const uint64_t *d_keys, const int64_t *d_ids,
+                  int64_t vocab_size, int64_t unknown_id, int64_t *d_ids_out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */
