@@ -415,10 +415,31 @@ int ugs_apx_gpu_sample_batch(const int64_t *edge_index, int64_t row_stride, int6
  *           parentheses, a single item gets a trailing comma "(('..', 2),)", iterations = 0 hashes "()".
  *      digest [rows, 2] uint64: bytes 0-7 and 8-15 of the digest as big-endian numbers (the hex string is "%016x%016x" of the two),
  *      zero where status != 0; status [rows] int32.  All pointers are DEVICE pointers.  1 <= k <= 32, 0 <= iterations <= 8, otherwise
- *      UGS_E_UNSUPPORTED.  Node-feature labels (the reference's use_node_features_in_wl: md5 of feature bytes) are not covered.
+ *      UGS_E_UNSUPPORTED.  This is the degree-labelled form (use_node_features_in_wl = false); ugs_wl_hash_labeled below is the
+ *      node-feature form.  Edge attributes and weisfeiler_lehman_subgraph_hashes are not covered.
  *      One launch on the calling thread's stream (ugs_set_stream), no allocation, no synchronisation with the host. */
 int ugs_wl_hash(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
                 const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, uint64_t *d_digest, int32_t *d_status);
+/* The node-feature form (use_node_features_in_wl = true; compute_wl_hash with node_features, wl_vocab.py:21-67, on the rows
+ * extract_subgraph_from_batch cuts out, wl_vocab.py:70-107).  The law of ugs_wl_hash holds except for the start labels:
+ *   a. label32(i) = the first four bytes of MD5(bytes of feature row i) (RFC 1321) as a big-endian number, i.e.
+ *      int(hashlib.md5(x[i].numpy().tobytes()).hexdigest()[:8], 16); a row of zero bytes gives 0xd41d8cd9.  ugs_wl_feature_labels
+ *      writes it, as int64, for num_rows rows of row_bytes bytes each, row i starting at d_x + i * row_stride_bytes (any byte
+ *      alignment).  0 <= row_bytes < 2^29 (otherwise UGS_E_UNSUPPORTED), row_stride_bytes >= row_bytes, num_rows >= 0.
+ *   b. the vertices of a row of nodes are its entries >= 0 in row order: vertex j is the j-th such entry, so an entry of -1 in the
+ *      middle shifts the later vertices down (subgraph_nodes[valid_mask]); a duplicated id is two vertices with one label.  The
+ *      start label of vertex j is "%08x" % d_labels[nodes[row, slot_j]]: 8 lowercase hex characters, whose string order is the
+ *      numeric order of the 32-bit values.  From there on: msg[u] = label[u] + sorted neighbour labels, BLAKE2b-128 hex, Counter
+ *      items, final string, as in 5. above.  There is no degree in this form: a loop only makes u its own neighbour.
+ *      iterations = 0 still hashes "()".
+ *   c. statuses 0, 1 and 2 as in ugs_wl_hash (a row with a bad endpoint is 2 whatever its labels); status 3, no digest: an entry
+ *      >= num_labels, or a label outside [0, 2^32) -- the reference raises IndexError for the former.  Other rows are not disturbed.
+ * d_labels [num_labels] int64 need not come from ugs_wl_feature_labels: any 32-bit categorical labels do.  All pointers are DEVICE
+ * pointers; each function makes one launch on the calling thread's stream, allocates nothing and does not synchronise with the host. */
+int ugs_wl_feature_labels(const void *d_x, int64_t row_bytes, int64_t row_stride_bytes, int64_t num_rows, int64_t *d_labels);
+int ugs_wl_hash_labeled(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                        const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, const int64_t *d_labels, int64_t num_labels,
+                        uint64_t *d_digest, int32_t *d_status);
 /* Vocabulary ids of digests (hash_to_id, wl_vocab.py:205-216): d_keys [vocab_size, 2] holds the vocabulary's digests in the form
  * above, ascending as 128-bit numbers and distinct, d_ids [vocab_size] their ids.  ids_out[i] = the id of digest i, or unknown_id
  * when it is not in the table or status[i] != 0.  Same stream rule; one launch, no allocation, no synchronisation. */

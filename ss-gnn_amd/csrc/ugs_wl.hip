@@ -1,14 +1,19 @@
 // ugs_wl.hip -- Weisfeiler-Lehman graph hashes and vocabulary ids of sampled subgraphs, on the device.
 // Replaces the host loop of the reference's SS-GNN-WL consumer (src/gps/gps/models/ss_gnn_wl.py:210-247 with
 // src/gps/gps/utils/wl_vocab.py:21-67): per sample one networkx.weisfeiler_lehman_graph_hash(G, node_attr='attr', iterations)
-// with the degree as attribute, and a dict lookup.  The law is stated at ugs_wl_hash in include/ugs_mi355.h; the digests are
-// networkx 3.4.2's, bit for bit.
+// with the degree as attribute -- or, with node features, the first 8 hex characters of the md5 of the vertex's feature row -- and
+// a dict lookup.  The law is stated at ugs_wl_hash and ugs_wl_hash_labeled in include/ugs_mi355.h; the digests are networkx
+// 3.4.2's, bit for bit.
 //
+// ugs_wl_feature_labels_kernel: one lane per feature row, MD5 (RFC 1321) of its bytes; the label is the digest's first four bytes.
 // ugs_wl_hash_kernel: one lane group (8, 16 or 32 lanes, by k) per sample, one lane per vertex; groups never span a wave.
 //   edges   the group's lanes stride over the row's edge entries and OR them into one 32-bit neighbour mask per vertex in LDS:
 //           range check, deduplication, reversed copies and loops at once;
 //   labels  128-bit, two uint64 compared big-endian, double-buffered in LDS.  The start labels are the degrees' decimal strings
-//           packed into the top bytes of the high word, so that the same comparison gives Python's string order ("10" < "2");
+//           packed into the top bytes of the high word, so that the same comparison gives Python's string order ("10" < "2").
+//           Label mode (a launch argument, the same code): the j-th valid slot of the row is vertex j (prefix popcount of the
+//           group's ballot) and puts labels[id] into the top 32 bits of the high word; its first message takes it as one piece of
+//           8 hex characters; an id or label out of range raises the group's flag: status 3;
 //   order   once per iteration every lane ranks its label among the group's (ties by vertex): order[rank] = vertex.  A vertex
 //           walks that list and keeps its neighbours -- its sorted neighbour labels -- and the run heads of the same list are the
 //           iteration's Counter items;
@@ -143,6 +148,96 @@ __device__ __forceinline__ unsigned hex_word(u64 hi, u64 lo, int p) {      // 32
     return (unsigned)((p & 1) ? w : (w >> 32));
 }
 
+// ---- MD5 (RFC 1321) of feature rows: the start labels of the node-feature form ----
+__device__ __forceinline__ unsigned rotl32(unsigned x, int r) { return (x << r) | (x >> (32 - r)); }
+
+#define MD5_F(b, c, d) ((d) ^ ((b) & ((c) ^ (d))))
+#define MD5_G(b, c, d) ((c) ^ ((d) & ((b) ^ (c))))
+#define MD5_H(b, c, d) ((b) ^ (c) ^ (d))
+#define MD5_I(b, c, d) ((c) ^ ((b) | ~(d)))
+#define MD5_STEP(f, a, b, c, d, x, t, s) a += f(b, c, d) + (x) + (t); a = rotl32(a, s) + b;
+
+// one 64-byte block, m[j] = its bytes 4j .. 4j+3 little-endian; the four rounds written out with the constants as literals
+__device__ __forceinline__ void md5_block(unsigned (&h)[4], const unsigned (&m)[16]) {
+    unsigned a = h[0], b = h[1], c = h[2], d = h[3];
+    MD5_STEP(MD5_F, a, b, c, d, m[0], 0xd76aa478u, 7) MD5_STEP(MD5_F, d, a, b, c, m[1], 0xe8c7b756u, 12)
+    MD5_STEP(MD5_F, c, d, a, b, m[2], 0x242070dbu, 17) MD5_STEP(MD5_F, b, c, d, a, m[3], 0xc1bdceeeu, 22)
+    MD5_STEP(MD5_F, a, b, c, d, m[4], 0xf57c0fafu, 7) MD5_STEP(MD5_F, d, a, b, c, m[5], 0x4787c62au, 12)
+    MD5_STEP(MD5_F, c, d, a, b, m[6], 0xa8304613u, 17) MD5_STEP(MD5_F, b, c, d, a, m[7], 0xfd469501u, 22)
+    MD5_STEP(MD5_F, a, b, c, d, m[8], 0x698098d8u, 7) MD5_STEP(MD5_F, d, a, b, c, m[9], 0x8b44f7afu, 12)
+    MD5_STEP(MD5_F, c, d, a, b, m[10], 0xffff5bb1u, 17) MD5_STEP(MD5_F, b, c, d, a, m[11], 0x895cd7beu, 22)
+    MD5_STEP(MD5_F, a, b, c, d, m[12], 0x6b901122u, 7) MD5_STEP(MD5_F, d, a, b, c, m[13], 0xfd987193u, 12)
+    MD5_STEP(MD5_F, c, d, a, b, m[14], 0xa679438eu, 17) MD5_STEP(MD5_F, b, c, d, a, m[15], 0x49b40821u, 22)
+    MD5_STEP(MD5_G, a, b, c, d, m[1], 0xf61e2562u, 5) MD5_STEP(MD5_G, d, a, b, c, m[6], 0xc040b340u, 9)
+    MD5_STEP(MD5_G, c, d, a, b, m[11], 0x265e5a51u, 14) MD5_STEP(MD5_G, b, c, d, a, m[0], 0xe9b6c7aau, 20)
+    MD5_STEP(MD5_G, a, b, c, d, m[5], 0xd62f105du, 5) MD5_STEP(MD5_G, d, a, b, c, m[10], 0x02441453u, 9)
+    MD5_STEP(MD5_G, c, d, a, b, m[15], 0xd8a1e681u, 14) MD5_STEP(MD5_G, b, c, d, a, m[4], 0xe7d3fbc8u, 20)
+    MD5_STEP(MD5_G, a, b, c, d, m[9], 0x21e1cde6u, 5) MD5_STEP(MD5_G, d, a, b, c, m[14], 0xc33707d6u, 9)
+    MD5_STEP(MD5_G, c, d, a, b, m[3], 0xf4d50d87u, 14) MD5_STEP(MD5_G, b, c, d, a, m[8], 0x455a14edu, 20)
+    MD5_STEP(MD5_G, a, b, c, d, m[13], 0xa9e3e905u, 5) MD5_STEP(MD5_G, d, a, b, c, m[2], 0xfcefa3f8u, 9)
+    MD5_STEP(MD5_G, c, d, a, b, m[7], 0x676f02d9u, 14) MD5_STEP(MD5_G, b, c, d, a, m[12], 0x8d2a4c8au, 20)
+    MD5_STEP(MD5_H, a, b, c, d, m[5], 0xfffa3942u, 4) MD5_STEP(MD5_H, d, a, b, c, m[8], 0x8771f681u, 11)
+    MD5_STEP(MD5_H, c, d, a, b, m[11], 0x6d9d6122u, 16) MD5_STEP(MD5_H, b, c, d, a, m[14], 0xfde5380cu, 23)
+    MD5_STEP(MD5_H, a, b, c, d, m[1], 0xa4beea44u, 4) MD5_STEP(MD5_H, d, a, b, c, m[4], 0x4bdecfa9u, 11)
+    MD5_STEP(MD5_H, c, d, a, b, m[7], 0xf6bb4b60u, 16) MD5_STEP(MD5_H, b, c, d, a, m[10], 0xbebfbc70u, 23)
+    MD5_STEP(MD5_H, a, b, c, d, m[13], 0x289b7ec6u, 4) MD5_STEP(MD5_H, d, a, b, c, m[0], 0xeaa127fau, 11)
+    MD5_STEP(MD5_H, c, d, a, b, m[3], 0xd4ef3085u, 16) MD5_STEP(MD5_H, b, c, d, a, m[6], 0x04881d05u, 23)
+    MD5_STEP(MD5_H, a, b, c, d, m[9], 0xd9d4d039u, 4) MD5_STEP(MD5_H, d, a, b, c, m[12], 0xe6db99e5u, 11)
+    MD5_STEP(MD5_H, c, d, a, b, m[15], 0x1fa27cf8u, 16) MD5_STEP(MD5_H, b, c, d, a, m[2], 0xc4ac5665u, 23)
+    MD5_STEP(MD5_I, a, b, c, d, m[0], 0xf4292244u, 6) MD5_STEP(MD5_I, d, a, b, c, m[7], 0x432aff97u, 10)
+    MD5_STEP(MD5_I, c, d, a, b, m[14], 0xab9423a7u, 15) MD5_STEP(MD5_I, b, c, d, a, m[5], 0xfc93a039u, 21)
+    MD5_STEP(MD5_I, a, b, c, d, m[12], 0x655b59c3u, 6) MD5_STEP(MD5_I, d, a, b, c, m[3], 0x8f0ccc92u, 10)
+    MD5_STEP(MD5_I, c, d, a, b, m[10], 0xffeff47du, 15) MD5_STEP(MD5_I, b, c, d, a, m[1], 0x85845dd1u, 21)
+    MD5_STEP(MD5_I, a, b, c, d, m[8], 0x6fa87e4fu, 6) MD5_STEP(MD5_I, d, a, b, c, m[15], 0xfe2ce6e0u, 10)
+    MD5_STEP(MD5_I, c, d, a, b, m[6], 0xa3014314u, 15) MD5_STEP(MD5_I, b, c, d, a, m[13], 0x4e0811a1u, 21)
+    MD5_STEP(MD5_I, a, b, c, d, m[4], 0xf7537e82u, 6) MD5_STEP(MD5_I, d, a, b, c, m[11], 0xbd3af235u, 10)
+    MD5_STEP(MD5_I, c, d, a, b, m[2], 0x2ad7d2bbu, 15) MD5_STEP(MD5_I, b, c, d, a, m[9], 0xeb86d391u, 21)
+    h[0] += a; h[1] += b; h[2] += c; h[3] += d;
+}
+
+struct WlLabelArgs {
+    const unsigned char *x;      // row i at x + i * stride, `len` bytes
+    int64_t stride, rows;
+    unsigned len;                // < 2^29: the bit length fits 32 bits
+    int64_t *labels;             // [rows]
+};
+
+// One lane per row.  A row that starts on a 4-byte boundary is read in whole words, any other one byte by byte; the last partial
+// word, the 0x80 byte, the zero padding and the bit length are put together per word, so m[16] keeps static indices (0 bytes of
+// scratch) and nothing past the row's last byte is read.
+__global__ __launch_bounds__(256) void ugs_wl_feature_labels_kernel(WlLabelArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.rows) return;
+    const unsigned char *p = a.x + i * a.stride;
+    const bool aligned = (reinterpret_cast<uintptr_t>(p) & 3u) == 0u;
+    const unsigned len = a.len;
+    const unsigned nblk = (len + 72u) >> 6;                // len + 0x80 + 8 length bytes, rounded up to blocks
+    unsigned h[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
+    for (unsigned blk = 0; blk < nblk; ++blk) {
+        unsigned m[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned o = (blk << 6) + 4u * j;
+            unsigned w = 0;
+            if (o + 4u <= len) {
+                if (aligned) w = *reinterpret_cast<const unsigned *>(p + o);
+                else w = (unsigned)p[o] | ((unsigned)p[o + 1] << 8) | ((unsigned)p[o + 2] << 16) | ((unsigned)p[o + 3] << 24);
+            } else if (o <= len) {                         // the row's last bytes and the 0x80 behind them
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const unsigned at = o + q;
+                    const unsigned byte = at < len ? (unsigned)p[at] : at == len ? 0x80u : 0u;
+                    w |= byte << (8 * q);
+                }
+            }
+            m[j] = w;
+        }
+        if (blk == nblk - 1u) m[14] = len << 3;            // bit length, low word; the high word stays zero
+        md5_block(h, m);
+    }
+    a.labels[i] = (int64_t)__builtin_bswap32(h[0]);        // digest bytes 0-3 as a big-endian number: int(hexdigest()[:8], 16)
+}
+
 struct WlHashArgs {
     const int64_t *nodes;        // [rows, k]
     const int64_t *edge_index;   // [2, num_cols], row stride `stride`
@@ -152,6 +247,9 @@ struct WlHashArgs {
     int k, iterations, wshift;   // lanes per group = 1 << wshift
     u64 *digest;                 // [rows, 2]
     int32_t *status;             // [rows]
+    const int64_t *labels;       // [num_labels]: start labels by vertex id (label mode), values in [0, 2^32)
+    int64_t num_labels;
+    int labeled;                 // 0: the start labels are the degrees; 1: labels[nodes[row, slot]]
 };
 
 __global__ __launch_bounds__(UGS_WL_BLOCK) void ugs_wl_hash_kernel(WlHashArgs a) {
@@ -172,9 +270,12 @@ __global__ __launch_bounds__(UGS_WL_BLOCK) void ugs_wl_hash_kernel(WlHashArgs a)
     const int T = a.iterations;
 
     // ---- vertices and neighbour masks ----
-    const bool valid = row_ok && u < a.k && a.nodes[row * a.k + u] >= 0;
+    const int64_t id = row_ok && u < a.k ? a.nodes[row * a.k + u] : -1;
+    const bool valid = id >= 0;
+    const u64 gmask = W == 32 ? 0xffffffffull : ((1ull << W) - 1ull);
+    const int gshift = (tid & 63) - u;                 // the group's first lane inside the wave
     const u64 ballot = __ballot(valid);
-    const int n = __popcll((ballot >> ((tid & 63) - u)) & (W == 32 ? 0xffffffffull : ((1ull << W) - 1ull)));
+    const int n = __popcll((ballot >> gshift) & gmask);
     mask_sh[tid] = 0;
     if (u == 0) bad_sh[g] = 0;
     __syncthreads();
@@ -194,13 +295,28 @@ __global__ __launch_bounds__(UGS_WL_BLOCK) void ugs_wl_hash_kernel(WlHashArgs a)
             }
         }
     }
+    // ---- label mode: the j-th valid slot of the row is vertex j and brings labels[id] as the top 32 bits of the high word ----
+    bool norange = false;
+    if (a.labeled) {
+        bool out = false;
+        if (valid) {
+            const int64_t l = id < a.num_labels ? a.labels[id] : -1;
+            out = (u64)l > 0xffffffffull;              // an id past the label rows, or a label outside [0, 2^32)
+            if (!out) {
+                const int j = __popcll((ballot >> gshift) & ((1ull << u) - 1ull));
+                lab_sh[0][base + j][0] = (u64)l << 32;
+                lab_sh[0][base + j][1] = 0;
+            }
+        }
+        norange = ((__ballot(out) >> gshift) & gmask) != 0ull;
+    }
     __syncthreads();
-    const int st = !row_ok ? -1 : n == 0 ? 1 : bad_sh[g] ? 2 : 0;
+    const int st = !row_ok ? -1 : n == 0 ? 1 : bad_sh[g] ? 2 : norange ? 3 : 0;
     const bool live = st == 0 && u < n;                // this lane hashes a vertex
     const unsigned mymask = live ? mask_sh[tid] : 0u;
 
     // ---- start labels: str(degree), a loop counting twice ----
-    if (live) {
+    if (live && !a.labeled) {
         unsigned len;
         const u64 d = dec2((unsigned)__popc(mymask) + ((mymask >> u) & 1u), &len);
         lab_sh[0][tid][0] = ((d & 0xffull) << 56) | ((d >> 8) << 48);
@@ -277,8 +393,8 @@ __global__ __launch_bounds__(UGS_WL_BLOCK) void ugs_wl_hash_kernel(WlHashArgs a)
         if (live) {
             WlStream s;
             wl_stream_init(s);
-            const bool dec = t == 0;                   // decimal start labels: one piece each; hex labels: four pieces of 8 characters
-            const int ppl_shift = dec ? 0 : 2;
+            const bool dec = t == 0 && !a.labeled;     // decimal start labels: one piece each; hex labels: four pieces of 8 characters,
+            const int ppl_shift = t == 0 ? 0 : 2;      // 32-bit start labels of label mode: one piece of 8 characters
             const int steps = ((n + 1) << ppl_shift) + 2;
             for (int j = 0; j < steps; ++j) {
                 const int li = j >> ppl_shift, p = j & ((1 << ppl_shift) - 1);
@@ -347,13 +463,16 @@ __global__ __launch_bounds__(256) void ugs_wl_lookup_kernel(WlLookupArgs a) {
 
 }  // namespace
 
-extern "C" int ugs_wl_hash(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
-                           const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, uint64_t *d_digest, int32_t *d_status) {
+static int wl_hash_launch(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols, const int64_t *d_edge_ptr,
+                          int64_t rows, int k, int iterations, int labeled, const int64_t *d_labels, int64_t num_labels, uint64_t *d_digest,
+                          int32_t *d_status) {
     if (k < 1 || k > UGS_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "wl_hash: 1 <= k <= 32");
     if (iterations < 0 || iterations > UGS_WL_MAX_ITER) return ugs_internal_fail(UGS_E_UNSUPPORTED, "wl_hash: 0 <= iterations <= 8");
     if (rows < 0 || num_cols < 0 || (num_cols > 0 && row_stride < num_cols)) return ugs_internal_fail(UGS_E_BAD_ARG, "wl_hash: rows >= 0, num_cols >= 0, row_stride >= num_cols");
+    if (num_labels < 0) return ugs_internal_fail(UGS_E_BAD_ARG, "wl_hash: num_labels >= 0");
     if (rows == 0) return UGS_OK;
-    if (!d_nodes || !d_edge_ptr || !d_digest || !d_status || (num_cols > 0 && !d_edge_index)) return ugs_internal_fail(UGS_E_BAD_ARG, "wl_hash: null pointer");
+    if (!d_nodes || !d_edge_ptr || !d_digest || !d_status || (num_cols > 0 && !d_edge_index) || (num_labels > 0 && !d_labels))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "wl_hash: null pointer");
     hipStream_t s = nullptr;
     if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
     WlHashArgs a{};
@@ -361,10 +480,40 @@ extern "C" int ugs_wl_hash(const int64_t *d_nodes, const int64_t *d_edge_index, 
     a.rows = rows; a.k = k; a.iterations = iterations;
     a.wshift = k <= 8 ? 3 : k <= 16 ? 4 : 5;
     a.digest = reinterpret_cast<u64 *>(d_digest); a.status = d_status;
+    a.labels = d_labels; a.num_labels = num_labels; a.labeled = labeled;
     const int64_t per_block = UGS_WL_BLOCK >> a.wshift;
     const int64_t blocks = (rows + per_block - 1) / per_block;
     if (blocks > 0x7fffffffll) return ugs_internal_fail(UGS_E_UNSUPPORTED, "wl_hash: too many rows for one launch");
     hipLaunchKernelGGL(ugs_wl_hash_kernel, dim3((unsigned)blocks), dim3(UGS_WL_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}
+
+extern "C" int ugs_wl_hash(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                           const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, uint64_t *d_digest, int32_t *d_status) {
+    return wl_hash_launch(d_nodes, d_edge_index, row_stride, num_cols, d_edge_ptr, rows, k, iterations, 0, nullptr, 0, d_digest, d_status);
+}
+
+extern "C" int ugs_wl_hash_labeled(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                                   const int64_t *d_edge_ptr, int64_t rows, int k, int iterations, const int64_t *d_labels,
+                                   int64_t num_labels, uint64_t *d_digest, int32_t *d_status) {
+    return wl_hash_launch(d_nodes, d_edge_index, row_stride, num_cols, d_edge_ptr, rows, k, iterations, 1, d_labels, num_labels, d_digest, d_status);
+}
+
+extern "C" int ugs_wl_feature_labels(const void *d_x, int64_t row_bytes, int64_t row_stride_bytes, int64_t num_rows, int64_t *d_labels) {
+    if (row_bytes < 0 || num_rows < 0 || row_stride_bytes < row_bytes)
+        return ugs_internal_fail(UGS_E_BAD_ARG, "wl_feature_labels: row_bytes >= 0, num_rows >= 0, row_stride_bytes >= row_bytes");
+    if (row_bytes >= (1ll << 29)) return ugs_internal_fail(UGS_E_UNSUPPORTED, "wl_feature_labels: row_bytes < 2^29");
+    if (num_rows == 0) return UGS_OK;
+    if (!d_labels || (row_bytes > 0 && !d_x)) return ugs_internal_fail(UGS_E_BAD_ARG, "wl_feature_labels: null pointer");
+    const int64_t blocks = (num_rows + 255) / 256;
+    if (blocks > 0x7fffffffll) return ugs_internal_fail(UGS_E_UNSUPPORTED, "wl_feature_labels: too many rows for one launch");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    WlLabelArgs a{};
+    a.x = static_cast<const unsigned char *>(d_x); a.stride = row_stride_bytes; a.rows = num_rows; a.len = (unsigned)row_bytes; a.labels = d_labels;
+    hipLaunchKernelGGL(ugs_wl_feature_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
     return UGS_OK;

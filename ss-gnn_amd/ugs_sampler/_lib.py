@@ -79,6 +79,8 @@ def _load():
         "ugs_plan_get_timing": [vp, C.POINTER(C.c_double), i64p],
         "ugs_plan_last_launch": [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), i64p],
         "ugs_wl_hash": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, vp],
+        "ugs_wl_hash_labeled": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp],
+        "ugs_wl_feature_labels": [vp, C.c_int64, C.c_int64, C.c_int64, vp],
         "ugs_wl_lookup": [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp],
     }
     for name, argtypes in sig.items():

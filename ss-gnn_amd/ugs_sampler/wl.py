@@ -16,8 +16,19 @@ sampler's three output tensors, and the lookup from a second one; nothing synchr
 The law is stated at ugs_wl_hash in include/ugs_mi355.h.  Row status: 0 = hashed; 1 = the row has no entry >= 0 (the reference
 answers the unknown id); 2 = an edge endpoint outside the row's vertices -- the one deviation: the reference hashes a fallback
 string "deg_.._edges_.." there, this module answers the unknown id; no sampler of this library produces such a row in mode
-"sample".  Limits: 1 <= k <= 32, 0 <= iterations <= 8.  Node-feature labels (`use_node_features_in_wl=True`: md5 of the feature
-bytes), edge attributes and weisfeiler_lehman_subgraph_hashes are out of scope.
+"sample".  Limits: 1 <= k <= 32, 0 <= iterations <= 8.
+
+Node-feature labels (`use_node_features_in_wl=True`, the reference's real-data configs): `x=batch.x` makes the start label of a
+vertex the first 8 hex characters of the md5 of its feature row's bytes instead of its degree, as compute_wl_hash does with
+node_features (one more launch: the md5 of every row of x, once per vertex of the batch):
+
+    wl_ids = table.ids(nodes, edge_index, edge_ptr, iterations=3, x=batch.x)
+
+`feature_labels(x)` returns those labels (int64 [N], values below 2^32) and `node_labels=` takes them, or any other 32-bit
+categorical labels, so that a caller hashes a batch's features once for several calls.  Vertex j of a row is its j-th entry >= 0
+(`subgraph_nodes[valid_mask]`).  Row status 3: an entry that is no row of x / node_labels, or a label outside [0, 2^32) -- the
+reference raises IndexError there; this module answers no digest and the unknown id, other rows are not disturbed.  Edge
+attributes and weisfeiler_lehman_subgraph_hashes are out of scope.
 """
 import re
 
@@ -27,7 +38,7 @@ import torch
 from . import _select_device
 from ._lib import check, lib
 
-__all__ = ["wl_hash", "hexdigests", "WLVocab", "extend_vocab"]
+__all__ = ["wl_hash", "feature_labels", "hexdigests", "WLVocab", "extend_vocab"]
 
 _HEX32 = re.compile(r"[0-9a-f]{32}\Z")
 
@@ -52,7 +63,82 @@ def _check_inputs(nodes, edge_index, edge_ptr, iterations):
         raise ValueError("tensors must be on the CPU or on a GPU")
 
 
-def _hash_on_device(nodes, edge_index, edge_ptr, iterations):
+# dtypes numpy represents: the reference hashes x[i].numpy().tobytes(), which fails for any other one (bfloat16, ...)
+_FEATURE_DTYPES = (torch.float16, torch.float32, torch.float64, torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8, torch.bool)
+
+
+def _check_x(x):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dtype not in _FEATURE_DTYPES:
+        raise TypeError(f"x must have a dtype numpy represents (float16/32/64, int8/16/32/64, uint8, bool), got {x.dtype}")
+    if x.dim() < 1:
+        raise ValueError("x must have shape [N, ...]")
+    if x.device.type not in ("cpu", "cuda"):
+        raise ValueError("x must be on the CPU or on a GPU")
+
+
+def _check_labels(nodes, x, node_labels):
+    """Validation of the two label keywords against the sampler tensors, before any device work."""
+    if x is not None and node_labels is not None:
+        raise ValueError("x= and node_labels= are mutually exclusive")
+    if x is not None:
+        _check_x(x)
+    if node_labels is not None:
+        if not isinstance(node_labels, torch.Tensor):
+            raise TypeError("node_labels must be a torch.Tensor")
+        if node_labels.dtype != torch.int64:
+            raise TypeError(f"node_labels must be int64, got {node_labels.dtype}")
+        if node_labels.dim() != 1:
+            raise ValueError("node_labels must have shape [N]")
+    given = x if x is not None else node_labels
+    if given is not None and given.device != nodes.device:
+        raise ValueError(f"the sampler tensors are on {nodes.device}, the labels on {given.device}")
+
+
+def _labels_on_device(x):
+    """label32 of every row of the GPU tensor x: int64 [N]; the library's device and stream are already selected."""
+    N = x.size(0)
+    rows = x.reshape(N, int(np.prod(x.shape[1:], dtype=np.int64)))
+    row_bytes = rows.size(1) * rows.element_size()
+    if not (rows.stride(1) == 1 or rows.size(1) <= 1) or (N > 1 and rows.stride(0) < rows.size(1)):
+        rows = rows.contiguous()                       # the logical C order of a row's elements
+    stride_bytes = rows.stride(0) * rows.element_size() if N > 1 else row_bytes
+    labels = torch.empty((N,), dtype=torch.int64, device=x.device)
+    if N > 0 or row_bytes >= 1 << 29:                  # the library states the limit
+        check(lib.ugs_wl_feature_labels(rows.data_ptr() if row_bytes > 0 and N > 0 else None, row_bytes, max(stride_bytes, row_bytes), N, labels.data_ptr()))
+    return labels
+
+
+def _gpu_of(t, device):
+    """The GPU that works on tensor t (its own, or `device` for a CPU tensor), and whether results go back to the CPU."""
+    if t.device.type == "cuda":
+        if device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, t.device.index):
+            raise ValueError(f"the tensors are on {t.device}, device={device} names another GPU")
+        return t.device, False
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise ValueError("device= must be a GPU device: the hashes are computed there")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev, True
+
+
+def feature_labels(x, *, device=None):
+    """The node-feature start labels of the reference's compute_wl_hash: int64 [N] with
+    labels[i] = int(hashlib.md5(x[i].numpy().tobytes()).hexdigest()[:8], 16), computed on the GPU in one launch.
+
+    x has shape [N, ...] (a 1-D x is N rows of one element) and a dtype numpy represents; a row's bytes are its elements in C
+    order in x's own dtype, whatever x's strides.  The result is on x's device: a CPU x is copied to `device` (default: the
+    current GPU) and the labels come back on the CPU.  For `wl_hash(..., node_labels=)` and `WLVocab.ids(..., node_labels=)`."""
+    _check_x(x)
+    dev, back = _gpu_of(x, device)
+    _select_device(dev, jobs=True)
+    labels = _labels_on_device(x.to(dev))
+    return labels.cpu() if back else labels
+
+
+def _hash_on_device(nodes, edge_index, edge_ptr, iterations, x=None, node_labels=None):
     """(digest int64 [S, 2], status int32 [S]) on the tensors' GPU; the library's device and stream are already selected."""
     dev = nodes.device
     S, k = nodes.shape
@@ -63,7 +149,15 @@ def _hash_on_device(nodes, edge_index, edge_ptr, iterations):
     if E > 0 and edge_index.stride(1) != 1:
         edge_index = edge_index.contiguous()
     stride = edge_index.stride(0) if E > 0 else 0
-    if S > 0 or not 1 <= k <= 32 or not 0 <= iterations <= 8:       # the library states the limits
+    if x is not None:
+        node_labels = _labels_on_device(x)
+    if node_labels is not None:
+        node_labels = node_labels.contiguous()
+        N = node_labels.numel()
+        if S > 0 or not 1 <= k <= 32 or not 0 <= iterations <= 8:
+            check(lib.ugs_wl_hash_labeled(nodes.data_ptr(), edge_index.data_ptr() if E > 0 else None, stride, E, edge_ptr.data_ptr(), S, k, iterations,
+                                          node_labels.data_ptr() if N > 0 else None, N, digest.data_ptr(), status.data_ptr()))
+    elif S > 0 or not 1 <= k <= 32 or not 0 <= iterations <= 8:     # the library states the limits
         check(lib.ugs_wl_hash(nodes.data_ptr(), edge_index.data_ptr() if E > 0 else None, stride, E, edge_ptr.data_ptr(), S, k, iterations,
                               digest.data_ptr(), status.data_ptr()))
     return digest, status
@@ -71,35 +165,37 @@ def _hash_on_device(nodes, edge_index, edge_ptr, iterations):
 
 def _placed(nodes, edge_index, edge_ptr, device):
     """The three tensors on the GPU that does the work (copies of CPU tensors), and whether results go back to the CPU."""
-    if nodes.device.type == "cuda":
-        if device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, nodes.device.index):
-            raise ValueError(f"the tensors are on {nodes.device}, device={device} names another GPU")
-        return nodes, edge_index, edge_ptr, nodes.device, False
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise ValueError("device= must be a GPU device: the hashes are computed there")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev, back = _gpu_of(nodes, device)
+    if not back:
+        return nodes, edge_index, edge_ptr, dev, False
     return nodes.to(dev), edge_index.to(dev), edge_ptr.to(dev), dev, True
 
 
-def wl_hash(nodes_sampled, edge_index_sampled, edge_ptr, iterations=3, *, device=None):
+def wl_hash(nodes_sampled, edge_index_sampled, edge_ptr, iterations=3, *, device=None, x=None, node_labels=None):
     """WL graph hash of every sampled subgraph: (digest int64 [S, 2], status int32 [S]).
 
     The inputs are the first three outputs of any sampler's sample_batch / sample_graphs in mode "sample" (or of
     PresampleCache.load).  digest[i] holds bytes 0-7 and 8-15 of row i's BLAKE2b-128 digest as big-endian numbers (as int64 bit
     patterns; zero where status != 0): `hexdigests` turns them into networkx's strings.  Device tensors are used in place and
     the results stay there, on torch's current stream; CPU tensors are copied to `device` (default: the current GPU) and the
-    results come back on the CPU.  Node-feature labels are not supported (module docstring)."""
+    results come back on the CPU.
+
+    Without `x` and `node_labels` the start labels are the degrees (use_node_features_in_wl=False).  `x=batch.x` [N, ...] gives
+    the node-feature form: the label of a vertex is the md5 of its feature row (`feature_labels`, one more launch);
+    `node_labels=` int64 [N] supplies the labels directly.  Either lives on the device of the sampler tensors; the two exclude
+    each other.  A row with an entry >= N or a label outside [0, 2^32) gets status 3 (module docstring)."""
     _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, iterations)
+    _check_labels(nodes_sampled, x, node_labels)
     nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, device)
     _select_device(dev, jobs=True)
-    digest, status = _hash_on_device(nodes, edge_index, eptr, iterations)
+    digest, status = _hash_on_device(nodes, edge_index, eptr, iterations, None if x is None else x.to(dev),
+                                     None if node_labels is None else node_labels.to(dev))
     return (digest.cpu(), status.cpu()) if back else (digest, status)
 
 
 def hexdigests(digest, status):
-    """networkx's hex strings of `wl_hash` results, None where status != 0: for a host-side consumer or a pickled vocabulary."""
+    """networkx's hex strings of `wl_hash` results, None where status != 0 (no vertices, a bad endpoint, or with labels status 3:
+    an id or label out of range): for a host-side consumer or a pickled vocabulary."""
     d = digest.detach().cpu().numpy().astype(np.int64, copy=False).view(np.uint64).reshape(-1, 2)
     s = status.detach().cpu().numpy().reshape(-1)
     if d.shape[0] != s.shape[0]:
@@ -110,7 +206,7 @@ def hexdigests(digest, status):
 def extend_vocab(vocab, digest, status):
     """Adds the unseen hashes of one batch to `vocab` (hex string -> id) in row order, with ids len(vocab), len(vocab) + 1, ...:
     one batch's worth of build_wl_vocabulary_from_loader (wl_vocab.py:156-175).  Rows without valid vertices are skipped as the
-    reference does, and so are rows of status 2 (module docstring).  Returns `vocab`."""
+    reference does, and so are rows of status 2 and 3 (module docstring).  Returns `vocab`."""
     for h in hexdigests(digest, status):
         if h is not None and h not in vocab:
             vocab[h] = len(vocab)
@@ -153,7 +249,7 @@ class WLVocab:
 
     def lookup(self, digest, status):
         """ids int64 [S] of `wl_hash` results that live on the table's GPU: the id of each digest, len(self) where it is unknown
-        or status != 0 (hash_to_id, wl_vocab.py:205-216)."""
+        or status != 0 -- rows of status 2 and 3 too (hash_to_id, wl_vocab.py:205-216)."""
         keys, key_ids = self._table()
         if digest.device != self.device or status.device != self.device:
             raise ValueError(f"digest and status must be on {self.device}")
@@ -169,16 +265,20 @@ class WLVocab:
                                 key_ids.data_ptr() if V else None, V, len(self), out.data_ptr()))
         return out
 
-    def ids(self, nodes_sampled, edge_index_sampled, edge_ptr, iterations=3):
-        """What the reference's _compute_wl_ids returns with use_node_features_in_wl=False: int64 [S] on the device of
-        nodes_sampled, len(self) for unknown hashes and for rows without valid vertices.  Two launches on torch's current
-        stream, no synchronisation with the host (CPU tensors: copied to the table's GPU, the ids come back on the CPU)."""
+    def ids(self, nodes_sampled, edge_index_sampled, edge_ptr, iterations=3, *, x=None, node_labels=None):
+        """What the reference's _compute_wl_ids returns: int64 [S] on the device of nodes_sampled, len(self) for unknown hashes
+        and for rows without valid vertices.  Without `x` and `node_labels` that is use_node_features_in_wl=False; `x=batch.x`
+        or `node_labels=feature_labels(batch.x)` is use_node_features_in_wl=True (see `wl_hash`; rows of status 3 get
+        len(self)).  Two launches on torch's current stream, three with `x=`, no synchronisation with the host (CPU tensors:
+        copied to the table's GPU, the ids come back on the CPU)."""
         _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, iterations)
+        _check_labels(nodes_sampled, x, node_labels)
         self._table()
         nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, self.device)
         if dev != self.device:
             raise ValueError(f"the tensors are on {dev}, the vocabulary on {self.device}")
         _select_device(dev, jobs=True)
-        digest, status = _hash_on_device(nodes, edge_index, eptr, iterations)
+        digest, status = _hash_on_device(nodes, edge_index, eptr, iterations, None if x is None else x.to(dev),
+                                         None if node_labels is None else node_labels.to(dev))
         out = self.lookup(digest, status)
         return out.cpu() if back else out
