@@ -279,6 +279,22 @@ int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
 int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                 int64_t *edge_src, int dst_is_device);
 
+/* ---- epsilon_uniform_sampler.sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode, epsilon): the batched form of the
+ *      reference trainer's presample loop (gps/experiment.py:379-440), which calls the sampler once per graph with
+ *      seed = cfg.seed + i.  Every graph g has its own seed seeds[g]: row b = g m + i keys its generator with
+ *      (seeds[g], i, attempt) instead of (seed, b, attempt), and nothing else differs from ugs_eps_sample_batch_begin.
+ *      The law: graph g's block -- nodes rows [g m, (g+1) m), their edge entries, edge_ptr re-based to the block -- equals what
+ *      ugs_eps_sample_batch_begin(edge_index, row_stride, num_cols, ptr + g, 1, m_per_graph, k, mode, seeds[g], epsilon) returns:
+ *      node ids and the edge ids of the batch-id mode are batch ids and edge_src holds batch column indices, so nothing else
+ *      needs re-basing; columns outside the graph's range are dropped, both modes.  sample_ptr = [0, m, 2m, ..., G m].
+ *      seeds: host array of num_graphs values (copied by begin); NULL with num_graphs > 0 is UGS_E_BAD_ARG.
+ *      graph_status: host array of num_graphs entries (may be NULL), written all zero -- no condition of this sampler makes one
+ *      graph fail alone; a graph with fewer than k vertices gives m rows of -1 without edges, as in sample_batch.
+ *      Same argument checks and error texts as ugs_eps_sample_batch_begin, same job: finish with ugs_eps_sample_batch_finish. */
+int ugs_eps_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, double epsilon,
+                                int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
+
 /* ---- uniform_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed): replaces the reference's
  *      src/samplers/uniform_sampler/src/uniform_sampler.cpp:86-285 (exact uniform sampling over ALL connected k-subsets).
  *      The law, for each graph g in batch order, vertices [ptr[g], ptr[g+1]), n = ptr[g+1] - ptr[g]:

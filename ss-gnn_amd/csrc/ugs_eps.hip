@@ -7,8 +7,10 @@
 // MI355X mapping: samples are independent and tiny (k <= 32 vertices, a handful of short adjacency rows), so ONE LANE owns
 // one sample (64 samples per wavefront); per-sample vertex and frontier lists live in LDS in a [slot][lane] layout
 // (conflict-free); random numbers come from a counter-based generator keyed by (seed, row, attempt), so a row never
-// depends on which lane, wave or GPU computes it.  Edge extraction is a count pass (fused into the walk), a scan, and a
-// fill pass that writes each sample's edges and orders them by column inside the sample's own segment.
+// depends on which lane, wave or GPU computes it.  The per-graph-seed form (sample_graphs) keys the generator with
+// (seeds[graph], row inside the graph, attempt) instead: graph g's rows draw what a one-graph call with seed seeds[g] draws.
+// Edge extraction is a count pass (fused into the walk), a scan, and a fill pass that writes each sample's edges and
+// orders them by column inside the sample's own segment.
 #include "ugs_device.h"
 
 namespace {
@@ -55,6 +57,7 @@ struct EpsArgs {
     int64_t num_graphs;
     int32_t m, k, mode, max_attempts;
     uint64_t seed;
+    const uint64_t *seeds;        // per-graph-seed form only: [num_graphs]
     double epsilon;
     int64_t rows;
     int64_t *nodes;               // [rows, k] batch node ids, ascending; -1 rows for failed samples
@@ -64,6 +67,9 @@ struct EpsArgs {
     int64_t ld;
 };
 
+// GRAPH_SEEDS = false: one seed per call, generator key (seed, batch row, attempt) -- sample_batch.
+// GRAPH_SEEDS = true: generator key (seeds[gi], row - gi * m, attempt) -- sample_graphs; nothing else differs.
+template <bool GRAPH_SEEDS>
 __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_walk(EpsArgs a) {
     __shared__ int32_t s_nodes[UGS_KMAX * EPS_BLOCK];
     __shared__ int32_t s_front[UGS_KMAX * EPS_BLOCK];
@@ -74,11 +80,13 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_walk(EpsArgs a) {
         const int64_t gi = row / a.m;
         const UgsGraphDesc gd = a.graphs[gi];
         const int n = gd.n;
+        const uint64_t key_seed = GRAPH_SEEDS ? a.seeds[gi] : a.seed;                       // read once per row
+        const uint64_t key_row = GRAPH_SEEDS ? (uint64_t)(row - gi * a.m) : (uint64_t)row;
         bool success = false;
         if (n >= k) {
             for (int attempt = 0; attempt < a.max_attempts && !success; ++attempt) {
                 CRng rng;
-                rng.init(a.seed, (uint64_t)row, (uint64_t)attempt);
+                rng.init(key_seed, key_row, (uint64_t)attempt);
                 int size = 1, fsz = 1;
                 const int start = (int)rng.below((uint32_t)n);
                 nd[0] = start; fr[0] = start;
@@ -193,18 +201,20 @@ struct UgsEpsLaunch {
     const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;
     int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
     int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
+    const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
 };
 
 hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s) {
     if (l.rows <= 0) return hipSuccess;
     EpsArgs a;
     a.graphs = l.graphs; a.rowptr = l.rowptr; a.nbr = l.nbr; a.ecs = l.ecs; a.num_graphs = l.num_graphs;
-    a.m = l.m; a.k = l.k; a.mode = l.mode; a.max_attempts = l.max_attempts; a.seed = l.seed; a.epsilon = l.epsilon; a.rows = l.rows;
+    a.m = l.m; a.k = l.k; a.mode = l.mode; a.max_attempts = l.max_attempts; a.seed = l.seed; a.seeds = l.seeds; a.epsilon = l.epsilon; a.rows = l.rows;
     a.nodes = l.nodes; a.counts = l.counts; a.edge_ptr = l.edge_ptr; a.edge_index = l.edge_index; a.edge_src = l.edge_src; a.ld = l.ld;
     int64_t grid = (l.rows + EPS_BLOCK - 1) / EPS_BLOCK;
     const int64_t cap = (int64_t)(cus > 0 ? cus : 256) * 8;
     if (grid > cap) grid = cap;
     if (fill) hipLaunchKernelGGL(ugs_eps_fill, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(ugs_eps_walk, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
+    else if (l.seeds) hipLaunchKernelGGL(ugs_eps_walk<true>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(ugs_eps_walk<false>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
     return hipGetLastError();
 }

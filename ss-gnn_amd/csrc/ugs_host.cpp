@@ -34,6 +34,7 @@ struct UgsEpsLaunch {
     const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;
     int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
     int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
+    const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
 };
 hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s);
 
@@ -2779,8 +2780,11 @@ int ugs_sample_stream(int64_t handle, int m_per_graph, int k, int edge_mode, int
 }
 
 // ---- epsilon_uniform_sampler.sample_batch (reference src/samplers/epsilon_uniform_sampler/src/epsilon_uniform_sampler.cpp) ----
-int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
-                               int m_per_graph, int k, int mode, uint64_t seed, double epsilon, ugs_job **job_out, int64_t *total_edges_out) {
+// Body of ugs_eps_sample_batch_begin (seeds == nullptr: `seed` keys every row) and ugs_eps_sample_graphs_begin (seeds: one per graph,
+// uploaded in the adjacency blob).
+static int eps_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                     int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, double epsilon, ugs_job **job_out,
+                     int64_t *total_edges_out) {
     if (!job_out || !ptr || num_graphs < 0 || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (!(epsilon > 0.0 && epsilon <= 1.0)) return fail(UGS_E_BAD_ARG, "epsilon must be in (0, 1]");
     if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
@@ -2801,8 +2805,10 @@ int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     size_t off_row = align_up(off_desc + (size_t)std::max<int64_t>(G, 1) * sizeof(UgsGraphDesc));
     size_t off_nbr = align_up(off_row + (size_t)std::max<int64_t>(nrows, 1) * sizeof(int64_t));
     size_t off_ecs = align_up(off_nbr + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
-    size_t total = align_up(off_ecs + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
+    size_t off_seeds = align_up(off_ecs + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
+    size_t total = seeds ? align_up(off_seeds + (size_t)std::max<int64_t>(G, 1) * sizeof(uint64_t)) : off_seeds;
     std::vector<char> host(total, 0);
+    if (seeds && G > 0) std::memcpy(host.data() + off_seeds, seeds, (size_t)G * sizeof(uint64_t));
     auto *desc = reinterpret_cast<UgsGraphDesc *>(host.data() + off_desc);
     auto *rowp = reinterpret_cast<int64_t *>(host.data() + off_row);
     auto *nbr = reinterpret_cast<int32_t *>(host.data() + off_nbr);
@@ -2846,7 +2852,8 @@ int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     l.ecs = reinterpret_cast<const int32_t *>(base + off_ecs);
     l.num_graphs = G; l.m = m_per_graph; l.k = k; l.mode = mode;
     l.max_attempts = std::max(10, (int)(10.0 / epsilon));
-    l.seed = seed; l.epsilon = epsilon; l.rows = j->rows;
+    l.seed = seed; l.seeds = seeds ? reinterpret_cast<const uint64_t *>(base + off_seeds) : nullptr;
+    l.epsilon = epsilon; l.rows = j->rows;
     l.nodes = static_cast<int64_t *>(j->nodes.p); l.counts = static_cast<uint32_t *>(j->eps_counts.p);
     l.edge_ptr = nullptr; l.edge_index = nullptr; l.edge_src = nullptr; l.ld = 0;
     e = ugs_eps_launch(l, 0, dc.cus, dc.stream);
@@ -2859,6 +2866,21 @@ int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, in
     *job_out = j;
     if (total_edges_out) *total_edges_out = j->total;
     return UGS_OK;
+}
+
+int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int m_per_graph, int k, int mode, uint64_t seed, double epsilon, ugs_job **job_out, int64_t *total_edges_out) {
+    return eps_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, seed, nullptr, epsilon, job_out, total_edges_out);
+}
+
+// ---- epsilon_uniform_sampler.sample_graphs: one seed per graph (the law is stated in include/ugs_mi355.h) ----
+int ugs_eps_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                                int m_per_graph, int k, int mode, const uint64_t *seeds, double epsilon, int32_t *graph_status,
+                                ugs_job **job_out, int64_t *total_edges_out) {
+    if (num_graphs > 0 && !seeds) return fail(UGS_E_BAD_ARG, "sample_graphs needs one seed per graph");
+    const int rc = eps_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds, epsilon, job_out, total_edges_out);
+    if (rc == UGS_OK && graph_status) std::fill(graph_status, graph_status + num_graphs, 0);   // no graph of this sampler fails alone
+    return rc;
 }
 
 int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,

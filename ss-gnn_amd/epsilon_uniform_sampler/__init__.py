@@ -7,14 +7,19 @@ Sampling runs in HIP kernels (one lane per sample, counter-based generator per (
 deterministic for this sampler (per-thread generators seeded with the OpenMP thread id, dynamic schedule, rows written in
 completion order); this implementation is deterministic in (seed, row) and its parity with the reference is statistical:
 same growth law, same acceptance law min(1, eps/(w+eps)), same attempt budget max(10, 10/eps), same output format.
+
+sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", epsilon=0.1) -> the 5-tuple + failed[G] (bool, all False):
+graph g's rows keyed by (seeds[g], row inside the graph) instead of (seed, batch row) -- the presample loop batched; law at
+ugs_eps_sample_graphs_begin.
 """
 import ctypes as C
 
 import torch
 
+from ugs_sampler import _graphs
 from ugs_sampler._lib import check, lib, vp
 
-__all__ = ["sample_batch"]
+__all__ = ["sample_batch", "sample_graphs", "_sample_graphs"]
 
 
 def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, epsilon=0.1):
@@ -61,3 +66,22 @@ def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, epsilo
         raise
     check(lib.ugs_eps_sample_batch_finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(), esrc.data_ptr(), 1 if on_dev else 0))
     return nodes, eidx, eptr, sptr, esrc
+
+
+def sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", epsilon=0.1):
+    """Many one-graph calls in one: graph g's block of m rows equals sample_batch(edge_index, ptr[g:g+2], m_per_graph, k, mode,
+    seeds[g], epsilon) with edge_ptr re-based (node ids are batch ids, edge_src batch columns).  No graph fails alone: a graph
+    with fewer than k vertices gives m rows of -1, and failed is all False.
+    Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src, failed), the five on the device of `edge_index`, failed on the host."""
+    out, failed = _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode, epsilon)
+    return out + (failed,)
+
+
+def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", epsilon=0.1, device=None):
+    """sample_graphs with the outputs on `device` (PresampleCache.add_many)"""
+    if not (epsilon > 0.0 and epsilon <= 1.0):
+        raise RuntimeError("epsilon must be in (0, 1]")
+    eps = C.c_double(float(epsilon))
+    return _graphs.sample_graphs(lambda ei, rs, nc, pt, G, m, kk, md, sd, st, job, tot:
+                                 lib.ugs_eps_sample_graphs_begin(ei, rs, nc, pt, G, m, kk, md, sd, eps, st, job, tot),
+                                 lib.ugs_eps_sample_batch_finish, edge_index, ptr, m_per_graph, k, seeds, mode, device)

@@ -44,6 +44,8 @@ def _load():
         "ugs_eps_sample_batch_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double,
                                        C.POINTER(vp), i64p],
         "ugs_eps_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
+        "ugs_eps_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
+                                        C.POINTER(vp), i64p],
         "ugs_uniform_sample_batch_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                            C.POINTER(vp), i64p],
         "ugs_uniform_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],

@@ -7,7 +7,8 @@ edge_src re-based by the number of batch columns that belong to earlier graphs, 
 with `.item()` per graph and per sample.  Here the cache lives in HBM as flat tensors and a batch is assembled by a handful of
 device gathers; the sizes that decide the output shapes are known on the host from build time, so nothing synchronises.
 
-    cache = PresampleCache(m, k, device="cuda:0", sampler="rwr")   # "ugs" (default), "uniform" or "rwr": the config's sampler
+    cache = PresampleCache(m, k, device="cuda:0", sampler="rwr")   # "ugs" (default), "uniform", "rwr" or "epsilon_uniform"
+                                                                   # (with epsilon=...): the config's sampler
     cache.add_many(range(len(dataset)), [(d.edge_index, d.num_nodes) for d in dataset],
                    [cfg.seed + i for i in range(len(dataset))])    # start-up, like _setup_presampling
     cache.finalize()
@@ -25,7 +26,7 @@ import torch
 
 from . import _I32_MAX, _I32_MIN, sample_batch
 
-SAMPLERS = ("ugs", "uniform", "rwr")
+SAMPLERS = ("ugs", "uniform", "rwr", "epsilon_uniform")
 # add_many's call bounds.  Vertices: the uniform count pass keeps 12 B per (root, first extension) item and 64 items per vertex,
 # 768 B per vertex, so 2^17 vertices hold about 100 MB of item arrays (a whole QM9 split would need gigabytes).  Rows: the
 # outputs and per-row scratch of 2^21 rows are about 130 MB at k = 6.  A graph larger than a bound is a call of its own.
@@ -41,17 +42,21 @@ def _drop_in(sampler):
     if sampler == "uniform":
         import uniform_sampler
         return uniform_sampler
+    if sampler == "epsilon_uniform":
+        import epsilon_uniform_sampler
+        return epsilon_uniform_sampler
     import rwr_sampler
     return rwr_sampler
 
 
 class PresampleCache:
-    def __init__(self, m, k, device, sampler="ugs", p_restart=0.2, chunk_vertices=CHUNK_VERTICES, chunk_rows=CHUNK_ROWS):
+    def __init__(self, m, k, device, sampler="ugs", p_restart=0.2, chunk_vertices=CHUNK_VERTICES, chunk_rows=CHUNK_ROWS,
+                 epsilon=0.1):
         if sampler not in SAMPLERS:
             raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
         self.m, self.k = int(m), int(k)
         self.dev = torch.device(device)
-        self.sampler, self.p_restart = sampler, float(p_restart)
+        self.sampler, self.p_restart, self.epsilon = sampler, float(p_restart), float(epsilon)
         self.chunk_vertices, self.chunk_rows = max(int(chunk_vertices), 1), max(int(chunk_rows), 1)
         self.failed = set()             # indices whose presampling failed
         self._slot = {}                 # graph index -> slot (-1: presampling failed)
@@ -68,6 +73,8 @@ class PresampleCache:
         ei = edge_index.to(self.dev)    # device in, device out
         if self.sampler == "rwr":
             return mod.sample_batch(ei, ptr, self.m, self.k, mode="sample", seed=int(seed), p_restart=self.p_restart)
+        if self.sampler == "epsilon_uniform":
+            return mod.sample_batch(ei, ptr, self.m, self.k, mode="sample", seed=int(seed), epsilon=self.epsilon)
         return mod.sample_batch(ei, ptr, self.m, self.k, mode="sample", seed=int(seed))
 
     def _fail(self, index):
@@ -145,7 +152,7 @@ class PresampleCache:
         bad = ((ei < 0) | (ei >= n[gid])).any(axis=0)
         ei = np.where(bad, -1, ei + ptr[gid])
         mod = _drop_in(self.sampler)
-        extra = dict(p_restart=self.p_restart) if self.sampler == "rwr" else {}
+        extra = {"rwr": dict(p_restart=self.p_restart), "epsilon_uniform": dict(epsilon=self.epsilon)}.get(self.sampler, {})
         try:
             (nodes, eidx, eptr, _, esrc), failed = mod._sample_graphs(torch.from_numpy(ei), torch.from_numpy(ptr), m, k,
                                                                       [g[3] for g in run], "sample",
@@ -158,7 +165,8 @@ class PresampleCache:
                 for i, e_i, n_i, s in run:
                     self.add(i, e_i, n_i, s)
             return
-        # back to the one-graph form: local node ids, edge_src local to the graph's own columns (rwr's -1 stays), edge_ptr per graph
+        # back to the one-graph form: local node ids, edge_src local to the graph's own columns (rwr's -1 stays; the other samplers'
+        # edge_src are column positions >= 0, so the guard leaves them alone), edge_ptr per graph
         dev = nodes.device
         i64 = dict(dtype=torch.int64, device=dev)
         ptr_d = torch.from_numpy(ptr).to(dev)
