@@ -253,7 +253,10 @@ int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len,
  *      device: offsets are taken from the headers ON the device, entries at positions >= ld are not written.  A message whose
  *      edge total exceeds edge_cap was truncated by its sender: the batch is then INVALID; d_max_total (one device word, kept
  *      by the caller across steps) receives the largest total seen so that the caller can find out without a per-step host
- *      round trip (total > edge_cap). */
+ *      round trip (total > edge_cap).
+ *      A batch without rows (row_off[world] == row_off[0]) is legal: nothing is launched over rows or edge entries, the one
+ *      closing word edge_ptr[row_off[world]] is set to 0, d_nodes / d_edge_index / d_edge_src may be null (an empty device
+ *      tensor has no address) and *d_max_total is left as it is.  With rows, a null output pointer is refused. */
 int ugs_collate_layout(int k, int node_bytes, int eidx_bytes, int esrc_bytes, int64_t rows_cap, int64_t edge_cap,
                        int64_t *section_off4, int64_t *msg_bytes);
 int ugs_collate_unpack(const void *d_msgs, int world, const int64_t *row_off /* host, world+1 */, int k, int node_bytes,
