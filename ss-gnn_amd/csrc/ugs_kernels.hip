@@ -1254,11 +1254,51 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
     return true;
 }
 
+// The row of the LAST vertex of a complete sample (one walk per wave, LDS tiers; do_walk).  Nothing is selected after it, so the row
+// adds no candidates and asks only "is this neighbour one of the `size` sampled vertices?".  The table answers that with a probe
+// sequence per lane -- at its fullest now, and nearly every sequence is an unsuccessful search that runs to an empty slot, the chunk
+// paying for the longest one -- but the members themselves are the `size` words SV[0..size-1]: lane j takes SV[j] once per row
+// (last_row_members), and a chunk compares its neighbour with each of them as a wave-uniform scalar (v_readlane, v_cmp, s_or per
+// member; no LDS, no EXEC narrowing, no loop for k <= 8).  The scanned vertex is SV[size-1] itself, so a self entry is found without
+// its flag in the table.  The suffix filter is not asked: every member passed it when it became a candidate, and a vertex has one rank.
+// Lanes past the sample hold kNoMember and lanes without an entry kEmpty: neither equals a vertex (< 2^30) nor each other.
+constexpr uint32_t kNoMember = 0xFFFFFFFEu;
+__device__ __forceinline__ uint32_t last_row_members(const Grp<64> &g, const uint32_t *SV, uint32_t size) {
+    return (uint32_t)g.lane < size ? SV[g.lane & (UGS_KMAX - 1)] : kNoMember;
+}
+template <bool SON>
+__device__ __forceinline__ void scan_chunk_last(const Grp<64> &g, uint32_t v, uint32_t size, uint32_t &ecount, StageCtx &sc,
+                                                uint32_t w, uint32_t p, uint32_t members) {
+    uint64_t im = 0ull;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) im |= __ballot(w == (uint32_t)__builtin_amdgcn_readlane((int)members, j));
+    if (__builtin_expect(size > 8u, 0)) {
+        for (uint32_t j = 8; j < size; j += 4) {             // (lanes size.. hold kNoMember: the last trip's extra compares add nothing)
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) im |= __ballot(w == (uint32_t)__builtin_amdgcn_readlane((int)members, (int)(j + u)));
+        }
+    }
+    // exactly what the probing form feeds: a self entry (w == v) counts once, an entry to an earlier member twice, every repeat again
+    ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;
+    stage_hits_mask<SON>(sc, g, im, w, p, size);
+}
+
 // row of v through the row pointer (8-lane tier, global-memory tier, plans without padded rows)
-template <int GS, class SP, bool ADD, bool STG>
+template <int GS, class SP, bool ADD, bool STG, bool LAST = false>
 __device__ __forceinline__ bool scan_row(const Work<SP> &ws, const Grp<GS> &g, const int2 *adj, uint32_t v,
                                          uint32_t root_vi, uint32_t size, uint32_t &c, uint32_t &hcount,
-                                         uint32_t &ecount, uint32_t r0, uint32_t r1, StageCtx &sc) {
+                                         uint32_t &ecount, uint32_t r0, uint32_t r1, StageCtx &sc, const uint32_t *SV = nullptr) {
+    if constexpr (LAST) {
+        static_assert(GS == 64 && STG && !ADD, "the compare form of the last row: one walk per wave, LDS tiers");
+        const uint32_t members = last_row_members(g, SV, size);
+        for (uint32_t base = r0; base < r1; base += 64) {
+            const uint32_t p = base + (uint32_t)g.lane;
+            int2 e = UGS_NO_ENTRY;
+            if (p < r1) e = adj[p];
+            scan_chunk_last<false>(g, v, size, ecount, sc, (uint32_t)e.x, p, members);
+        }
+        return true;
+    }
     for (uint32_t base = r0; base < r1; base += GS) {
         const uint32_t p = base + (uint32_t)g.lane;
         int2 e = UGS_NO_ENTRY;
@@ -1282,10 +1322,10 @@ __device__ __forceinline__ int2 load_prow(const UgsPlanDev &P, int64_t vrow, int
     return e;
 }
 
-template <class SP, bool ADD, bool STG, bool SON = false>
+template <class SP, bool ADD, bool STG, bool SON = false, bool LAST = false>
 __device__ __forceinline__ bool scan_prow(const Work<SP> &ws, const Grp<64> &g, const UgsPlanDev &P, uint32_t v,
                                           uint32_t root_vi, uint32_t size, uint32_t &c, uint32_t &hcount,
-                                          uint32_t &ecount, int2 e0, int64_t vrow, StageCtx &sc) {
+                                          uint32_t &ecount, int2 e0, int64_t vrow, StageCtx &sc, const uint32_t *SV = nullptr) {
     const uint32_t deg = g.bcast((uint32_t)e0.x, 0);
     const uint32_t start = g.bcast((uint32_t)e0.y, 0);
     const uint32_t inl = (1u << P.prow_shift) - 1u;                              // entries held by the block itself
@@ -1294,6 +1334,21 @@ __device__ __forceinline__ bool scan_prow(const Work<SP> &ws, const Grp<64> &g, 
         if (g.lane >= P.prow_first && g.lane <= (int)n0) e0 = prow_entry(P, vrow, g.lane);
     }
     if ((uint32_t)(g.lane - 1) >= n0) e0 = UGS_NO_ENTRY;                        // the header's lane and the lanes behind the row
+    if constexpr (LAST) {                                                        // the row of the last vertex: see scan_chunk_last
+        static_assert(STG && !ADD, "the compare form of the last row: one walk per wave, LDS tiers");
+        const uint32_t members = last_row_members(g, SV, size);
+        if (n0) scan_chunk_last<SON>(g, v, size, ecount, sc, (uint32_t)e0.x, start + (uint32_t)g.lane - 1u, members);
+        if (__builtin_expect(deg > inl, 0)) {
+            const uint32_t r1 = start + deg;
+            for (uint32_t base = start + inl; base < r1; base += 64) {
+                const uint32_t p = base + (uint32_t)g.lane;
+                int2 e = UGS_NO_ENTRY;
+                if (p < r1) e = P.adj[p];
+                scan_chunk_last<SON>(g, v, size, ecount, sc, (uint32_t)e.x, p, members);
+            }
+        }
+        return true;
+    }
     // a row whose every entry could be a new candidate and still fit needs no per-chunk overflow tests (nearly all rows); the
     // others take the guarded chunks, so the walks a tier hands on are exactly those it handed on before
     // (`n0 != 0` is tested on an opaque scalar copy in each path: shared between the two, the compiler carries the condition through
@@ -1521,7 +1576,18 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     uint32_t size = 1, c = 0, hcount = 1, ecount = 0;
     int nvalid = 0;           // leading stages of the order computation that are still valid
     STAMP_END(0);
-    for (int step = 0;; ++step) {
+    // One walk per wave, LDS tiers: the growth loop below ends with the k-th PICK, and the k-th vertex's row is scanned behind it
+    // (`last_row`; k = 1: the root's row, the loop is not entered).  Once that vertex is known nothing is selected any more, so the
+    // last pick keeps only the request for its row and its word of SV; the upkeep that serves a further selection is left out:
+    // the shift that drops it from D, the stages' validity (`nvalid`) and `c`, and its kInS flag in the table (the row's scan finds
+    // the members, the vertex itself included, in SV: scan_chunk_last).  Nothing behind the loop reads what is left undone: the row's
+    // outputs come from SV, `size`, `ecount` and the staged hits (nodes row, counts word, stage_flush, the list of unstaged rows; the
+    // fill kernels read those, the plan and the nodes row), and the next walk of this wave resets the whole table, starts from
+    // c = 0 and nvalid = 0 and rebuilds D and the order stages from there.  A walk that stops early (c == 0) or is handed on (an
+    // ADD scan's overflow) leaves the loop before this and is what it was.  The other tiers keep the loop as it was.
+    const bool root_only = STG && k == 1;                                     // the root's row is the last row: no growth step
+    bool last_row = root_only;                                                // set by the last pick, nowhere else
+    for (int step = 0; !root_only; ++step) {
         Grp<GS> g = g_;                                                       // see select_lds: keeps lane-derived constants out of long-lived registers
         if constexpr (GS == 64) asm volatile("" : "+v"(g.lane));
 #ifdef UGS_PAD      // diagnostic A/B builds only (tools/pad_probe.sh): 64 dummy instructions per growth step -- scalar or vector, 4- or 8-byte
@@ -1553,16 +1619,24 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
         }
 #endif
         bool ok;
-        if (step < k - 1) {                                                   // the last vertex adds no candidates
+        if constexpr (STG) {                                                  // every row scanned in the loop adds candidates: the last vertex's follows the loop
             if constexpr (PAD) ok = scan_prow<SP, true, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
             else ok = scan_row<GS, SP, true, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
+            STAMP_END(1);
+            if (!ok) return false;
+            if (c == 0) break;                                                // growth failed: partial row
         } else {
-            if constexpr (PAD) ok = scan_prow<SP, false, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
-            else ok = scan_row<GS, SP, false, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
+            if (step < k - 1) {                                               // the last vertex adds no candidates
+                if constexpr (PAD) ok = scan_prow<SP, true, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
+                else ok = scan_row<GS, SP, true, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
+            } else {
+                if constexpr (PAD) ok = scan_prow<SP, false, STG, UNI>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc);
+                else ok = scan_row<GS, SP, false, STG>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc);
+            }
+            STAMP_END(1);
+            if (!ok) return false;
+            if (step >= k - 1 || c == 0) break;                               // complete, or growth failed: partial row
         }
-        STAMP_END(1);
-        if (!ok) return false;
-        if (step >= k - 1 || c == 0) break;                                   // complete, or growth failed: partial row
         const uint32_t rsel = g.uni(mod64_by<sizeof(typename SP::TW) == 4, sizeof(typename SP::TW) == 4 && GS == 64>(rng.next(), c));
         STAMP_END(4);
         const Pick pick = select_any<GS, MAXPER>(ws, g, c, rsel, nvalid);
@@ -1575,6 +1649,16 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
             r0 = g.uni(r0); r1 = g.uni(r1);
         }
         STAMP_END(2);
+        if constexpr (STG) {
+            if (size + 1u == (uint32_t)k) {                                   // the last pick (wave-uniform; the one test a growth step pays)
+                SV[size] = w;
+                size += 1;
+                v = w;
+                SP::sync();
+                last_row = true;
+                break;
+            }
+        }
         // move w from the candidates to the sample: drop it from D keeping the order of the others.  The LDS tiers' final stage
         // names its position; the global-memory tier searches D.
         uint32_t q = pick.q;
@@ -1680,6 +1764,13 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
         v = w;
         SP::sync();
         STAMP_END(3);
+    }
+    if constexpr (STG) {
+        if (last_row) {                                                       // the sample is complete: the induced entries of its last vertex's row
+            if constexpr (PAD) (void)scan_prow<SP, false, STG, UNI, true>(ws, g, P, v, root_vi, size, c, hcount, ecount, e0, gd.vbase + v, sc, SV);
+            else (void)scan_row<GS, SP, false, STG, true>(ws, g, P.adj, v, root_vi, size, c, hcount, ecount, r0, r1, sc, SV);
+            STAMP_END(1);
+        }
     }
     if constexpr (GS == 64) ecount = g.last(g.prefix_incl(ecount));              // the lanes' counts -> the row's
     const uint32_t nedges = (size == (uint32_t)k) ? ecount : 0u;                // incomplete rows carry no edges (:219-223)

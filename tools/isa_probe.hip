@@ -48,6 +48,17 @@ template <bool ADD, bool GUARD = true, bool SON = false> __global__ __launch_bou
     const bool ok = scan_chunk<64, LdsSpace, ADD, true, GUARD, SON>(pw.ws, g, rsel, c >> 3, 3, cc, hcount, ecount, sc, e, threadIdx.x + 1000u);
     out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + cc + hcount + ecount + sc.ne + (ok ? 1u : 0u);
 }
+// one chunk of the last vertex's row in the compare form (scan_chunk_last) with the per-row load of the members; `size` is a
+// runtime value, so the listing holds the straight eight compares and, on the "cold" row, the loop for k > 8
+template <bool SON> __global__ __launch_bounds__(64, 5) void probe_chunk_last(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel, const int2 *adj, uint2 *stage) {
+    PROBE_PRE
+    StageCtx sc; sc.EL = pw.EL; sc.ne = rsel & 3; sc.on = stage != nullptr; { uint32_t on32 = (uint32_t)__builtin_amdgcn_readfirstlane(sc.on ? 1 : 0); asm volatile("" : "+s"(on32)); sc.onm = 0ull - (uint64_t)on32; }
+    uint32_t ecount = rsel >> 8;
+    int2 e = UGS_NO_ENTRY; if (threadIdx.x < 40) e = adj[threadIdx.x];
+    const uint32_t members = last_row_members(g, pw.SV, c);
+    scan_chunk_last<SON>(g, rsel, c, ecount, sc, (uint32_t)e.x, threadIdx.x + 1000u, members);
+    out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + ecount + sc.ne;
+}
 __global__ __launch_bounds__(64, 5) void probe_draw(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel) {
     PROBE_PRE
     Rng rng; rng.init(((uint64_t)rsel << 32) | c);
@@ -85,4 +96,6 @@ template __global__ void probe_chunk<true, false>(uint32_t *, const uint32_t *, 
 template __global__ void probe_chunk<false, false>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
 template __global__ void probe_chunk<true, false, true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
 template __global__ void probe_chunk<false, false, true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk_last<false>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
+template __global__ void probe_chunk_last<true>(uint32_t *, const uint32_t *, uint32_t, uint32_t, const int2 *, uint2 *);
 }  // namespace
