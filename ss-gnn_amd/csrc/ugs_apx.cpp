@@ -17,6 +17,7 @@
 #include "../../include/ugs_mi355.h"
 
 #include "ugs_apx_common.h"
+#include "ugs_device.h"
 
 #include <random>
 
@@ -224,8 +225,6 @@ class Trials {
 };
 
 }  // namespace
-
-int ugs_internal_fail(int code, const char *msg);      // ugs_host.cpp: sets the message ugs_last_error() returns
 
 extern "C" int ugs_apx_sample_batch(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t ptr_len,
                                     int m_per_graph, int k, uint64_t seed, double epsilon, int64_t *samples_out, int64_t *num_samples_out) {

@@ -14,8 +14,7 @@
 // are dropped, as in the reference.
 #include "../../include/ugs_mi355.h"
 #include "ugs_apx_common.h"
-
-#include <hip/hip_runtime.h>
+#include "ugs_device.h"
 
 #include <algorithm>
 
@@ -187,9 +186,6 @@ struct CounterRng {           // host generator of the APX-DD order: one draw pe
 };
 
 }  // namespace
-
-int ugs_internal_fail(int code, const char *msg);      // ugs_host.cpp: sets the message ugs_last_error() returns
-int ugs_internal_ctx(int *device, hipStream_t *stream);   // ugs_host.cpp: the calling thread's device and stream (ugs_set_device / ugs_set_stream)
 
 extern "C" int ugs_apx_gpu_sample_batch(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t ptr_len,
                                         int m_per_graph, int k, uint64_t seed, double epsilon, int64_t *samples_out, int64_t *num_samples_out,

@@ -303,3 +303,27 @@ struct UgsRwrCall {
 size_t ugs_rwr_cub_bytes(int64_t E);
 hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s);
 hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+
+// ---- epsilon_uniform_sampler (ugs_eps.hip): one launcher for the walk (fill = 0: nodes and per-row counts) and the fill ----
+struct UgsEpsLaunch {
+    const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;
+    int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
+    int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
+    const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
+};
+hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s);
+
+// ---- device-side preprocessing stages (ugs_preproc.hip) ----
+struct UgsDevPre;
+size_t ugs_devpre_bytes(int64_t n, int64_t E);
+hipError_t ugs_devpre_csr(UgsDevPre **out, const int64_t *h_src, const int64_t *h_dst, int64_t E, int64_t n, hipStream_t s, int64_t *h_rowptr, int64_t *nnz_out);
+hipError_t ugs_devpre_roots(UgsDevPre *d, const int32_t *h_order, const int32_t *h_rank, int k, int32_t *h_sdeg, uint8_t *h_reach);
+hipError_t ugs_devpre_download(UgsDevPre *d, int32_t *h_nbr, int32_t *h_col);
+void ugs_devpre_free(UgsDevPre *d);
+void ugs_devpre_trim(UgsDevPre *d);
+size_t ugs_devpre_resident_bytes(const UgsDevPre *d);
+hipError_t ugs_devpre_assemble(UgsDevPre *d, const int64_t *h_colmap, int64_t cols, int2 *adj, int2 *adjf, hipStream_t s);
+
+// ---- what the other translation units take from ugs_host.cpp (internal, not part of the C ABI) ----
+int ugs_internal_fail(int code, const char *msg);            // sets the calling thread's message, the one ugs_last_error() returns; returns code
+int ugs_internal_ctx(int *device, hipStream_t *stream);      // the calling thread's device and stream (ugs_set_device / ugs_set_stream)

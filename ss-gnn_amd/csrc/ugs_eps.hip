@@ -197,13 +197,6 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_fill(EpsArgs a) {
 
 }  // namespace
 
-struct UgsEpsLaunch {
-    const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;
-    int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
-    int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
-    const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
-};
-
 hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s) {
     if (l.rows <= 0) return hipSuccess;
     EpsArgs a;

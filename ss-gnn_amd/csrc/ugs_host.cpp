@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -29,34 +30,13 @@
 struct ugs_plan;
 namespace { void plan_unref(ugs_plan *p); void arena_release(int dev, int64_t roots_off, int64_t n_roots, int64_t via_off, int64_t n_via); void pin_slot_put(char *p); }
 
-// launcher of the epsilon_uniform kernels (ugs_eps.hip)
-struct UgsEpsLaunch {
-    const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;
-    int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
-    int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
-    const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
-};
-hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s);
-
-// device-side preprocessing stages (ugs_preproc.hip)
-struct UgsDevPre;
-size_t ugs_devpre_bytes(int64_t n, int64_t E);
-hipError_t ugs_devpre_csr(UgsDevPre **out, const int64_t *h_src, const int64_t *h_dst, int64_t E, int64_t n, hipStream_t s, int64_t *h_rowptr, int64_t *nnz_out);
-hipError_t ugs_devpre_roots(UgsDevPre *d, const int32_t *h_order, const int32_t *h_rank, int k, int32_t *h_sdeg, uint8_t *h_reach);
-hipError_t ugs_devpre_download(UgsDevPre *d, int32_t *h_nbr, int32_t *h_col);
-void ugs_devpre_free(UgsDevPre *d);
-void ugs_devpre_trim(UgsDevPre *d);
-size_t ugs_devpre_resident_bytes(const UgsDevPre *d);
-hipError_t ugs_devpre_assemble(UgsDevPre *d, const int64_t *h_colmap, int64_t cols, int2 *adj, int2 *adjf, hipStream_t s);
-
 namespace {
 
 thread_local std::string t_err;
 int fail(int code, const std::string &msg) { t_err = msg; return code; }
 }  // namespace
-// the other translation units of the library report through the same thread-local message (internal, not part of the C ABI)
+// the other translation units of the library report through the same thread-local message (ugs_device.h)
 int ugs_internal_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
-int ugs_internal_ctx(int *device, hipStream_t *stream);    // below: the calling thread's device and stream (ugs_set_device / ugs_set_stream)
 namespace {
 int fail_hip(hipError_t e, const char *what) { return fail(UGS_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail_hip(e_, #expr); } while (0)
@@ -2310,12 +2290,16 @@ int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len,
 // ---------------------------------------------------------------------------------------------------------------
 // jobs: the two-phase host-facing API (begin = walks + counts, finish = fill + copy-out)
 // ---------------------------------------------------------------------------------------------------------------
+// What fills a side sampler's edge outputs at finish: edge_index [2, ld] and edge_src [ld] on the device, on the job's stream.
+using JobFill = std::function<hipError_t(int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s)>;
+enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR };
+
 struct ugs_job {
-    ugs_plan *plan = nullptr;
+    ugs_plan *plan = nullptr;          // ugs jobs only
     DeviceCtx dc;
+    int kind = UGS_JOB_UGS;            // which begin made it: the samplers' own *_finish take no other's job
     int m = 0, k = 0, mode = 0;
     int64_t extra = 0, rows = 0, total = 0, G = 0;
-    bool batch = false;
     PoolBuf nodes;                     // nodes [rows, k] and, right behind it, edge_ptr [rows + 1]: one buffer, so that a caller whose
     int64_t *d_eptr = nullptr;         // output tensors are adjacent too gets both with one copy
     // batches of small graphs: begin ran walk + fill as one step (scan folded into the fill) into this staging -- edge_index [2, total]
@@ -2323,20 +2307,11 @@ struct ugs_job {
     bool packed_ok = false;
     // ugs_sample_graphs_begin: the per-graph seed bases, widened; uploaded on the job's stream to the end of `nodes` (begin_common)
     std::vector<uint64_t> seeds;
-    // epsilon_uniform path
-    bool eps = false;
-    PoolBuf eps_blob;                  // pooled: hipMalloc/hipFree per call cost milliseconds once the process holds large plans
-    UgsEpsLaunch eps_l{};
-    PoolBuf eps_counts, eps_scantmp;
-    // uniform_sampler path (ugs_uniform.hip): the call's device arrays in one pooled blob; finish runs uni_fill from them
-    bool uni = false;
-    PoolBuf uni_blob;
-    UgsUniCall uni_c{};
-    UgsUniWide uni_w{};    // the call's wide graphs (none: nv_mask == nv)
-    // rwr_sampler path (ugs_rwr.hip): the same, finish runs rwr_fill
-    bool rwr = false;
-    PoolBuf rwr_blob;
-    UgsRwrCall rwr_c{};
+    // the side samplers (epsilon_uniform, uniform, rwr): the call's device arrays -- inputs, then the scratch of
+    // every stage -- in one pooled blob (hipMalloc/hipFree per call cost milliseconds once the process holds large plans), and the fill
+    // that finish runs from them.  The hook holds the sampler's call struct by value; empty: the job fills through its plan.
+    PoolBuf blob;
+    JobFill fill;
 };
 
 namespace {
@@ -2344,12 +2319,14 @@ std::atomic<int64_t> g_spec_kept{0}, g_spec_wrong{0};              // large call
 void free_job(ugs_job *j) {
     if (!j) return;
     pool_put(j->nodes);
-    pool_put(j->eps_counts); pool_put(j->eps_scantmp);
-    pool_put(j->eps_blob);
-    pool_put(j->uni_blob);
-    pool_put(j->rwr_blob);
+    pool_put(j->blob);
     plan_unref(j->plan);
     delete j;
+}
+int hand_out(ugs_job *j, ugs_job **job_out, int64_t *total_out) {
+    *job_out = j;
+    if (total_out) *total_out = j->total;
+    return UGS_OK;
 }
 
 // second launch of a job's step (see begin_common): ugs_fill_scan into the job's staging, total through the pinned slot of the plan.
@@ -2396,12 +2373,12 @@ int packed_fill_locked(ugs_job *j, int64_t cap3) {
 }
 
 // seeds (ugs_sample_graphs_begin): plan->G per-graph seeds that replace `seed`; nullptr: one seed for the call
-int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed, bool batch, ugs_job **job_out, int64_t *total_out,
+int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed, ugs_job **job_out, int64_t *total_out,
                  const int32_t *seeds = nullptr) {
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) { plan_unref(plan); return rc; }
     auto *j = new ugs_job();
-    j->plan = plan; j->dc = dc; j->m = m; j->k = k; j->mode = mode; j->extra = extra; j->batch = batch;
+    j->plan = plan; j->dc = dc; j->m = m; j->k = k; j->mode = mode; j->extra = extra;
     j->G = plan->G;
     j->rows = plan->G * (int64_t)m;
     // (a job that may run the packed step keeps its edge staging right behind nodes and edge_ptr: all four outputs leave in ONE copy when
@@ -2445,9 +2422,7 @@ int begin_common(ugs_plan *plan, int m, int k, int mode, int64_t extra, int seed
         }
     }
     if (rc) { free_job(j); return rc; }
-    *job_out = j;
-    if (total_out) *total_out = j->total;
-    return UGS_OK;
+    return hand_out(j, job_out, total_out);
 }
 
 int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr, int64_t *edge_src, int dst_is_device) {
@@ -2464,21 +2439,11 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
             if (int r = pool_get((size_t)(3 * tot) * sizeof(int64_t), j->dc.id, e_idx)) return r;
             d_ei = static_cast<int64_t *>(e_idx.p); d_es = d_ei + 2 * tot;
         }
-        if (tot > 0 && j->eps) {
+        if (tot > 0 && !packed) {                                   // (a side sampler's job is never packed)
             if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
-            UgsEpsLaunch l = j->eps_l;
-            l.edge_ptr = j->d_eptr; l.edge_index = d_ei; l.edge_src = d_es; l.ld = tot;
-            HIP_TRY(ugs_eps_launch(l, 1, j->dc.cus, s));
-        } else if (tot > 0 && j->uni) {
-            if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
-            HIP_TRY(ugs_uniform_fill(j->uni_c, j->uni_w, d_ei, d_es, tot, s));
-        } else if (tot > 0 && j->rwr) {
-            if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
-            HIP_TRY(ugs_rwr_fill(j->rwr_c, d_ei, d_es, tot, s));
-        } else if (tot > 0 && !packed) {
-            if (!d_ei || !d_es) return fail(UGS_E_BAD_ARG, "null edge output pointer");
-            if (int r = ugs_plan_fill(j->plan, j->m, j->k, j->mode, j->extra, 0, rows, s, static_cast<const int64_t *>(j->nodes.p),
-                                      j->d_eptr, d_ei, tot, d_es)) return r;
+            if (j->fill) HIP_TRY(j->fill(d_ei, d_es, tot, s));
+            else if (int r = ugs_plan_fill(j->plan, j->m, j->k, j->mode, j->extra, 0, rows, s, static_cast<const int64_t *>(j->nodes.p),
+                                           j->d_eptr, d_ei, tot, d_es)) return r;
         }
         const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         // adjacent outputs (the Python shim carves its tensors out of one allocation) travel in one copy each -- or all in one
@@ -2517,6 +2482,73 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
     free_job(j);
     return rc;
 }
+
+// ---- what the begins of the side samplers share (eps_begin, uniform_begin, rwr_begin below) ----
+// Layout of a job's blob: pieces in the order they are taken, each at a multiple of 256 bytes.  The inputs come first, so that they
+// go up in one copy of in_bytes; the scratch of every stage follows.
+struct BlobLayout {
+    size_t off = 0, in_bytes = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; }
+    void end_inputs() { in_bytes = off; }
+};
+
+// The inputs of a sampler that reads the batch itself: both edge rows, ptr, one descriptor per graph and (sample_graphs) the seeds.
+struct BatchInputs {
+    size_t src, dst, ptr, desc, seeds;
+    BatchInputs(BlobLayout &L, int64_t E, int64_t G, size_t desc_bytes, bool per_graph)
+        : src(L.take((size_t)E * 8)), dst(L.take((size_t)E * 8)), ptr(L.take((size_t)(G + 1) * 8)), desc(L.take((size_t)G * desc_bytes)),
+          seeds(L.take(per_graph ? (size_t)G * 8 : 0)) {}
+    void stage(char *host, const int64_t *edge_index, int64_t row_stride, int64_t E, const int64_t *ptr_in, int64_t G, const void *descs,
+               size_t desc_bytes, const uint64_t *seeds_in) const {
+        for (int64_t e = 0; e < E; ++e) {
+            reinterpret_cast<int64_t *>(host + src)[e] = edge_index[e];
+            reinterpret_cast<int64_t *>(host + dst)[e] = edge_index[row_stride + e];
+        }
+        std::memcpy(host + ptr, ptr_in, (size_t)(G + 1) * 8);
+        if (G > 0) std::memcpy(host + desc, descs, (size_t)G * desc_bytes);
+        if (seeds_in && G > 0) std::memcpy(host + seeds, seeds_in, (size_t)G * 8);
+    }
+};
+
+// The ptr scan of such a sampler.  ptr must not decrease.  `each(g, n, why)` writes graph g's descriptor and says whether the sampler
+// cannot take the graph, leaving the refusal's text in `why`: sample_batch refuses the call with it, sample_graphs lets the graph fail
+// alone (too_big[g] = 1: m rows of -1, no draws).
+template <class Each>
+int scan_ptr(const int64_t *ptr, int64_t G, bool per_graph, std::vector<int32_t> &too_big, Each each) {
+    too_big.assign(per_graph ? (size_t)G : 0, 0);
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t n = ptr[g + 1] - ptr[g];
+        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
+        std::string why;
+        if (!each(g, n, why)) continue;
+        if (!per_graph) return fail(UGS_E_UNSUPPORTED, why);
+        too_big[(size_t)g] = 1;
+    }
+    return UGS_OK;
+}
+
+// The job of a side sampler: its parameters, its blob, and nodes [rows, k] with edge_ptr [rows + 1] right behind it.
+int side_job(const DeviceCtx &dc, int kind, int64_t G, int m, int k, int mode, size_t blob_bytes, ugs_job **out) {
+    auto *j = new ugs_job();
+    j->dc = dc; j->kind = kind; j->m = m; j->k = k; j->mode = mode; j->G = G; j->rows = G * (int64_t)m;
+    int rc = pool_get(blob_bytes, dc.id, j->blob);
+    if (!rc) rc = pool_get((size_t)(j->rows * k + j->rows + 1) * sizeof(int64_t), dc.id, j->nodes);
+    if (rc) { free_job(j); return rc; }
+    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + j->rows * k;
+    *out = j;
+    return UGS_OK;
+}
+
+// The end of such a begin.  `e` is the outcome of everything the sampler has queued on the job's stream since side_job (upload, kernels,
+// read-backs of its own): the total follows them to the host, the stream is drained, and a HIP error of any of it is reported as
+// `what`.  On failure the job is gone.
+int side_job_total(ugs_job *j, hipError_t e, const char *what) {
+    if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + j->rows, sizeof(int64_t), hipMemcpyDeviceToHost, j->dc.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(j->dc.stream);
+    if (e == hipSuccess) return UGS_OK;
+    free_job(j);
+    return fail_hip(e, what);
+}
 }  // namespace
 
 extern "C" {
@@ -2530,7 +2562,7 @@ int ugs_sample_begin(int64_t handle, int m_per_graph, int k, int edge_mode, int6
     if (g->n == 0) return fail(UGS_E_NO_ROOTS, "No viable roots available");
     ugs_plan *plan = nullptr;
     if (int rc = ugs_plan_create_handle(handle, &plan)) return rc;
-    return begin_common(plan, m_per_graph, k, edge_mode, edge_mode == UGS_EDGE_GLOBAL ? base_offset : 0, seed, false, job_out, total_edges_out);
+    return begin_common(plan, m_per_graph, k, edge_mode, edge_mode == UGS_EDGE_GLOBAL ? base_offset : 0, seed, job_out, total_edges_out);
 }
 
 int ugs_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *edge_src, int dst_is_device) {
@@ -2568,19 +2600,19 @@ int ugs_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_
         } catch (...) { plan_unref(guess); guess = nullptr; }          // no thread to be had: look up first, as without a guess
         if (!guess) {
             if (int rc = ugs_plan_create_batch(edge_index, row_stride, num_cols, ptr, num_graphs, k, &plan)) return rc;
-            return begin_common(plan, m_per_graph, k, mode, 0, seed, true, job_out, total_edges_out);
+            return begin_common(plan, m_per_graph, k, mode, 0, seed, job_out, total_edges_out);
         }
         *job_out = nullptr;
-        const int rc = begin_common(guess, m_per_graph, k, mode, 0, seed, true, job_out, total_edges_out);   // (owns the guess's reference)
+        const int rc = begin_common(guess, m_per_graph, k, mode, 0, seed, job_out, total_edges_out);   // (owns the guess's reference)
         lookup_thread.join();
         if (lookup_rc != UGS_OK) { if (rc == UGS_OK) { free_job(*job_out); *job_out = nullptr; } return fail(lookup_rc, lookup_err); }
         if (plan == guess) { plan_unref(plan); g_spec_kept.fetch_add(1); return rc; }
         if (rc == UGS_OK) { free_job(*job_out); *job_out = nullptr; }                       // a different batch after all: once more, on its plan
         g_spec_wrong.fetch_add(1);
-        return begin_common(plan, m_per_graph, k, mode, 0, seed, true, job_out, total_edges_out);
+        return begin_common(plan, m_per_graph, k, mode, 0, seed, job_out, total_edges_out);
     }
     if (int rc = ugs_plan_create_batch(edge_index, row_stride, num_cols, ptr, num_graphs, k, &plan)) return rc;
-    return begin_common(plan, m_per_graph, k, mode, 0, seed, true, job_out, total_edges_out);
+    return begin_common(plan, m_per_graph, k, mode, 0, seed, job_out, total_edges_out);
 }
 
 // sample_batch with one seed per graph: the same plan lookup (LRU replay, device batch pass) and the same job; the seeds go to the
@@ -2595,7 +2627,7 @@ int ugs_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64
     if (num_graphs > 0 && !seeds) return fail(UGS_E_BAD_ARG, "sample_graphs needs one seed per graph");
     ugs_plan *plan = nullptr;
     if (int rc = ugs_plan_create_batch(edge_index, row_stride, num_cols, ptr, num_graphs, k, &plan)) return rc;
-    return begin_common(plan, m_per_graph, k, mode, 0, 0, true, job_out, total_edges_out, num_graphs > 0 ? seeds : nullptr);
+    return begin_common(plan, m_per_graph, k, mode, 0, 0, job_out, total_edges_out, num_graphs > 0 ? seeds : nullptr);
 }
 
 int ugs_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
@@ -2806,13 +2838,14 @@ static int eps_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
     int64_t nrows = 0, nnz = 2 * (int64_t)cols_of.size();
     for (int64_t g = 0; g < G; ++g) nrows += std::max<int64_t>(ptr[g + 1] - ptr[g], 0) + 1;
     if (nnz >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large");
-    size_t off_desc = 0;
-    size_t off_row = align_up(off_desc + (size_t)std::max<int64_t>(G, 1) * sizeof(UgsGraphDesc));
-    size_t off_nbr = align_up(off_row + (size_t)std::max<int64_t>(nrows, 1) * sizeof(int64_t));
-    size_t off_ecs = align_up(off_nbr + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
-    size_t off_seeds = align_up(off_ecs + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
-    size_t total = seeds ? align_up(off_seeds + (size_t)std::max<int64_t>(G, 1) * sizeof(uint64_t)) : off_seeds;
-    std::vector<char> host(total, 0);
+    const int64_t rows = G * (int64_t)m_per_graph;
+    BlobLayout L;
+    const size_t off_desc = L.take((size_t)G * sizeof(UgsGraphDesc)), off_row = L.take((size_t)nrows * sizeof(int64_t)),
+                 off_nbr = L.take((size_t)nnz * sizeof(int32_t)), off_ecs = L.take((size_t)nnz * sizeof(int32_t)),
+                 off_seeds = L.take(seeds ? (size_t)G * sizeof(uint64_t) : 0);
+    L.end_inputs();
+    const size_t off_counts = L.take((size_t)rows * sizeof(uint32_t)), off_st = L.take((size_t)ugs_scan_tmp_words(rows) * sizeof(int64_t));
+    std::vector<char> host(L.in_bytes, 0);
     if (seeds && G > 0) std::memcpy(host.data() + off_seeds, seeds, (size_t)G * sizeof(uint64_t));
     auto *desc = reinterpret_cast<UgsGraphDesc *>(host.data() + off_desc);
     auto *rowp = reinterpret_cast<int64_t *>(host.data() + off_row);
@@ -2838,19 +2871,10 @@ static int eps_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
         for (int64_t r = 0; r <= n; ++r) rowp[rb + r] += ab;
         rb += n + 1; ab += 2 * cn;
     }
-    auto *j = new ugs_job();
-    j->dc = dc; j->eps = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G;
-    j->rows = G * (int64_t)m_per_graph;
-    auto bail = [&](int rc) { free_job(j); return rc; };
-    if (int rc = pool_get(total, dc.id, j->eps_blob)) return bail(rc);
-    hipError_t e = hipMemcpy(j->eps_blob.p, host.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(fail_hip(e, "hipMemcpy"));
-    char *base = static_cast<char *>(j->eps_blob.p);
-    if (int rc = pool_get((size_t)(j->rows * k + j->rows + 1) * sizeof(int64_t), dc.id, j->nodes)) return bail(rc);
-    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + j->rows * k;
-    if (int rc = pool_get((size_t)std::max<int64_t>(j->rows, 1) * sizeof(uint32_t), dc.id, j->eps_counts)) return bail(rc);
-    if (int rc = pool_get((size_t)ugs_scan_tmp_words(j->rows) * sizeof(int64_t), dc.id, j->eps_scantmp)) return bail(rc);
-    UgsEpsLaunch &l = j->eps_l;
+    ugs_job *j = nullptr;
+    if (int rc = side_job(dc, UGS_JOB_EPS, G, m_per_graph, k, mode, L.off, &j)) return rc;
+    char *base = static_cast<char *>(j->blob.p);
+    UgsEpsLaunch l{};
     l.graphs = reinterpret_cast<const UgsGraphDesc *>(base + off_desc);
     l.rowptr = reinterpret_cast<const int64_t *>(base + off_row);
     l.nbr = reinterpret_cast<const int32_t *>(base + off_nbr);
@@ -2858,19 +2882,18 @@ static int eps_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
     l.num_graphs = G; l.m = m_per_graph; l.k = k; l.mode = mode;
     l.max_attempts = std::max(10, (int)(10.0 / epsilon));
     l.seed = seed; l.seeds = seeds ? reinterpret_cast<const uint64_t *>(base + off_seeds) : nullptr;
-    l.epsilon = epsilon; l.rows = j->rows;
-    l.nodes = static_cast<int64_t *>(j->nodes.p); l.counts = static_cast<uint32_t *>(j->eps_counts.p);
-    l.edge_ptr = nullptr; l.edge_index = nullptr; l.edge_src = nullptr; l.ld = 0;
-    e = ugs_eps_launch(l, 0, dc.cus, dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "ugs_eps_walk"));
-    e = ugs_launch_scan(l.counts, j->rows, j->d_eptr, static_cast<int64_t *>(j->eps_scantmp.p), dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "ugs_launch_scan"));
-    e = hipMemcpyAsync(&j->total, j->d_eptr + j->rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "epsilon walk"));
-    *job_out = j;
-    if (total_edges_out) *total_edges_out = j->total;
-    return UGS_OK;
+    l.epsilon = epsilon; l.rows = rows;
+    l.nodes = static_cast<int64_t *>(j->nodes.p); l.counts = reinterpret_cast<uint32_t *>(base + off_counts);
+    hipError_t e = hipMemcpyAsync(base, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (e == hipSuccess) e = ugs_eps_launch(l, 0, dc.cus, dc.stream);
+    if (e == hipSuccess) e = ugs_launch_scan(l.counts, rows, j->d_eptr, reinterpret_cast<int64_t *>(base + off_st), dc.stream);
+    if (int rc = side_job_total(j, e, "epsilon walk")) return rc;
+    j->fill = [l, d_eptr = j->d_eptr, cus = dc.cus](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {
+        UgsEpsLaunch f = l;
+        f.edge_ptr = d_eptr; f.edge_index = edge_index; f.edge_src = edge_src; f.ld = ld;
+        return ugs_eps_launch(f, 1, cus, s);
+    };
+    return hand_out(j, job_out, total_edges_out);
 }
 
 int ugs_eps_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
@@ -2890,7 +2913,7 @@ int ugs_eps_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, i
 
 int ugs_eps_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                 int64_t *edge_src, int dst_is_device) {
-    if (!job || !job->eps) return fail(UGS_E_BAD_ARG, "not an epsilon job");
+    if (!job || job->kind != UGS_JOB_EPS) return fail(UGS_E_BAD_ARG, "not an epsilon job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 
@@ -2958,33 +2981,27 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     int max_vertices = 64, mask_vertices = 64;                          // the limits in force for this call
     uniform_limits(&max_vertices, &mask_vertices);
     std::vector<UgsUniGraph> gd((size_t)G);
-    std::vector<int32_t> too_big(per_graph ? (size_t)G : 0, 0);
+    std::vector<int32_t> too_big;
     int64_t nv = 0, nv_wide = 0, adj_words = 0;
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t n = ptr[g + 1] - ptr[g];
-        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
-        const bool wanted = k >= 1 && n >= k;
-        int b = 1;                                                      // field width of the wide key: bit length of n - 1
-        while (b < 62 && ((int64_t)1 << b) < n) ++b;
-        const bool key_fits = k <= UGS_UNI_WIDE_MAX_K && (int64_t)k * b <= 64;
-        const bool over = wanted && n > 64 && (n > max_vertices || !key_fits);
-        if (over && !per_graph) {
-            if (n > max_vertices)
-                return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
-                                               " vertices; graphs of more than " + std::to_string(max_vertices) +
-                                               " vertices (and at least k) are not supported");
-            return fail(UGS_E_UNSUPPORTED, "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
-                                           " vertices; a graph of more than 64 vertices (limit in force: " + std::to_string(max_vertices) +
-                                           ") needs k <= 8 and k * b <= 64, b = the bit length of n - 1 (here k = " + std::to_string(k) +
-                                           ", b = " + std::to_string(b) + ")");
-        }
-        if (over) too_big[(size_t)g] = 1;                               // per-graph: m rows of -1, no draws
-        UgsUniGraph &d = gd[(size_t)g];
-        d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = 0;
-        d.enumerable = !wanted || over ? 0 : n > 64 || (n > mask_vertices && key_fits) ? 2 : 1;
-        if (d.enumerable == 1) { d.vbase = nv; nv += n; }
-        if (d.enumerable == 2) nv_wide += n;
-    }
+    if (int rc = scan_ptr(ptr, G, per_graph, too_big, [&](int64_t g, int64_t n, std::string &why) {
+            const bool wanted = k >= 1 && n >= k;
+            int b = 1;                                                  // field width of the wide key: bit length of n - 1
+            while (b < 62 && ((int64_t)1 << b) < n) ++b;
+            const bool key_fits = k <= UGS_UNI_WIDE_MAX_K && (int64_t)k * b <= 64;
+            const bool over = wanted && n > 64 && (n > max_vertices || !key_fits);
+            if (over)
+                why = "uniform_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
+                      (n > max_vertices ? " vertices; graphs of more than " + std::to_string(max_vertices) + " vertices (and at least k) are not supported"
+                                        : " vertices; a graph of more than 64 vertices (limit in force: " + std::to_string(max_vertices) +
+                                              ") needs k <= 8 and k * b <= 64, b = the bit length of n - 1 (here k = " + std::to_string(k) +
+                                              ", b = " + std::to_string(b) + ")");
+            UgsUniGraph &d = gd[(size_t)g];
+            d.lo = ptr[g]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX); d.vbase = 0;
+            d.enumerable = !wanted || over ? 0 : n > 64 || (n > mask_vertices && key_fits) ? 2 : 1;
+            if (d.enumerable == 1) { d.vbase = nv; nv += n; }
+            if (d.enumerable == 2) nv_wide += n;
+            return over;
+        })) return rc;
     // the enumerated vertices: the mask graphs' first, the wide graphs' after them
     const int64_t nv_mask = nv;
     std::vector<int64_t> wbase(nv_wide > 0 ? (size_t)G : 0, -1);
@@ -2998,12 +3015,12 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     if (int rc = device_ctx(dc)) return rc;
     const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? UGS_UNI_BUDGET : 0;
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
-    const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
-                 o_gd = take((size_t)G * sizeof(UgsUniGraph)), o_vg = take((size_t)nv * 4), o_seeds = take(per_graph ? (size_t)G * 8 : 0);
+    BlobLayout L;
+    auto take = [&](size_t bytes) { return L.take(bytes); };
+    const BatchInputs in(L, E, G, sizeof(UgsUniGraph), per_graph);
     const bool wide = nv_wide > 0;                                      // a call without wide graphs allocates nothing for them
-    const size_t o_wb = wide ? take((size_t)G * 8) : 0, in_bytes = off;
+    const size_t o_vg = take((size_t)nv * 4), o_wb = wide ? take((size_t)G * 8) : 0;
+    L.end_inputs();
     const size_t o_wadj = wide ? take((size_t)adj_words * 8) : 0, o_wp = wide ? take((size_t)E * 4) : 0, o_gzm = wide ? take((size_t)G * 8) : 0,
                  o_rk = wide ? take((size_t)rows * 8) : 0;
     const size_t o_gc = take(per_graph ? (size_t)G * 8 : 0);
@@ -3014,32 +3031,23 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
                  o_st = take((size_t)ugs_scan_tmp_words(std::max(items, rows)) * 8), o_sl = take((size_t)nv * 4), o_sh = take((size_t)nv * 4),
                  o_ka = take((size_t)budget * 8), o_kb = take((size_t)budget * 8), o_gs = take((size_t)G * 8), o_gz = take((size_t)G * 8),
                  o_np = take((size_t)G * 4), o_nl = take((size_t)G * 4), o_dr = take((size_t)rows * 4), o_rm = take((size_t)rows * 8),
-                 o_ec = take((size_t)rows * 4), o_status = take(4 * 8), total = off;
-    std::vector<char> host(in_bytes, 0);
-    for (int64_t e = 0; e < E; ++e) {
-        reinterpret_cast<int64_t *>(host.data() + o_src)[e] = edge_index[e];
-        reinterpret_cast<int64_t *>(host.data() + o_dst)[e] = edge_index[row_stride + e];
-    }
-    std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
-    if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsUniGraph));
-    if (per_graph && G > 0) std::memcpy(host.data() + o_seeds, seeds, (size_t)G * 8);
+                 o_ec = take((size_t)rows * 4), o_status = take(4 * 8);
+    std::vector<char> host(L.in_bytes, 0);
+    in.stage(host.data(), edge_index, row_stride, E, ptr, G, gd.data(), sizeof(UgsUniGraph), per_graph ? seeds : nullptr);
     if (wide) std::memcpy(host.data() + o_wb, wbase.data(), (size_t)G * 8);
     auto *vg = reinterpret_cast<int32_t *>(host.data() + o_vg);
     for (int64_t g = 0; g < G; ++g)
         if (gd[(size_t)g].enumerable) for (int32_t v = 0; v < gd[(size_t)g].n; ++v) vg[gd[(size_t)g].vbase + v] = (int32_t)g;
-    auto *j = new ugs_job();
-    j->dc = dc; j->uni = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G; j->rows = rows;
+    ugs_job *j = nullptr;
+    if (int rc = side_job(dc, UGS_JOB_UNIFORM, G, m_per_graph, k, mode, L.off, &j)) return rc;
     auto bail = [&](int rc) { free_job(j); return rc; };
-    if (int rc = pool_get(total, dc.id, j->uni_blob)) return bail(rc);
-    if (int rc = pool_get((size_t)(rows * k + rows + 1) * sizeof(int64_t), dc.id, j->nodes)) return bail(rc);
-    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + rows * k;
-    char *b = static_cast<char *>(j->uni_blob.p);
-    UgsUniCall &c = j->uni_c;
+    char *b = static_cast<char *>(j->blob.p);
+    UgsUniCall c{};
     c.G = G; c.E = E; c.nv = nv; c.rows = rows; c.budget = budget; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
-    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + o_seeds) : nullptr;
+    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
     c.gcount = per_graph ? reinterpret_cast<int64_t *>(b + o_gc) : nullptr;
-    c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
-    c.ptr = reinterpret_cast<const int64_t *>(b + o_ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + o_gd);
+    c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
+    c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + in.desc);
     c.vgraph = reinterpret_cast<const int32_t *>(b + o_vg);
     c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
     c.ckey = reinterpret_cast<uint32_t *>(b + o_ck); c.ckey2 = reinterpret_cast<uint32_t *>(b + o_ck2);
@@ -3054,23 +3062,20 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     c.draws = reinterpret_cast<int32_t *>(b + o_dr); c.rowmask = reinterpret_cast<uint64_t *>(b + o_rm);
     c.ecount = reinterpret_cast<uint32_t *>(b + o_ec); c.status = reinterpret_cast<int64_t *>(b + o_status);
     c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
-    UgsUniWide &w = j->uni_w;
+    UgsUniWide w{};
     w.nv_mask = nv_mask; w.adj_words = adj_words;
     if (wide) {
         w.wbase = reinterpret_cast<const int64_t *>(b + o_wb); w.wadj = reinterpret_cast<uint64_t *>(b + o_wadj);
         w.wpair = reinterpret_cast<uint32_t *>(b + o_wp); w.gsize_mask = reinterpret_cast<int64_t *>(b + o_gzm);
         w.rowkey = reinterpret_cast<uint64_t *>(b + o_rk);
     }
-    hipError_t e = hipMemcpyAsync(b, host.data(), in_bytes, hipMemcpyHostToDevice, dc.stream);
-    if (e == hipSuccess) e = ugs_uniform_begin(c, w, dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
     int64_t status[4] = {0, 0, 0, 0};
     std::vector<int64_t> gcount(per_graph && nv > 0 ? (size_t)G : 0, 0);   // per-graph subset counts: read back once, with the total
-    e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
+    hipError_t e = hipMemcpyAsync(b, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (e == hipSuccess) e = ugs_uniform_begin(c, w, dc.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
     if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
+    if (int rc = side_job_total(j, e, "uniform_sampler pipeline")) return rc;
     if (status[1] && per_graph)
         return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the call's graphs together have " + std::to_string(status[0]) +
                                             " connected k-subsets, more than the device budget of " + std::to_string(budget) +
@@ -3080,9 +3085,8 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
                                             " connected k-subsets (the device budget; " + std::to_string(status[0]) + " counted before stopping)"));
     for (int64_t g = 0; per_graph && g < G; ++g)
         graph_status[g] = too_big[(size_t)g] || (!gcount.empty() && gd[(size_t)g].enumerable && gcount[(size_t)g] > budget) ? 1 : 0;
-    *job_out = j;
-    if (total_edges_out) *total_edges_out = j->total;
-    return UGS_OK;
+    j->fill = [c, w](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_uniform_fill(c, w, edge_index, edge_src, ld, s); };
+    return hand_out(j, job_out, total_edges_out);
 }
 
 int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
@@ -3103,7 +3107,7 @@ int ugs_uniform_sample_graphs_begin(const int64_t *edge_index, int64_t row_strid
 
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device) {
-    if (!job || !job->uni) return fail(UGS_E_BAD_ARG, "not a uniform_sampler job");
+    if (!job || job->kind != UGS_JOB_UNIFORM) return fail(UGS_E_BAD_ARG, "not a uniform_sampler job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 
@@ -3124,56 +3128,42 @@ static int rwr_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
     const int64_t G = num_graphs, E = num_cols;
     if (per_graph && G >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
     std::vector<UgsRwrGraph> gd((size_t)G);
-    std::vector<int32_t> too_big(per_graph ? (size_t)G : 0, 0);
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t n = ptr[g + 1] - ptr[g];
-        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
-        const bool over = n >= k && n > (int64_t)INT32_MAX / (10 * (int64_t)k);
-        if (over && !per_graph)
-            return fail(UGS_E_UNSUPPORTED, "rwr_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) +
-                                           " vertices; 10 n k must fit the reference's int iteration limit");
-        if (over) too_big[(size_t)g] = 1;                               // per-graph: T = 0, m rows of -1 and no draws
-        UgsRwrGraph &d = gd[(size_t)g];
-        d.lo = ptr[g]; d.vbase = ptr[g] - ptr[0]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX);
-        d.T = n >= k && !over ? (int32_t)(n * k * 10) : 0;
-    }
+    std::vector<int32_t> too_big;
+    if (int rc = scan_ptr(ptr, G, per_graph, too_big, [&](int64_t g, int64_t n, std::string &why) {
+            const bool over = n >= k && n > (int64_t)INT32_MAX / (10 * (int64_t)k);
+            if (over) why = "rwr_sampler: graph " + std::to_string(g) + " has " + std::to_string(n) + " vertices; 10 n k must fit the reference's int iteration limit";
+            UgsRwrGraph &d = gd[(size_t)g];
+            d.lo = ptr[g]; d.vbase = ptr[g] - ptr[0]; d.n = (int32_t)std::min<int64_t>(n, INT32_MAX);
+            d.T = n >= k && !over ? (int32_t)(n * k * 10) : 0;          // (T = 0: m rows of -1 and no draws)
+            return over;
+        })) return rc;
     const int64_t NV = G > 0 ? ptr[G] - ptr[0] : 0;
     if (NV >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: vertices must be < 2^31 - 1");
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
     const int64_t rows = G * (int64_t)m_per_graph;
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 8)); return o; };
-    const size_t o_src = take((size_t)E * 8), o_dst = take((size_t)E * 8), o_ptr = take((size_t)(G + 1) * 8),
-                 o_gd = take((size_t)G * sizeof(UgsRwrGraph)), o_seeds = take(per_graph ? (size_t)G * 8 : 0), in_bytes = off;
+    BlobLayout L;
+    auto take = [&](size_t bytes) { return L.take(bytes); };
+    const BatchInputs in(L, E, G, sizeof(UgsRwrGraph), per_graph);
+    L.end_inputs();
     const size_t cub_bytes = ugs_rwr_cub_bytes(E);
     const size_t o_cub = take(cub_bytes), o_hk = take((size_t)E * 8), o_hk2 = take((size_t)E * 8), o_hv = take((size_t)E * 8),
                  o_hv2 = take((size_t)E * 8), o_rs = take((size_t)(NV + 1) * 4), o_par = take((size_t)NV * 4), o_cs = take((size_t)NV * 4),
                  o_dm = take((size_t)NV), o_rst = take((size_t)rows * 8), o_ec = take((size_t)rows * 4),
-                 o_st = take((size_t)ugs_scan_tmp_words(rows) * 8), total = off;
-    std::vector<char> host(in_bytes, 0);
-    for (int64_t e = 0; e < E; ++e) {
-        reinterpret_cast<int64_t *>(host.data() + o_src)[e] = edge_index[e];
-        reinterpret_cast<int64_t *>(host.data() + o_dst)[e] = edge_index[row_stride + e];
-    }
-    std::memcpy(host.data() + o_ptr, ptr, (size_t)(G + 1) * 8);
-    if (G > 0) std::memcpy(host.data() + o_gd, gd.data(), (size_t)G * sizeof(UgsRwrGraph));
-    if (per_graph && G > 0) std::memcpy(host.data() + o_seeds, seeds, (size_t)G * 8);
-    auto *j = new ugs_job();
-    j->dc = dc; j->rwr = true; j->batch = true; j->m = m_per_graph; j->k = k; j->mode = mode; j->G = G; j->rows = rows;
-    auto bail = [&](int rc) { free_job(j); return rc; };
-    if (int rc = pool_get(total, dc.id, j->rwr_blob)) return bail(rc);
-    if (int rc = pool_get((size_t)(rows * k + rows + 1) * sizeof(int64_t), dc.id, j->nodes)) return bail(rc);
-    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + rows * k;
-    char *b = static_cast<char *>(j->rwr_blob.p);
-    UgsRwrCall &c = j->rwr_c;
+                 o_st = take((size_t)ugs_scan_tmp_words(rows) * 8);
+    std::vector<char> host(L.in_bytes, 0);
+    in.stage(host.data(), edge_index, row_stride, E, ptr, G, gd.data(), sizeof(UgsRwrGraph), per_graph ? seeds : nullptr);
+    ugs_job *j = nullptr;
+    if (int rc = side_job(dc, UGS_JOB_RWR, G, m_per_graph, k, mode, L.off, &j)) return rc;
+    char *b = static_cast<char *>(j->blob.p);
+    UgsRwrCall c{};
     c.G = G; c.E = E; c.NV = NV; c.rows = rows; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed; c.p = p_restart;
-    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + o_seeds) : nullptr;
+    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
     // speculation window: room for about 16 draws per wanted walk, 1 to 4 offsets per lane
     c.spec = (int32_t)std::min<int64_t>(4, std::max<int64_t>(1, ((int64_t)m_per_graph * 16 + 255) / 256));
-    c.src = reinterpret_cast<const int64_t *>(b + o_src); c.dst = reinterpret_cast<const int64_t *>(b + o_dst);
-    c.ptr = reinterpret_cast<const int64_t *>(b + o_ptr); c.graphs = reinterpret_cast<const UgsRwrGraph *>(b + o_gd);
+    c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
+    c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsRwrGraph *>(b + in.desc);
     c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
     c.hkey = reinterpret_cast<uint32_t *>(b + o_hk); c.hkey2 = reinterpret_cast<uint32_t *>(b + o_hk2);
     c.hval = reinterpret_cast<int32_t *>(b + o_hv); c.hval2 = reinterpret_cast<int32_t *>(b + o_hv2);
@@ -3182,15 +3172,12 @@ static int rwr_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
     c.rstart = reinterpret_cast<int64_t *>(b + o_rst); c.ecount = reinterpret_cast<uint32_t *>(b + o_ec);
     c.scan_tmp = reinterpret_cast<int64_t *>(b + o_st);
     c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
-    hipError_t e = hipMemcpyAsync(b, host.data(), in_bytes, hipMemcpyHostToDevice, dc.stream);
+    hipError_t e = hipMemcpyAsync(b, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
     if (e == hipSuccess) e = ugs_rwr_begin(c, dc.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&j->total, j->d_eptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, dc.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
-    if (e != hipSuccess) return bail(fail_hip(e, "rwr_sampler pipeline"));
+    if (int rc = side_job_total(j, e, "rwr_sampler pipeline")) return rc;
     for (int64_t g = 0; per_graph && g < G; ++g) graph_status[g] = too_big[(size_t)g];
-    *job_out = j;
-    if (total_edges_out) *total_edges_out = j->total;
-    return UGS_OK;
+    j->fill = [c](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_rwr_fill(c, edge_index, edge_src, ld, s); };
+    return hand_out(j, job_out, total_edges_out);
 }
 
 int ugs_rwr_sample_batch_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
@@ -3212,7 +3199,7 @@ int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, i
 
 int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                 int64_t *edge_src, int dst_is_device) {
-    if (!job || !job->rwr) return fail(UGS_E_BAD_ARG, "not an rwr_sampler job");
+    if (!job || job->kind != UGS_JOB_RWR) return fail(UGS_E_BAD_ARG, "not an rwr_sampler job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 

@@ -27,9 +27,6 @@
 #include "ugs_device.h"
 #include "../../include/ugs_mi355.h"
 
-int ugs_internal_fail(int code, const char *msg);      // ugs_host.cpp: sets the message ugs_last_error() returns
-int ugs_internal_ctx(int *device, hipStream_t *stream);   // ugs_host.cpp: the calling thread's device and stream (ugs_set_device / ugs_set_stream)
-
 #define UGS_WL_MAX_ITER 8
 #define UGS_WL_BLOCK 256
 

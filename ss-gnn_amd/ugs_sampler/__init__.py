@@ -19,6 +19,7 @@ import os
 
 import torch
 
+from ._graphs import _edge_index_view, _out_opts, _select_device
 from ._lib import UGS_E_CAPACITY, check, lib, vp
 
 __version__ = (lib.ugs_version() or b"").decode()
@@ -52,25 +53,6 @@ def _check_cpu_i64(t, name):
         raise RuntimeError(f"{name} must be int64")
 
 
-def _edge_index_view(edge_index):
-    """(tensor kept alive, data pointer, row stride in elements, number of columns) of an int64 [2, E] tensor."""
-    if edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise RuntimeError("edge_index must have shape [2, E]")
-    if edge_index.size(1) > 0 and edge_index.stride(1) != 1:
-        edge_index = edge_index.contiguous()
-    stride = edge_index.stride(0) if edge_index.size(1) > 0 else 0
-    return edge_index, edge_index.data_ptr(), stride, edge_index.size(1)
-
-
-def _out_opts(device):
-    if device is None:
-        return dict(dtype=torch.int64, device="cpu", pin_memory=torch.cuda.is_available()), 0
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("device= must be a GPU device (or None for pinned host tensors)")
-    return dict(dtype=torch.int64, device=dev), 1
-
-
 def _carve(opts, shapes):
     """int64 tensors of the given shapes as views of ONE allocation, in order: one allocator call instead of len(shapes), and
     the library moves adjacent outputs with one copy (ugs_host.cpp finish_common).  Each view is contiguous."""
@@ -87,24 +69,6 @@ def device_count():
     n = C.c_int()
     check(lib.ugs_device_count(C.byref(n)))
     return n.value
-
-
-def _select_device(device, jobs=False):
-    """Device of the calling thread's next library calls.  For a job (`jobs`) that returns DEVICE tensors, the job also runs on
-    torch's current stream of that device: the outputs come from torch's stream-ordered allocator, and only stream order keeps
-    the job's writes behind kernels that may still read a recycled block."""
-    if device is not None:
-        idx = torch.device(device).index
-        idx = idx if idx is not None else torch.cuda.current_device()
-        check(lib.ugs_set_device(idx))
-        if jobs:
-            check(lib.ugs_set_stream(torch.cuda.current_stream(idx).cuda_stream, 1))
-        else:
-            check(lib.ugs_set_stream(None, 0))       # only a device job runs on the caller's stream: a stale handle must not outlive it
-    else:
-        if torch.cuda.is_available():
-            check(lib.ugs_set_device(torch.cuda.current_device()))
-        check(lib.ugs_set_stream(None, 0))
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
-"""Shared body of uniform_sampler.sample_graphs and rwr_sampler.sample_graphs: one call over many graphs, graph g drawn from its
-own seed seeds[g] (C ABI: ugs_*_sample_graphs_begin in include/ugs_mi355.h, which states the law)."""
+"""What the batch entry points of every sampler package share: the view of a batch (`_edge_index_view`), where the outputs go and on
+which device and stream the job runs (`_out_opts`, `_select_device`), the two-phase call of uniform_sampler, rwr_sampler and
+epsilon_uniform_sampler (`run_job`), and their sample_graphs on top of it: one call over many graphs, graph g drawn from its own
+seed seeds[g] (C ABI: ugs_*_sample_graphs_begin in include/ugs_mi355.h, which states the law)."""
 import ctypes as C
 
 import numpy as np
@@ -26,38 +28,68 @@ def seed_array(seeds, G):
     return a
 
 
-def sample_graphs(begin, finish, edge_index, ptr, m_per_graph, k, seeds, mode, device=None):
-    """Runs begin(ei, row_stride, num_cols, ptr, G, m, k, mode, seeds, graph_status, job, total) and finish.  Returns the five
-    tensors on `device` (default: the device of `edge_index`) and the per-graph failures as a host bool tensor [G]."""
-    if edge_index.dtype != torch.int64:
-        raise RuntimeError("edge_index must be int64")
-    if ptr.dtype != torch.int64:
-        raise RuntimeError("ptr must be int64")
-    in_dev = torch.device(device) if device is not None else edge_index.device
-    ei = edge_index.cpu()
-    if ei.dim() != 2 or ei.size(0) != 2:
+def _edge_index_view(edge_index):
+    """(tensor kept alive, data pointer, row stride in elements, number of columns) of an int64 [2, E] tensor."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise RuntimeError("edge_index must have shape [2, E]")
-    if ei.size(1) > 0 and ei.stride(1) != 1:
-        ei = ei.contiguous()
-    pt = ptr.cpu().contiguous()
-    G = pt.numel() - 1
-    m, k = int(m_per_graph), int(k)
-    sd = seed_array(seeds, max(G, 0))
-    status = np.zeros(max(G, 1), dtype=np.int32)
-    if in_dev.type == "cuda":     # device in, device out: the job runs on torch's current stream of that device (see ugs_set_stream)
-        idx = in_dev.index if in_dev.index is not None else torch.cuda.current_device()
+    if edge_index.size(1) > 0 and edge_index.stride(1) != 1:
+        edge_index = edge_index.contiguous()
+    stride = edge_index.stride(0) if edge_index.size(1) > 0 else 0
+    return edge_index, edge_index.data_ptr(), stride, edge_index.size(1)
+
+
+def _out_opts(device):
+    if device is None:
+        return dict(dtype=torch.int64, device="cpu", pin_memory=torch.cuda.is_available()), 0
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("device= must be a GPU device (or None for pinned host tensors)")
+    return dict(dtype=torch.int64, device=dev), 1
+
+
+def _select_device(device, jobs=False):
+    """Device of the calling thread's next library calls.  For a job (`jobs`) that returns DEVICE tensors, the job also runs on
+    torch's current stream of that device: the outputs come from torch's stream-ordered allocator, and only stream order keeps
+    the job's writes behind kernels that may still read a recycled block."""
+    if device is not None:
+        idx = torch.device(device).index
+        idx = idx if idx is not None else torch.cuda.current_device()
         check(lib.ugs_set_device(idx))
-        check(lib.ugs_set_stream(torch.cuda.current_stream(idx).cuda_stream, 1))
+        if jobs:
+            check(lib.ugs_set_stream(torch.cuda.current_stream(idx).cuda_stream, 1))
+        else:
+            check(lib.ugs_set_stream(None, 0))       # only a device job runs on the caller's stream: a stale handle must not outlive it
     else:
         if torch.cuda.is_available():
             check(lib.ugs_set_device(torch.cuda.current_device()))
         check(lib.ugs_set_stream(None, 0))
+
+
+def check_int64(edge_index, ptr):
+    if edge_index.dtype != torch.int64:
+        raise RuntimeError("edge_index must be int64")
+    if ptr.dtype != torch.int64:
+        raise RuntimeError("ptr must be int64")
+
+
+def run_job(begin, finish, edge_index, ptr, m_per_graph, k, device=None):
+    """The two-phase call of a side sampler: begin (walks and edge counts), five tensors sized by its total, finish (fill and copy).
+    `begin(batch, out)` calls the sampler's ugs_*_begin with batch = (ei, row_stride, num_cols, ptr, G, m, k), its own arguments
+    behind them, and out = (job, total) last; it returns the status.  A batch on a GPU (or `device`) gives device tensors and runs on
+    torch's current stream of that device; a host batch gives pinned host tensors.  Returns (nodes, edge_index, edge_ptr,
+    sample_ptr, edge_src)."""
+    check_int64(edge_index, ptr)
+    in_dev = torch.device(device) if device is not None else edge_index.device
+    keep, p, stride, e = _edge_index_view(edge_index.cpu())
+    pt = ptr.cpu().contiguous()
+    G = pt.numel() - 1
+    m, k = int(m_per_graph), int(k)
+    dev = in_dev if in_dev.type == "cuda" else None
+    _select_device(dev, jobs=True)
     job, total = vp(), C.c_int64()
-    check(begin(ei.data_ptr(), ei.stride(0) if ei.size(1) else 0, ei.size(1), pt.data_ptr(), G, m, k, 0 if mode == "sample" else 1,
-                sd.ctypes.data, status.ctypes.data, C.byref(job), C.byref(total)))
-    on_dev = in_dev.type == "cuda"
+    check(begin((p, stride, e, pt.data_ptr(), G, m, k), (C.byref(job), C.byref(total))))
     try:
-        opts = dict(dtype=torch.int64, device=in_dev) if on_dev else dict(dtype=torch.int64, device="cpu", pin_memory=torch.cuda.is_available())
+        opts, on_dev = _out_opts(dev)
         B = G * m
         nodes = torch.empty((B, k), **opts)
         eidx = torch.empty((2, total.value), **opts)
@@ -67,5 +99,20 @@ def sample_graphs(begin, finish, edge_index, ptr, m_per_graph, k, seeds, mode, d
     except BaseException:
         lib.ugs_job_cancel(job)
         raise
-    check(finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(), esrc.data_ptr(), 1 if on_dev else 0))
-    return (nodes, eidx, eptr, sptr, esrc), torch.from_numpy(status[:G] != 0)
+    check(finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(), esrc.data_ptr(), on_dev))
+    return nodes, eidx, eptr, sptr, esrc
+
+
+def sample_graphs(begin, finish, edge_index, ptr, m_per_graph, k, seeds, mode, device=None):
+    """run_job with one seed per graph: `begin(batch, mode, seeds, graph_status, out)` calls the sampler's ugs_*_sample_graphs_begin.
+    Returns the five tensors on `device` (default: the device of `edge_index`) and the per-graph failures as a host bool tensor [G]."""
+    status = []
+
+    def begin_graphs(batch, out):
+        G = batch[4]
+        sd = seed_array(seeds, max(G, 0))
+        status.append(np.zeros(max(G, 1), dtype=np.int32))
+        return begin(batch, 0 if mode == "sample" else 1, sd.ctypes.data, status[0].ctypes.data, out)
+
+    five = run_job(begin_graphs, finish, edge_index, ptr, m_per_graph, k, device)
+    return five, torch.from_numpy(status[0][:ptr.numel() - 1] != 0)
