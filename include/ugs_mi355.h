@@ -331,6 +331,37 @@ int ugs_uniform_sample_batch_begin(const int64_t *edge_index, int64_t row_stride
                                    ugs_job **job_out, int64_t *total_edges_out);
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device);
+/* ---- uniform_sampler.enumerate_graphs(edge_index, ptr, k, mode, max_rows) / count_graphs(edge_index, ptr, k, limit): the population
+ *      ugs_uniform_sample_batch_begin draws from, whole.  Items 1, 2, 4 and 5 of the law above hold verbatim; item 3 (the draws) is
+ *      replaced by:
+ *        - S_g is the list of item 2 (empty for k = 0 or n < k); sample_ptr[g+1] - sample_ptr[g] = |S_g| for a healthy graph and 0
+ *          for a failed one, sample_ptr[0] = 0, R = sample_ptr[G];
+ *        - row sample_ptr[g] + i is the i-th set of S_g written as item 4 says, its edges as item 5 says; no row is padded with -1;
+ *        - so row sample_ptr[g] + d is exactly the row ugs_uniform_sample_batch_begin / _sample_graphs_begin emit when the graph's
+ *          generator draws d.
+ *      enumerate_begin runs the same count pass, scan, write pass and sorts as the samplers, reads the per-graph counts back (the
+ *      row count is known only then: the first of its two read-backs, the second is the edge total), and turns every key of the
+ *      sorted array into a row.  Outputs of finish: nodes[R,k], edge_index[2,total_edges], edge_ptr[R+1], sample_ptr[G+1],
+ *      edge_src[total_edges].  Same job protocol, stream rules and ugs_job_cancel as the other jobs; enumerate_finish takes only an
+ *      enumeration job, ugs_uniform_sample_batch_finish does not take one.
+ *      A graph that fails alone contributes no rows and leaves the others undisturbed: graph_status[g] = 1 for a graph of at least k
+ *      vertices that ugs_uniform_sample_batch_begin refuses for its size (more than 64 vertices and over the limit in force, or a k
+ *      outside the wide rule), 2 for a graph whose own |S_g| exceeds max_rows (count_graphs: limit); 0 otherwise.  graph_status is a
+ *      host array of num_graphs entries, written by the call.  Healthy graphs whose sets TOGETHER exceed max_rows fail the call:
+ *      UGS_E_UNSUPPORTED, "split the call".  max_rows must be 1 ... 2^25 (the device budget), else UGS_E_BAD_ARG; it sizes the two
+ *      key arrays, while nodes, edge_ptr and the per-row edge counts are sized by R.  The other argument errors are those of
+ *      ugs_uniform_sample_batch_begin.
+ *      count_graphs is synchronous and has no job: counts_out[g] = |S_g|, exact wherever |S_g| <= limit; -1, with graph_status as
+ *      above, for a graph past limit or refused for its size.  limit must be 1 ... 2^32, else UGS_E_BAD_ARG.  It runs the column
+ *      buckets, the adjacency and the count pass only, stores no keys, allocates the adjacency and the per-item counters but
+ *      neither key array, and its work per graph is bounded by limit (a graph past it stops counting at its next flush). */
+int ugs_uniform_count_graphs(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                             int k, int64_t limit, int64_t *counts_out, int32_t *graph_status);
+int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                                int64_t num_graphs, int k, int mode, int64_t max_rows, int32_t *graph_status,
+                                ugs_job **job_out, int64_t *total_rows_out, int64_t *total_edges_out);
+int ugs_uniform_enumerate_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                 int64_t *edge_src, int dst_is_device);
 /* Vertices per graph up to which ugs_uniform_* enumerates.  Default 64: every call behaves as it did before the wide form existed.
  * A caller whose graphs are larger (PROTEINS, IMDB-BINARY) raises it, to 1024 at most, once at start-up; nothing raises it
  * implicitly.  Results for graphs of at most 64 vertices never depend on it, and a call without wide graphs allocates and launches

@@ -229,8 +229,10 @@ struct UgsUniCall {
     int64_t G, E, nv, rows, budget;          // graphs, columns, enumerated vertices, G * m rows, mask budget
     int32_t m, k, mode;                      // mode 0: "sample" (row positions), otherwise batch ids
     uint64_t seed;
-    const uint64_t *seeds;                   // [G] per-graph generators (ugs_uniform_sample_graphs_begin); nullptr: one for the call
-    int64_t *gcount;                         // [G] per-graph subset count of the count pass (seeds only; > budget: the graph failed)
+    const uint64_t *seeds;                   // [G] per-graph generators (ugs_uniform_sample_graphs_begin); nullptr: one for the call, or no draws
+    int32_t per_graph;                       // the budget bounds every graph's own count (sample_graphs, count, enumerate), not the call's
+    int64_t *gcount;                         // [G] per-graph subset count of the count pass (per_graph only; > budget: the graph failed)
+    const int64_t *sptr;                     // [G + 1] enumerate only: exclusive scan of gsize in batch graph order (= sample_ptr); rows = sptr[G]
     const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
     const UgsUniGraph *graphs;               // [G]
     const int32_t *vgraph;                   // [nv] graph of an enumerated vertex
@@ -272,6 +274,13 @@ struct UgsUniWide {
 size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget);
 hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
 hipError_t ugs_uniform_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+// count: column buckets, adjacency and the count pass only (gcount; reads neither ioff nor a key array).  enumerate: enum_keys runs
+// everything up to gstart / gsize; with sptr, rows, nodes, edge_ptr and ecount set, enum_rows writes one row per key and scans the
+// edge counts, enum_fill the edges.
+hipError_t ugs_uniform_count(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
+hipError_t ugs_uniform_enum_keys(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
+hipError_t ugs_uniform_enum_rows(const UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
+hipError_t ugs_uniform_enum_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 
 // ---- rwr_sampler (ugs_rwr.hip): random walk with restart, one SplitMix64 stream per graph, counter-based speculation ----
 #define UGS_RWR_KMAX 64

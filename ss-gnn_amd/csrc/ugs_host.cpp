@@ -2292,7 +2292,7 @@ int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len,
 // ---------------------------------------------------------------------------------------------------------------
 // What fills a side sampler's edge outputs at finish: edge_index [2, ld] and edge_src [ld] on the device, on the job's stream.
 using JobFill = std::function<hipError_t(int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s)>;
-enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR };
+enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR, UGS_JOB_UNIFORM_ENUM };
 
 struct ugs_job {
     ugs_plan *plan = nullptr;          // ugs jobs only
@@ -2312,6 +2312,9 @@ struct ugs_job {
     // that finish runs from them.  The hook holds the sampler's call struct by value; empty: the job fills through its plan.
     PoolBuf blob;
     JobFill fill;
+    // a job whose begin reports its own row count (ugs_uniform_enumerate_begin): its sample_ptr [G + 1], rows = sample_ptr[G];
+    // empty: rows = G m and sample_ptr = g m
+    std::vector<int64_t> sample_ptr;
 };
 
 namespace {
@@ -2470,7 +2473,7 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
         }
         if (sample_ptr) {
             std::vector<int64_t> sp((size_t)j->G + 1);
-            for (int64_t g = 0; g <= j->G; ++g) sp[(size_t)g] = g * (int64_t)j->m;
+            for (int64_t g = 0; g <= j->G; ++g) sp[(size_t)g] = j->sample_ptr.empty() ? g * (int64_t)j->m : j->sample_ptr[(size_t)g];
             if (dst_is_device) HIP_TRY(hipMemcpy(sample_ptr, sp.data(), sp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
             else std::memcpy(sample_ptr, sp.data(), sp.size() * sizeof(int64_t));
         }
@@ -2527,14 +2530,22 @@ int scan_ptr(const int64_t *ptr, int64_t G, bool per_graph, std::vector<int32_t>
     return UGS_OK;
 }
 
-// The job of a side sampler: its parameters, its blob, and nodes [rows, k] with edge_ptr [rows + 1] right behind it.
-int side_job(const DeviceCtx &dc, int kind, int64_t G, int m, int k, int mode, size_t blob_bytes, ugs_job **out) {
+// nodes [rows, k] with edge_ptr [rows + 1] right behind it, and `extra_bytes` of the sampler's own behind both (finish copies none of
+// them out).  On failure the job is gone.
+int side_job_rows(ugs_job *j, int64_t rows, size_t extra_bytes = 0) {
+    j->rows = rows;
+    if (int rc = pool_get((size_t)(rows * j->k + rows + 1) * sizeof(int64_t) + extra_bytes, j->dc.id, j->nodes)) { free_job(j); return rc; }
+    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + rows * j->k;
+    return UGS_OK;
+}
+
+// The job of a side sampler: its parameters, its blob, and the G m rows of side_job_rows.  rows_later: the begin learns its row count
+// from the device (enumeration) and calls side_job_rows itself, or never has rows (counting).
+int side_job(const DeviceCtx &dc, int kind, int64_t G, int m, int k, int mode, size_t blob_bytes, ugs_job **out, bool rows_later = false) {
     auto *j = new ugs_job();
-    j->dc = dc; j->kind = kind; j->m = m; j->k = k; j->mode = mode; j->G = G; j->rows = G * (int64_t)m;
-    int rc = pool_get(blob_bytes, dc.id, j->blob);
-    if (!rc) rc = pool_get((size_t)(j->rows * k + j->rows + 1) * sizeof(int64_t), dc.id, j->nodes);
-    if (rc) { free_job(j); return rc; }
-    j->d_eptr = static_cast<int64_t *>(j->nodes.p) + j->rows * k;
+    j->dc = dc; j->kind = kind; j->m = m; j->k = k; j->mode = mode; j->G = G;
+    if (int rc = pool_get(blob_bytes, dc.id, j->blob)) { free_job(j); return rc; }
+    if (!rows_later) if (int rc = side_job_rows(j, G * (int64_t)m)) return rc;
     *out = j;
     return UGS_OK;
 }
@@ -2967,12 +2978,18 @@ int ugs_uniform_set_mask_vertices(int n, int *previous) {
 // seeds == nullptr: sample_batch, one generator for the call; otherwise sample_graphs: graph g draws from seeds[g], and a graph whose
 // one-graph call would be refused (more vertices than the limit in force or than its k allows, |S_g| past the budget) fails alone,
 // graph_status[g] = 1.
+// what = UNI_ENUMERATE / UNI_COUNT (ugs_uniform_enumerate_begin / ugs_uniform_count_graphs): no generator and no draws; `cap` (max_rows /
+// limit) takes the budget's place, per graph as in sample_graphs, graph_status[g] = 1 for a size refusal and 2 for a graph past cap.
+// UNI_ENUMERATE: m_per_graph = 0, one row per set, *rows_out = their number.  UNI_COUNT: no job; counts_out[g] = |S_g|, -1 where refused.
+enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT };
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
-                         ugs_job **job_out, int64_t *total_edges_out) {
-    if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+                         ugs_job **job_out, int64_t *total_edges_out, int what = UNI_SAMPLE, int64_t cap = UGS_UNI_BUDGET,
+                         int64_t *rows_out = nullptr, int64_t *counts_out = nullptr) {
+    if ((!job_out && what != UNI_COUNT) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
+        return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
-    const bool per_graph = seeds != nullptr;
+    const bool per_graph = seeds != nullptr || what != UNI_SAMPLE;
     if (per_graph && num_graphs >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
     if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
     if (k < 0) return fail(UGS_E_BAD_ARG, "k must be >= 0");
@@ -3013,38 +3030,46 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     }
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
-    const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? UGS_UNI_BUDGET : 0;
+    const bool sampling = what == UNI_SAMPLE, counting = what == UNI_COUNT;
+    const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? cap : 0;   // (enumerate: m = 0, its rows come later)
+    const int64_t keys = counting ? 0 : budget;                         // counting stores no keys and scans nothing
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
     BlobLayout L;
     auto take = [&](size_t bytes) { return L.take(bytes); };
-    const BatchInputs in(L, E, G, sizeof(UgsUniGraph), per_graph);
+    const BatchInputs in(L, E, G, sizeof(UgsUniGraph), seeds != nullptr);
     const bool wide = nv_wide > 0;                                      // a call without wide graphs allocates nothing for them
     const size_t o_vg = take((size_t)nv * 4), o_wb = wide ? take((size_t)G * 8) : 0;
     L.end_inputs();
-    const size_t o_wadj = wide ? take((size_t)adj_words * 8) : 0, o_wp = wide ? take((size_t)E * 4) : 0, o_gzm = wide ? take((size_t)G * 8) : 0,
-                 o_rk = wide ? take((size_t)rows * 8) : 0;
+    const size_t o_wadj = wide ? take((size_t)adj_words * 8) : 0, o_wp = wide ? take((size_t)E * 4) : 0,
+                 o_gzm = wide && sampling ? take((size_t)G * 8) : 0, o_rk = wide && sampling ? take((size_t)rows * 8) : 0;
     const size_t o_gc = take(per_graph ? (size_t)G * 8 : 0);
-    const size_t cub_bytes = ugs_uniform_cub_bytes(E, nv, budget);
+    const size_t cub_bytes = counting ? ugs_uniform_cub_bytes(E, 0, 0) : ugs_uniform_cub_bytes(E, nv, budget);
     const size_t o_cub = take(cub_bytes), o_ck = take((size_t)E * 4), o_ck2 = take((size_t)E * 4), o_cv = take((size_t)E * 4),
                  o_cv2 = take((size_t)E * 4), o_cst = take((size_t)(G + 1) * 8), o_bp = take((size_t)E * 2), o_adj = take((size_t)nv * 8),
-                 o_ic = take((size_t)items * 4), o_io = take((size_t)(items + 1) * 8),
-                 o_st = take((size_t)ugs_scan_tmp_words(std::max(items, rows)) * 8), o_sl = take((size_t)nv * 4), o_sh = take((size_t)nv * 4),
-                 o_ka = take((size_t)budget * 8), o_kb = take((size_t)budget * 8), o_gs = take((size_t)G * 8), o_gz = take((size_t)G * 8),
-                 o_np = take((size_t)G * 4), o_nl = take((size_t)G * 4), o_dr = take((size_t)rows * 4), o_rm = take((size_t)rows * 8),
-                 o_ec = take((size_t)rows * 4), o_status = take(4 * 8);
+                 o_ic = take((size_t)items * 4), o_status = take(4 * 8);
+    // (enumerate scans the edge counts of up to `budget` rows)
+    const size_t o_io = counting ? 0 : take((size_t)(items + 1) * 8),
+                 o_st = counting ? 0 : take((size_t)ugs_scan_tmp_words(std::max(items, sampling ? rows : budget)) * 8),
+                 o_sl = counting ? 0 : take((size_t)nv * 4), o_sh = counting ? 0 : take((size_t)nv * 4),
+                 o_ka = counting ? 0 : take((size_t)keys * 8), o_kb = counting ? 0 : take((size_t)keys * 8),
+                 o_gs = counting ? 0 : take((size_t)G * 8), o_gz = counting ? 0 : take((size_t)G * 8);
+    const size_t o_np = sampling ? take((size_t)G * 4) : 0, o_nl = sampling ? take((size_t)G * 4) : 0, o_dr = sampling ? take((size_t)rows * 4) : 0,
+                 o_rm = sampling ? take((size_t)rows * 8) : 0, o_ec = sampling ? take((size_t)rows * 4) : 0;
+    const size_t o_sp = what == UNI_ENUMERATE ? take((size_t)(G + 1) * 8) : 0;
     std::vector<char> host(L.in_bytes, 0);
-    in.stage(host.data(), edge_index, row_stride, E, ptr, G, gd.data(), sizeof(UgsUniGraph), per_graph ? seeds : nullptr);
+    in.stage(host.data(), edge_index, row_stride, E, ptr, G, gd.data(), sizeof(UgsUniGraph), seeds);
     if (wide) std::memcpy(host.data() + o_wb, wbase.data(), (size_t)G * 8);
     auto *vg = reinterpret_cast<int32_t *>(host.data() + o_vg);
     for (int64_t g = 0; g < G; ++g)
         if (gd[(size_t)g].enumerable) for (int32_t v = 0; v < gd[(size_t)g].n; ++v) vg[gd[(size_t)g].vbase + v] = (int32_t)g;
     ugs_job *j = nullptr;
-    if (int rc = side_job(dc, UGS_JOB_UNIFORM, G, m_per_graph, k, mode, L.off, &j)) return rc;
+    if (int rc = side_job(dc, sampling ? UGS_JOB_UNIFORM : UGS_JOB_UNIFORM_ENUM, G, m_per_graph, k, mode, L.off, &j, !sampling)) return rc;
     auto bail = [&](int rc) { free_job(j); return rc; };
     char *b = static_cast<char *>(j->blob.p);
     UgsUniCall c{};
     c.G = G; c.E = E; c.nv = nv; c.rows = rows; c.budget = budget; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
-    c.seeds = per_graph ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
+    c.seeds = seeds ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
+    c.per_graph = per_graph ? 1 : 0;
     c.gcount = per_graph ? reinterpret_cast<int64_t *>(b + o_gc) : nullptr;
     c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
     c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + in.desc);
@@ -3061,7 +3086,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     c.nepos = reinterpret_cast<int32_t *>(b + o_np); c.ne_list = reinterpret_cast<int32_t *>(b + o_nl);
     c.draws = reinterpret_cast<int32_t *>(b + o_dr); c.rowmask = reinterpret_cast<uint64_t *>(b + o_rm);
     c.ecount = reinterpret_cast<uint32_t *>(b + o_ec); c.status = reinterpret_cast<int64_t *>(b + o_status);
-    c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    if (sampling) { c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr; }
     UgsUniWide w{};
     w.nv_mask = nv_mask; w.adj_words = adj_words;
     if (wide) {
@@ -3072,6 +3097,39 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     int64_t status[4] = {0, 0, 0, 0};
     std::vector<int64_t> gcount(per_graph && nv > 0 ? (size_t)G : 0, 0);   // per-graph subset counts: read back once, with the total
     hipError_t e = hipMemcpyAsync(b, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (!sampling) {
+        // the count pass (count: nothing else; enumerate: through the sorts), then the first read-back: the graphs' counts and sizes
+        std::vector<int64_t> gsize(!counting && nv > 0 ? (size_t)G : 0, 0);
+        if (e == hipSuccess) e = counting ? ugs_uniform_count(c, w, dc.stream) : ugs_uniform_enum_keys(c, w, dc.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
+        if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
+        if (e == hipSuccess && !gsize.empty()) e = hipMemcpyAsync(gsize.data(), c.gsize, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
+        if (e != hipSuccess) return bail(fail_hip(e, "uniform_sampler pipeline"));
+        for (int64_t g = 0; g < G; ++g) {
+            const bool past = !gcount.empty() && gd[(size_t)g].enumerable && gcount[(size_t)g] > budget;
+            graph_status[g] = too_big[(size_t)g] ? 1 : past ? 2 : 0;
+            if (counting) counts_out[g] = graph_status[g] ? -1 : gcount.empty() ? 0 : gcount[(size_t)g];
+        }
+        if (counting) return bail(UGS_OK);
+        if (status[1])
+            return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the call's graphs together have " + std::to_string(status[0]) +
+                                                " connected k-subsets, more than max_rows = " + std::to_string(cap) + "; split the call"));
+        // sample_ptr: the sizes scanned in batch order (the keys lie in the order of the enumerated vertices, mask graphs first)
+        j->sample_ptr.assign((size_t)G + 1, 0);
+        for (int64_t g = 0; g < G; ++g) j->sample_ptr[(size_t)g + 1] = j->sample_ptr[(size_t)g] + (gsize.empty() ? 0 : gsize[(size_t)g]);
+        const int64_t R = j->sample_ptr[(size_t)G];
+        if (int rc = side_job_rows(j, R, (size_t)R * 4)) return rc;    // nodes and edge_ptr by R, the per-row edge counts behind them
+        c.rows = R; c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+        c.ecount = reinterpret_cast<uint32_t *>(j->d_eptr + R + 1);
+        c.sptr = reinterpret_cast<const int64_t *>(b + o_sp);
+        e = hipMemcpyAsync(b + o_sp, j->sample_ptr.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, dc.stream);
+        if (e == hipSuccess) e = ugs_uniform_enum_rows(c, w, dc.stream);
+        if (int rc = side_job_total(j, e, "uniform_sampler enumeration")) return rc;    // the second read-back: the edge total
+        if (rows_out) *rows_out = R;
+        j->fill = [c, w](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_uniform_enum_fill(c, w, edge_index, edge_src, ld, s); };
+        return hand_out(j, job_out, total_edges_out);
+    }
     if (e == hipSuccess) e = ugs_uniform_begin(c, w, dc.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
     if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
@@ -3108,6 +3166,31 @@ int ugs_uniform_sample_graphs_begin(const int64_t *edge_index, int64_t row_strid
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                     int64_t *edge_src, int dst_is_device) {
     if (!job || job->kind != UGS_JOB_UNIFORM) return fail(UGS_E_BAD_ARG, "not a uniform_sampler job");
+    return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
+}
+
+// ---- uniform_sampler.count_graphs / enumerate_graphs: the population the sampler draws from (the law is stated in include/ugs_mi355.h) ----
+int ugs_uniform_count_graphs(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,
+                             int64_t limit, int64_t *counts_out, int32_t *graph_status) {
+    if (limit < 1 || limit > ((int64_t)1 << 32)) return fail(UGS_E_BAD_ARG, "limit must be 1 ... 2^32 (got " + std::to_string(limit) + ")");
+    if (num_graphs > 0 && (!counts_out || !graph_status)) return fail(UGS_E_BAD_ARG, "count_graphs needs counts_out and graph_status");
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_COUNT, limit,
+                         nullptr, counts_out);
+}
+
+int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,
+                                int mode, int64_t max_rows, int32_t *graph_status, ugs_job **job_out, int64_t *total_rows_out,
+                                int64_t *total_edges_out) {
+    if (max_rows < 1 || max_rows > UGS_UNI_BUDGET) return fail(UGS_E_BAD_ARG, "max_rows must be 1 ... 2^25 (got " + std::to_string(max_rows) + ")");
+    if (num_graphs > 0 && !graph_status) return fail(UGS_E_BAD_ARG, "enumerate_graphs needs graph_status");
+    if (!total_rows_out) return fail(UGS_E_BAD_ARG, "total_rows_out is null");
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, mode, 0, nullptr, graph_status, job_out, total_edges_out,
+                         UNI_ENUMERATE, max_rows, total_rows_out);
+}
+
+int ugs_uniform_enumerate_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr, int64_t *edge_src,
+                                 int dst_is_device) {
+    if (!job || job->kind != UGS_JOB_UNIFORM_ENUM) return fail(UGS_E_BAD_ARG, "not a uniform_sampler enumeration job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 

@@ -5,9 +5,12 @@
 // vertex tuples (:47-80), m draws std::uniform_int_distribution<int>(0, |S_g|-1) from ONE std::mt19937_64(seed) per
 // graph with S_g non-empty (:144, :189), edges = the batch columns inside the row's subset, in column order (:193-236).
 //
-// ugs_uniform_sample_graphs_begin (c.seeds != nullptr) gives every graph its own generator and its own budget: the count pass
+// ugs_uniform_sample_graphs_begin gives every graph its own budget (c.per_graph) and its own generator (c.seeds): the count pass
 // adds into the graph's counter and stops counting a graph once it is past the budget, uni_cap empties the items of such graphs
 // before the scan, uni_joint flags a call whose healthy graphs together are past it, and uni_draw_graphs replaces uni_draw.
+// ugs_uniform_count_graphs and ugs_uniform_enumerate_begin take the per-graph budget without any generator: the first stops behind
+// the count pass, the second replaces draws, uni_rows and uni_fill by uni_enum_rows / uni_enum_fill (wide: uni_wenum_*), one row
+// per key of the sorted array.
 //
 // Pipeline (one stream, no host round trip until the edge total):
 //   uni_colgraph + radix sort   stable bucket of the batch's columns by graph (key = graph id, ties keep column order)
@@ -90,10 +93,10 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
     const int64_t vi = item >> 6;
     const int w0 = (int)(item & 63);
     const int32_t gi = c.vgraph[vi];
-    if (WRITE && c.seeds && c.gcount[gi] > c.budget) return;
+    if (WRITE && c.per_graph && c.gcount[gi] > c.budget) return;
     const UgsUniGraph gd = c.graphs[gi];
-    // running total that bounds the work: the call's, or the graph's with per-graph seeds
-    unsigned long long *const ctr = (unsigned long long *)(c.seeds ? &c.gcount[gi] : &c.status[0]);
+    // running total that bounds the work: the call's, or the graph's with per-graph budgets
+    unsigned long long *const ctr = (unsigned long long *)(c.per_graph ? &c.gcount[gi] : &c.status[0]);
     const int v = (int)(vi - gd.vbase);
     const uint64_t *adj = c.adj + gd.vbase;
     const int k = c.k;
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
                         if (cnt - flushed >= 4096) {                // bounded work for calls (graphs) over the budget
                             const unsigned long long now = atomicAdd(ctr, (unsigned long long)(cnt - flushed)) + (cnt - flushed);
                             flushed = cnt;
-                            if (now > (unsigned long long)c.budget) { if (!c.seeds) c.status[1] = 1; break; }
+                            if (now > (unsigned long long)c.budget) { if (!c.per_graph) c.status[1] = 1; break; }
                         }
                     }
                     --d;
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_esu(UgsUniCall c) {
         c.icount[item] = (uint32_t)(cnt < 0xFFFFFFFFull ? cnt : 0xFFFFFFFFull);
         if (cnt > flushed) {
             const unsigned long long now = atomicAdd(ctr, (unsigned long long)(cnt - flushed)) + (cnt - flushed);
-            if (now > (unsigned long long)c.budget && !c.seeds) c.status[1] = 1;
+            if (now > (unsigned long long)c.budget && !c.per_graph) c.status[1] = 1;
         }
     }
 }
@@ -508,7 +511,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wesu(UgsUniCall c, UgsUniWide w
     const int64_t vi = item >> 6;
     const int slot = (int)(item & 63);
     const int32_t gi = c.vgraph[vi];
-    if (WRITE && c.seeds && c.gcount[gi] > c.budget) return;
+    if (WRITE && c.per_graph && c.gcount[gi] > c.budget) return;
     const UgsUniGraph gd = c.graphs[gi];
     const int v = (int)(vi - gd.vbase), vw = v >> 6;
     WGroup x;
@@ -518,8 +521,8 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wesu(UgsUniCall c, UgsUniWide w
     x.abv = x.l < vw ? 0ull : x.l == vw ? above_mask(v & 63) : ~0ull;
     x.out = WRITE ? c.keys_a + c.ioff[item] : nullptr;
     x.cnt = 0; x.flushed = 0;
-    x.ctr = (unsigned long long *)(c.seeds ? &c.gcount[gi] : &c.status[0]);
-    x.budget = c.budget; x.status = c.seeds ? nullptr : c.status; x.stop = false;
+    x.ctr = (unsigned long long *)(c.per_graph ? &c.gcount[gi] : &c.status[0]);
+    x.budget = c.budget; x.status = c.per_graph ? nullptr : c.status; x.stop = false;
     const uint64_t av = x.l < x.W ? x.adj[(int64_t)v * x.W + x.l] : 0ull;
     const uint64_t ext1 = av & x.abv;
     const uint64_t nb1 = av | (x.l == vw ? 1ull << (v & 63) : 0ull);
@@ -552,7 +555,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wesu(UgsUniCall c, UgsUniWide w
             c.icount[item] = tot;
             if (rest) {
                 const unsigned long long now = atomicAdd(x.ctr, (unsigned long long)rest) + rest;
-                if (now > (unsigned long long)c.budget && !c.seeds) c.status[1] = 1;
+                if (now > (unsigned long long)c.budget && !c.per_graph) c.status[1] = 1;
             }
         }
     }
@@ -615,6 +618,98 @@ __global__ void uni_wfill(UgsUniCall c, UgsUniWide wd, int64_t *edge_index, int6
     }
 }
 
+// ---- enumeration (ugs_uniform_enumerate_begin): the whole sorted key array as rows.  Row r belongs to the graph g with
+//      sptr[g] <= r < sptr[g + 1], sptr = the exclusive scan of gsize in BATCH graph order (the call's sample_ptr), and is the
+//      (r - sptr[g])-th key of that graph: keys_sorted[gstart[g] + r - sptr[g]].  gstart follows the enumerated vertices (mask graphs
+//      first, wide graphs behind them), so it is not monotonic in g when the two kinds interleave; sptr is.  The key is read again by
+//      the fill, so no per-row mask or key is kept. ----
+__device__ __forceinline__ int64_t enum_graph(const UgsUniCall &c, int64_t row) {
+    int64_t lo = 0, hi = c.G - 1;                                   // the first g with sptr[g + 1] > row (row < sptr[G])
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (c.sptr[mid + 1] <= row) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ uint64_t enum_key(const UgsUniCall &c, int64_t g, int64_t row) { return c.keys_sorted[c.gstart[g] + (row - c.sptr[g])]; }
+
+__global__ void uni_enum_rows(UgsUniCall c) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = enum_graph(c, row);
+    const UgsUniGraph gd = c.graphs[g];
+    if (gd.enumerable != 1) return;                                 // a wide graph's row: uni_wenum_rows
+    const uint64_t mask = mask_of(enum_key(c, g, row));
+    int64_t *out = c.nodes + row * c.k;
+    int j = 0;
+    for (uint64_t e = mask; e && j < c.k; e &= e - 1) out[j++] = gd.lo + (__ffsll((unsigned long long)e) - 1);
+    uint32_t cnt = 0;
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = c.bpair[p];
+        cnt += ((mask >> (uv & 63)) & (mask >> (uv >> 8)) & 1) ? 1u : 0u;
+    }
+    c.ecount[row] = cnt;
+}
+
+__global__ void uni_enum_fill(UgsUniCall c, int64_t *edge_index, int64_t *edge_src, int64_t ld) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = enum_graph(c, row);
+    const UgsUniGraph gd = c.graphs[g];
+    if (gd.enumerable != 1) return;
+    const uint64_t mask = mask_of(enum_key(c, g, row));
+    int64_t w = c.edge_ptr[row];
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = c.bpair[p];
+        const int u = uv & 63, v = uv >> 8;
+        if (!((mask >> u) & (mask >> v) & 1)) continue;
+        if (c.mode == 0) {
+            edge_index[w] = __popcll(mask & ((1ull << u) - 1));
+            edge_index[ld + w] = __popcll(mask & ((1ull << v) - 1));
+        } else {
+            edge_index[w] = gd.lo + u;
+            edge_index[ld + w] = gd.lo + v;
+        }
+        edge_src[w] = c.cval2[p];
+        ++w;
+    }
+}
+
+__global__ void uni_wenum_rows(UgsUniCall c, UgsUniWide wd) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = enum_graph(c, row);
+    const UgsUniGraph gd = c.graphs[g];
+    if (gd.enumerable != 2) return;
+    const int k = c.k, b = field_bits(gd.n);
+    const uint64_t key = enum_key(c, g, row);
+    int64_t *out = c.nodes + row * k;
+    for (int j = 0; j < k; ++j) out[j] = gd.lo + (int64_t)((key >> (b * (k - 1 - j))) & ((1ull << b) - 1));
+    uint32_t cnt = 0;
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = wd.wpair[p];
+        cnt += tuple_pos(key, k, b, uv & 0xFFFFu) >= 0 && tuple_pos(key, k, b, uv >> 16) >= 0 ? 1u : 0u;
+    }
+    c.ecount[row] = cnt;
+}
+
+__global__ void uni_wenum_fill(UgsUniCall c, UgsUniWide wd, int64_t *edge_index, int64_t *edge_src, int64_t ld) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t g = enum_graph(c, row);
+    const UgsUniGraph gd = c.graphs[g];
+    if (gd.enumerable != 2) return;
+    const int k = c.k, b = field_bits(gd.n);
+    const uint64_t key = enum_key(c, g, row);
+    int64_t w = c.edge_ptr[row];
+    for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
+        const uint32_t uv = wd.wpair[p];
+        const int pu = tuple_pos(key, k, b, uv & 0xFFFFu), pv = tuple_pos(key, k, b, uv >> 16);
+        if (pu < 0 || pv < 0) continue;
+        edge_index[w] = c.mode == 0 ? pu : gd.lo + (int64_t)(uv & 0xFFFFu);
+        edge_index[ld + w] = c.mode == 0 ? pv : gd.lo + (int64_t)(uv >> 16);
+        edge_src[w] = c.cval2[p];
+        ++w;
+    }
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace
@@ -631,11 +726,12 @@ size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget) {
     return a > b ? a : b;
 }
 
-hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) {
+// The stages every entry shares, up to the per-graph sizes: column buckets, adjacency, the count pass and -- unless `count_only` --
+// scan, write pass, sorts, gstart / gsize.  count_only stops behind the count pass: it touches neither ioff nor a key array.
+static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_only, hipStream_t s) {
     const int64_t nv_wide = c.nv - w.nv_mask;                                  // 0: the call runs the mask form's launches only
-    UgsUniCall cm = c;                                                         // the mask form's view: its own roots, its own graphs' sizes
+    UgsUniCall cm = c;                                                         // the mask form's view: its own roots
     cm.nv = w.nv_mask;
-    if (nv_wide > 0) cm.gsize = w.gsize_mask;
     hipError_t e = hipMemsetAsync(c.status, 0, 4 * sizeof(int64_t), s);
     if (e != hipSuccess) return e;
     int bits = 1;
@@ -656,15 +752,16 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) 
             if (c.E > 0) hipLaunchKernelGGL(uni_wadj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
         }
         const int64_t items = c.nv * 64, mitems = cm.nv * 64, witems = nv_wide * 64;
-        if (c.seeds && (e = hipMemsetAsync(c.gcount, 0, (size_t)c.G * sizeof(int64_t), s)) != hipSuccess) return e;
+        if (c.per_graph && (e = hipMemsetAsync(c.gcount, 0, (size_t)c.G * sizeof(int64_t), s)) != hipSuccess) return e;
         if (mitems > 0) {
             if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
             else hipLaunchKernelGGL((uni_esu<64, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
         }
         if (witems > 0) hipLaunchKernelGGL((uni_wesu<false>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), 0, s, c, w);
-        if (c.seeds) hipLaunchKernelGGL(uni_cap, dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        if (count_only) return hipGetLastError();
+        if (c.per_graph) hipLaunchKernelGGL(uni_cap, dim3(blocks(items, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         if ((e = ugs_launch_scan(c.icount, items, c.ioff, c.scan_tmp, s)) != hipSuccess) return e;
-        if (c.seeds) hipLaunchKernelGGL(uni_joint, dim3(1), dim3(64), 0, s, c);
+        if (c.per_graph) hipLaunchKernelGGL(uni_joint, dim3(1), dim3(64), 0, s, c);
         if (mitems > 0) {
             if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, true>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
             else hipLaunchKernelGGL((uni_esu<64, true>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
@@ -679,13 +776,22 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) 
         c.keys_sorted = keys.Current();
         hipLaunchKernelGGL(uni_sort_small, dim3((unsigned)c.nv), dim3(UNI_BLOCK), 0, s, c, keys.Current());
     }
+    if (c.G > 0 && !count_only) hipLaunchKernelGGL(uni_graph_sizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+    return hipGetLastError();
+}
+
+hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) {
+    const int64_t nv_wide = c.nv - w.nv_mask;
+    hipError_t e = uni_prepare(c, w, false, s);
+    if (e != hipSuccess) return e;
+    UgsUniCall cm = c;                                                         // the mask form's view: its own graphs' sizes
+    cm.nv = w.nv_mask;
+    if (nv_wide > 0) cm.gsize = w.gsize_mask;
     if (c.G > 0) {
-        hipLaunchKernelGGL(uni_graph_sizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
         if (nv_wide > 0) hipLaunchKernelGGL(uni_wsizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
         if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
         else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
     }
-    cm.keys_sorted = c.keys_sorted;
     if (c.rows > 0) hipLaunchKernelGGL(uni_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
     if (c.rows > 0 && nv_wide > 0) hipLaunchKernelGGL(uni_wrows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -696,5 +802,23 @@ hipError_t ugs_uniform_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *e
     if (c.rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(uni_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, edge_index, edge_src, ld);
     if (c.nv > w.nv_mask) hipLaunchKernelGGL(uni_wfill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w, edge_index, edge_src, ld);
+    return hipGetLastError();
+}
+
+hipError_t ugs_uniform_count(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) { return uni_prepare(c, w, true, s); }
+
+hipError_t ugs_uniform_enum_keys(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) { return uni_prepare(c, w, false, s); }
+
+hipError_t ugs_uniform_enum_rows(const UgsUniCall &c, const UgsUniWide &w, hipStream_t s) {
+    if (c.rows > 0 && w.nv_mask > 0) hipLaunchKernelGGL(uni_enum_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+    if (c.rows > 0 && c.nv > w.nv_mask) hipLaunchKernelGGL(uni_wenum_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return ugs_launch_scan(c.ecount, c.rows, c.edge_ptr, c.scan_tmp, s);
+}
+
+hipError_t ugs_uniform_enum_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {
+    if (c.rows <= 0) return hipSuccess;
+    if (w.nv_mask > 0) hipLaunchKernelGGL(uni_enum_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, edge_index, edge_src, ld);
+    if (c.nv > w.nv_mask) hipLaunchKernelGGL(uni_wenum_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w, edge_index, edge_src, ld);
     return hipGetLastError();
 }

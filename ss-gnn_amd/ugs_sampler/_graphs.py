@@ -1,6 +1,6 @@
 """What the batch entry points of every sampler package share: the view of a batch (`_edge_index_view`), where the outputs go and on
 which device and stream the job runs (`_out_opts`, `_select_device`), the two-phase call of uniform_sampler, rwr_sampler and
-epsilon_uniform_sampler (`run_job`), and their sample_graphs on top of it: one call over many graphs, graph g drawn from its own
+epsilon_uniform_sampler (`run_job`; `run_rows_job` where the begin reports its own row count), and their sample_graphs on top of it: one call over many graphs, graph g drawn from its own
 seed seeds[g] (C ABI: ugs_*_sample_graphs_begin in include/ugs_mi355.h, which states the law)."""
 import ctypes as C
 
@@ -94,6 +94,34 @@ def run_job(begin, finish, edge_index, ptr, m_per_graph, k, device=None):
         nodes = torch.empty((B, k), **opts)
         eidx = torch.empty((2, total.value), **opts)
         eptr = torch.empty((B + 1,), **opts)
+        sptr = torch.empty((G + 1,), **opts)
+        esrc = torch.empty((total.value,), **opts)
+    except BaseException:
+        lib.ugs_job_cancel(job)
+        raise
+    check(finish(job, nodes.data_ptr(), eidx.data_ptr(), eptr.data_ptr(), sptr.data_ptr(), esrc.data_ptr(), on_dev))
+    return nodes, eidx, eptr, sptr, esrc
+
+
+def run_rows_job(begin, finish, edge_index, ptr, k, device=None):
+    """run_job for a begin that reports its own row count (uniform_sampler.enumerate_graphs): `begin(batch, out)` gets
+    batch = (ei, row_stride, num_cols, ptr, G, k) and out = (job, rows, total); the five tensors are sized by rows and total.
+    Same placement and stream rules as run_job."""
+    check_int64(edge_index, ptr)
+    in_dev = torch.device(device) if device is not None else edge_index.device
+    keep, p, stride, e = _edge_index_view(edge_index.cpu())
+    pt = ptr.cpu().contiguous()
+    G = pt.numel() - 1
+    k = int(k)
+    dev = in_dev if in_dev.type == "cuda" else None
+    _select_device(dev, jobs=True)
+    job, rows, total = vp(), C.c_int64(), C.c_int64()
+    check(begin((p, stride, e, pt.data_ptr(), G, k), (C.byref(job), C.byref(rows), C.byref(total))))
+    try:
+        opts, on_dev = _out_opts(dev)
+        nodes = torch.empty((rows.value, k), **opts)
+        eidx = torch.empty((2, total.value), **opts)
+        eptr = torch.empty((rows.value + 1,), **opts)
         sptr = torch.empty((G + 1,), **opts)
         esrc = torch.empty((total.value,), **opts)
     except BaseException:

@@ -54,6 +54,10 @@ def _load():
         "ugs_rwr_sample_batch_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
         "ugs_uniform_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp,
                                             C.POINTER(vp), i64p],
+        "ugs_uniform_count_graphs": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int64, vp, vp],
+        "ugs_uniform_enumerate_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int64, vp,
+                                        C.POINTER(vp), i64p, i64p],
+        "ugs_uniform_enumerate_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
         "ugs_rwr_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
                                         C.POINTER(vp), i64p],
         "ugs_cache_clear": [],
