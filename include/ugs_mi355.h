@@ -362,6 +362,52 @@ int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, i
                                 ugs_job **job_out, int64_t *total_rows_out, int64_t *total_edges_out);
 int ugs_uniform_enumerate_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                  int64_t *edge_src, int dst_is_device);
+/* ---- uniform_sampler.PopulationCache: the populations S_g of a dataset's graphs, enumerated once and kept on the device; every
+ *      later sample call over any batch of those graphs is served from them and runs only column buckets, draws, rows and fill.
+ *      The law.  Let graph g of the batch (vertices ptr[g] ... ptr[g+1]-1) have the same vertex count and the same adjacency (as
+ *      a set of undirected non-loop pairs of local vertices) as the graph added under slots[g].  Then
+ *        - population_sample_begin with seeds == NULL, finished, gives the five tensors of ugs_uniform_sample_batch_begin for the same
+ *          edge_index, ptr, m, mode, seed and the population's k, bit for bit;
+ *        - with seeds != NULL it gives those of ugs_uniform_sample_graphs_begin, graph_status included.
+ *      The draws depend on the population only through |S_g|, which the slot holds; the vertex sets come from the slot's keys; edges
+ *      and edge_src come from the batch's own columns, so column order, duplicate columns, loops and columns that cross graphs are
+ *      treated as the uncached call treats them (items 1 and 5 of the law of ugs_uniform_sample_batch_begin).
+ *      One difference: the uncached call refuses a batch with more than 2^25 sets in all; a call served from a population holds no
+ *      key array of its own and does not refuse.
+ *      create(k, block_keys): no device work.  Storage is a list of device blocks of block_keys keys (1 ... 2^28) that are never moved
+ *      or reallocated; a graph's keys are contiguous in one block, a graph with more keys than a block gets a block of its own.  A
+ *      population belongs to the device of its first add.  destroy may be called with jobs in flight: the storage is freed when the
+ *      last of them has finished.
+ *      add: ugs_uniform_enumerate_begin's passes (count, scan, write, sorts; per-graph budget max_rows, 1 ... 2^25) over the given
+ *      batch, then a copy of each healthy graph's sorted keys into the storage, with a 64-bit fingerprint of its adjacency bitmap.
+ *      slots_out[g] is the graph's slot (slots are never reused; adding a graph again gives a new one).  graph_status[g] as
+ *      enumerate_begin sets it (1: refused for its size under the limit in force, 2: more than max_rows sets of its own): such a
+ *      graph gets a slot without keys, marked failed.  Healthy graphs with more than max_rows sets TOGETHER fail the call
+ *      (UGS_E_UNSUPPORTED, "split the call"; nothing is added).  Synchronous.  Adds take the population's lock exclusively and never
+ *      invalidate a job in flight; any number of threads may sample from one population at once.
+ *      sizes: |S_g| per slot, -1 for a failed one.  info: slots, keys held, bytes and blocks allocated (any may be NULL).
+ *      sample_begin checks, before any device work: every slot exists (UGS_E_BAD_ARG), ptr[g+1] - ptr[g] equals the slot's vertex
+ *      count (UGS_E_BAD_ARG, naming the graph and both counts), and, with seeds == NULL, no slot is a failed one (UGS_E_UNSUPPORTED
+ *      naming the graph, as the uncached call refuses it); with seeds != NULL a failed slot gives m rows of -1 and graph_status[g] = 1.
+ *      check != 0 also builds the batch's adjacency bitmaps and compares each graph's fingerprint with the slot's; the outcome
+ *      comes back in the status words read with the edge total, and a mismatch is UGS_E_BAD_ARG naming the first such graph.
+ *      check == 0 skips that stage: for a graph that is not the slot's the result is unspecified (never a fault: only the
+ *      vertex count bounds what the kernels index).  Same job protocol, stream rules and ugs_job_cancel as the other jobs;
+ *      population_sample_finish takes only a population job. */
+typedef struct ugs_uniform_population ugs_uniform_population;
+int ugs_uniform_population_create(int k, int64_t block_keys, ugs_uniform_population **pop_out);
+int ugs_uniform_population_destroy(ugs_uniform_population *pop);
+int ugs_uniform_population_add(ugs_uniform_population *pop, const int64_t *edge_index, int64_t row_stride, int64_t num_cols,
+                               const int64_t *ptr, int64_t num_graphs, int64_t max_rows, int64_t *slots_out, int32_t *graph_status);
+int ugs_uniform_population_sizes(ugs_uniform_population *pop, const int64_t *slots, int64_t num_graphs, int64_t *sizes_out);
+int ugs_uniform_population_info(ugs_uniform_population *pop, int64_t *slots_out, int64_t *keys_out, int64_t *bytes_out,
+                                int64_t *blocks_out);
+int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index,
+                                        int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph,
+                                        int mode, uint64_t seed, const uint64_t *seeds, int check, int32_t *graph_status,
+                                        ugs_job **job_out, int64_t *total_edges_out);
+int ugs_uniform_population_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                         int64_t *edge_src, int dst_is_device);
 /* Vertices per graph up to which ugs_uniform_* enumerates.  Default 64: every call behaves as it did before the wide form existed.
  * A caller whose graphs are larger (PROTEINS, IMDB-BINARY) raises it, to 1024 at most, once at start-up; nothing raises it
  * implicitly.  Results for graphs of at most 64 vertices never depend on it, and a call without wide graphs allocates and launches

@@ -282,6 +282,33 @@ hipError_t ugs_uniform_enum_keys(UgsUniCall &c, const UgsUniWide &w, hipStream_t
 hipError_t ugs_uniform_enum_rows(const UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
 hipError_t ugs_uniform_enum_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 
+// ---- the population cache (ugs_uniform_population_*): the sorted keys of a graph kept on the device across calls ----
+// A 64-bit fingerprint of a graph's adjacency: the sum over its non-zero bitmap words of a mix of (word, position), the bitmap being
+// n rows of W = ceil(n / 64) words in either form (W = 1: the mask form's adj).  Independent of column order and duplicates.
+// ugs_uniform_pop_store, behind enum_keys on the same stream: graph g's gsize[g] sorted keys go to dst[g] (nullptr: nothing to
+// copy) and its fingerprint to fp_out[g] (0 for a graph that is not enumerated).
+hipError_t ugs_uniform_pop_store(const UgsUniCall &c, const UgsUniWide &w, uint64_t *const *dst, uint64_t *fp_out, hipStream_t s);
+struct UgsPopGraph {
+    const uint64_t *keys; // the graph's |S_g| sorted keys in the population's storage (nullptr: S_g is empty or the graph failed)
+    int64_t lo;           // ptr[g]
+    uint64_t fp;          // fingerprint stored at add time
+    int32_t n, form, b;   // vertices; 1: mask keys, 2: wide keys of b-bit fields, 0: no keys
+};
+// A sample call served from a population.  `c` carries what the shared kernels read (uni_colgraph, uni_bucket, uni_draw /
+// uni_draw_graphs; with check: uni_adj / uni_wadj over c.graphs, c.adj, w.wbase, w.wadj); gsize comes from the host.  pair[p] =
+// u | v << 16, the local endpoints of sorted column p; rowkey[row] = the row's mask (mask form; 0: a row of -1) or key (wide).
+// status[2] = G - (first graph whose fingerprint differs), 0: none.
+struct UgsPopCall {
+    UgsUniCall c;
+    UgsUniWide w;
+    const UgsPopGraph *pg;                   // [G]
+    uint32_t *pair;                          // [E]
+    uint64_t *rowkey;                        // [rows]
+    int32_t check, any_wide;                 // any_wide: some graph of the batch has wide keys to draw from
+};
+hipError_t ugs_uniform_pop_begin(UgsPopCall &p, hipStream_t s);
+hipError_t ugs_uniform_pop_fill(const UgsPopCall &p, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+
 // ---- rwr_sampler (ugs_rwr.hip): random walk with restart, one SplitMix64 stream per graph, counter-based speculation ----
 #define UGS_RWR_KMAX 64
 struct UgsRwrGraph {

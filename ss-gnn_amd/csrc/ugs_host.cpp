@@ -16,12 +16,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <chrono>
 #include <functional>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <unordered_map>
 #include <thread>
@@ -2292,7 +2294,7 @@ int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len,
 // ---------------------------------------------------------------------------------------------------------------
 // What fills a side sampler's edge outputs at finish: edge_index [2, ld] and edge_src [ld] on the device, on the job's stream.
 using JobFill = std::function<hipError_t(int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s)>;
-enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR, UGS_JOB_UNIFORM_ENUM };
+enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR, UGS_JOB_UNIFORM_ENUM, UGS_JOB_UNIFORM_POP };
 
 struct ugs_job {
     ugs_plan *plan = nullptr;          // ugs jobs only
@@ -2981,12 +2983,16 @@ int ugs_uniform_set_mask_vertices(int n, int *previous) {
 // what = UNI_ENUMERATE / UNI_COUNT (ugs_uniform_enumerate_begin / ugs_uniform_count_graphs): no generator and no draws; `cap` (max_rows /
 // limit) takes the budget's place, per graph as in sample_graphs, graph_status[g] = 1 for a size refusal and 2 for a graph past cap.
 // UNI_ENUMERATE: m_per_graph = 0, one row per set, *rows_out = their number.  UNI_COUNT: no job; counts_out[g] = |S_g|, -1 where refused.
-enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT };
+// UNI_POPULATE (ugs_uniform_population_add): UNI_ENUMERATE up to its first read-back; `populate` then takes the sorted keys, and no job
+// is handed out.
+enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE };
+using UniPopulate = std::function<int(const UgsUniCall &c, const UgsUniWide &w, const std::vector<UgsUniGraph> &gd, const std::vector<int64_t> &gsize,
+                                      const int32_t *graph_status, const DeviceCtx &dc)>;
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
                          ugs_job **job_out, int64_t *total_edges_out, int what = UNI_SAMPLE, int64_t cap = UGS_UNI_BUDGET,
-                         int64_t *rows_out = nullptr, int64_t *counts_out = nullptr) {
-    if ((!job_out && what != UNI_COUNT) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
+                         int64_t *rows_out = nullptr, int64_t *counts_out = nullptr, const UniPopulate *populate = nullptr) {
+    if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
         return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     const bool per_graph = seeds != nullptr || what != UNI_SAMPLE;
@@ -3115,6 +3121,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
         if (status[1])
             return bail(fail(UGS_E_UNSUPPORTED, "uniform_sampler: the call's graphs together have " + std::to_string(status[0]) +
                                                 " connected k-subsets, more than max_rows = " + std::to_string(cap) + "; split the call"));
+        if (what == UNI_POPULATE) return bail((*populate)(c, w, gd, gsize, graph_status, dc));
         // sample_ptr: the sizes scanned in batch order (the keys lie in the order of the enumerated vertices, mask graphs first)
         j->sample_ptr.assign((size_t)G + 1, 0);
         for (int64_t g = 0; g < G; ++g) j->sample_ptr[(size_t)g + 1] = j->sample_ptr[(size_t)g] + (gsize.empty() ? 0 : gsize[(size_t)g]);
@@ -3191,6 +3198,264 @@ int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, i
 int ugs_uniform_enumerate_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr, int64_t *edge_src,
                                  int dst_is_device) {
     if (!job || job->kind != UGS_JOB_UNIFORM_ENUM) return fail(UGS_E_BAD_ARG, "not a uniform_sampler enumeration job");
+    return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
+}
+
+// ---- uniform_sampler.PopulationCache: every graph enumerated once, sample calls served from the stored keys (the law is stated in
+//      include/ugs_mi355.h at ugs_uniform_population_create) ----
+namespace {
+struct PopSlot {
+    const uint64_t *keys = nullptr;   // in a block of the population; nullptr: S_g is empty or the graph failed
+    int64_t size = 0;                 // |S_g|; -1: the graph failed at add time
+    uint64_t fp = 0;                  // fingerprint of its adjacency (ugs_device.h)
+    int32_t n = 0, form = 0, b = 0;   // vertices; 1: mask keys, 2: wide keys of b-bit fields, 0: not enumerated
+};
+struct PopBlock { uint64_t *p = nullptr; int64_t cap = 0, used = 0; };
+// Blocks are never moved or freed before the population dies, slots are only appended: what a job has read stays valid through any add.
+struct PopState {
+    int k = 0, dev = -1;
+    int64_t block_keys = 0, keys = 0, bytes = 0;
+    int cur = -1;                     // the block of block_keys keys that takes the next small graph
+    std::shared_mutex mu;             // adds: exclusive; sample begins, sizes, info: shared
+    std::deque<PopSlot> slots;
+    std::vector<PopBlock> blocks;
+    ~PopState() { for (PopBlock &b : blocks) (void)hipFree(b.p); }
+    // room for n keys, contiguous in one block (mu held exclusively)
+    int take(int64_t n, uint64_t **out) {
+        const bool own = n > block_keys;
+        if (own || cur < 0 || blocks[(size_t)cur].cap - blocks[(size_t)cur].used < n) {
+            PopBlock b;
+            b.cap = own ? n : block_keys;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.p), (size_t)b.cap * sizeof(uint64_t)));
+            blocks.push_back(b);
+            bytes += b.cap * (int64_t)sizeof(uint64_t);
+            if (own) { blocks.back().used = n; *out = b.p; return UGS_OK; }
+            cur = (int)blocks.size() - 1;
+        }
+        PopBlock &b = blocks[(size_t)cur];
+        *out = b.p + b.used;
+        b.used += n;
+        return UGS_OK;
+    }
+};
+}  // namespace
+struct ugs_uniform_population { std::shared_ptr<PopState> st; };
+
+int ugs_uniform_population_create(int k, int64_t block_keys, ugs_uniform_population **pop_out) {
+    if (!pop_out) return fail(UGS_E_BAD_ARG, "pop_out is null");
+    if (k < 0) return fail(UGS_E_BAD_ARG, "k must be >= 0");
+    if (block_keys < 1 || block_keys > ((int64_t)1 << 28))
+        return fail(UGS_E_BAD_ARG, "block_keys must be 1 ... 2^28 (got " + std::to_string(block_keys) + ")");
+    auto *p = new ugs_uniform_population();
+    p->st = std::make_shared<PopState>();
+    p->st->k = k; p->st->block_keys = block_keys;
+    *pop_out = p;
+    return UGS_OK;
+}
+
+int ugs_uniform_population_destroy(ugs_uniform_population *pop) {
+    delete pop;                                                          // the storage goes with the last job that samples from it
+    return UGS_OK;
+}
+
+int ugs_uniform_population_add(ugs_uniform_population *pop, const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                               int64_t num_graphs, int64_t max_rows, int64_t *slots_out, int32_t *graph_status) {
+    if (!pop) return fail(UGS_E_BAD_ARG, "population is null");
+    if (max_rows < 1 || max_rows > UGS_UNI_BUDGET) return fail(UGS_E_BAD_ARG, "max_rows must be 1 ... 2^25 (got " + std::to_string(max_rows) + ")");
+    if (num_graphs > 0 && (!slots_out || !graph_status)) return fail(UGS_E_BAD_ARG, "population add needs slots_out and graph_status");
+    PopState &st = *pop->st;
+    const int64_t G = num_graphs;
+    const UniPopulate store = [&](const UgsUniCall &c, const UgsUniWide &w, const std::vector<UgsUniGraph> &gd, const std::vector<int64_t> &gsize,
+                                  const int32_t *status, const DeviceCtx &dc) -> int {
+        std::unique_lock<std::shared_mutex> lk(st.mu);
+        if (st.dev >= 0 && st.dev != dc.id)
+            return fail(UGS_E_BAD_ARG, "the population lives on device " + std::to_string(st.dev) + ", this add runs on device " + std::to_string(dc.id));
+        st.dev = dc.id;
+        // host side of the copy: per graph the destination of its keys, then the fingerprints come back
+        std::vector<uint64_t *> dst((size_t)G, nullptr);
+        for (int64_t g = 0; g < G; ++g) {
+            const int64_t sz = status[g] || gsize.empty() ? 0 : gsize[(size_t)g];
+            if (sz > 0) if (int rc = st.take(sz, &dst[(size_t)g])) return rc;
+        }
+        PoolBuf tab;                                                     // dst [G] and the fingerprints [G]
+        if (int rc = pool_get((size_t)G * 16, dc.id, tab)) return rc;
+        auto **d_dst = static_cast<uint64_t **>(tab.p);
+        auto *d_fp = reinterpret_cast<uint64_t *>(d_dst + G);
+        std::vector<uint64_t> fp((size_t)G, 0);
+        hipError_t e = hipMemcpyAsync(d_dst, dst.data(), (size_t)G * 8, hipMemcpyHostToDevice, dc.stream);
+        if (e == hipSuccess) e = ugs_uniform_pop_store(c, w, d_dst, d_fp, dc.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(fp.data(), d_fp, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
+        pool_put(tab);
+        if (e != hipSuccess) return fail_hip(e, "uniform_sampler population add");
+        for (int64_t g = 0; g < G; ++g) {
+            PopSlot s;
+            const UgsUniGraph &d = gd[(size_t)g];
+            s.n = d.n;
+            if (status[g]) s.size = -1;
+            else {
+                s.form = d.enumerable; s.fp = fp[(size_t)g];
+                s.size = gsize.empty() ? 0 : gsize[(size_t)g];
+                s.keys = dst[(size_t)g];
+                int b = 1;
+                while (b < 16 && (1 << b) < d.n) ++b;
+                s.b = b;
+                st.keys += s.size;
+            }
+            slots_out[g] = (int64_t)st.slots.size();
+            st.slots.push_back(s);
+        }
+        return UGS_OK;
+    };
+    if (G == 0) return UGS_OK;
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, G, 0, st.k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_POPULATE, max_rows,
+                         nullptr, nullptr, &store);
+}
+
+int ugs_uniform_population_sizes(ugs_uniform_population *pop, const int64_t *slots, int64_t num_graphs, int64_t *sizes_out) {
+    if (!pop || (num_graphs > 0 && (!slots || !sizes_out))) return fail(UGS_E_BAD_ARG, "bad arguments to population sizes");
+    PopState &st = *pop->st;
+    std::shared_lock<std::shared_mutex> lk(st.mu);
+    for (int64_t g = 0; g < num_graphs; ++g) {
+        if (slots[g] < 0 || slots[g] >= (int64_t)st.slots.size()) return fail(UGS_E_BAD_ARG, "unknown population slot " + std::to_string(slots[g]));
+        sizes_out[g] = st.slots[(size_t)slots[g]].size;
+    }
+    return UGS_OK;
+}
+
+int ugs_uniform_population_info(ugs_uniform_population *pop, int64_t *slots_out, int64_t *keys_out, int64_t *bytes_out, int64_t *blocks_out) {
+    if (!pop) return fail(UGS_E_BAD_ARG, "population is null");
+    PopState &st = *pop->st;
+    std::shared_lock<std::shared_mutex> lk(st.mu);
+    if (slots_out) *slots_out = (int64_t)st.slots.size();
+    if (keys_out) *keys_out = st.keys;
+    if (bytes_out) *bytes_out = st.bytes;
+    if (blocks_out) *blocks_out = (int64_t)st.blocks.size();
+    return UGS_OK;
+}
+
+int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                                        int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, uint64_t seed,
+                                        const uint64_t *seeds, int check, int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out) {
+    if (!pop || !job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+    if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
+    if (num_graphs > 0 && !slots) return fail(UGS_E_BAD_ARG, "population sample needs one slot per graph");
+    if (seeds && num_graphs > 0 && !graph_status) return fail(UGS_E_BAD_ARG, "sample_graphs needs seeds and graph_status");
+    if (num_graphs >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
+    if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
+    if (num_cols >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: columns must be < 2^31 - 1");
+    const std::shared_ptr<PopState> stp = pop->st;
+    PopState &st = *stp;
+    const int64_t G = num_graphs, E = num_cols;
+    const int k = st.k;
+    // the slots of the batch, read under the shared lock; everything they point at outlives the job
+    std::vector<UgsPopGraph> pg((size_t)G);
+    std::vector<UgsUniGraph> gd((size_t)G);
+    std::vector<int64_t> gsize((size_t)G, 0), wbase;
+    int64_t nv = 0, nv_wide = 0, adj_words = 0;
+    bool any_wide = false;
+    int pop_dev = -1;
+    {
+        std::shared_lock<std::shared_mutex> lk(st.mu);
+        pop_dev = st.dev;
+        for (int64_t g = 0; g < G; ++g) {
+            if (slots[g] < 0 || slots[g] >= (int64_t)st.slots.size()) return fail(UGS_E_BAD_ARG, "unknown population slot " + std::to_string(slots[g]));
+            const PopSlot &s = st.slots[(size_t)slots[g]];
+            const int64_t n = ptr[g + 1] - ptr[g];
+            if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
+            if (n != s.n)
+                return fail(UGS_E_BAD_ARG, "uniform_sampler population: graph " + std::to_string(g) + " of the batch has " + std::to_string(n) +
+                                               " vertices, the graph added in its place has " + std::to_string(s.n));
+            if (s.size < 0 && !seeds)
+                return fail(UGS_E_UNSUPPORTED, "uniform_sampler population: graph " + std::to_string(g) +
+                                                   " of the batch failed when it was added (its size or its number of connected k-subsets)");
+            if (graph_status) graph_status[g] = s.size < 0 ? 1 : 0;
+            UgsPopGraph &d = pg[(size_t)g];
+            d.keys = s.keys; d.lo = ptr[g]; d.fp = s.fp; d.n = s.n; d.form = s.size < 0 ? 0 : s.form; d.b = s.b;
+            gsize[(size_t)g] = s.size > 0 ? s.size : 0;
+            any_wide = any_wide || (d.form == 2 && s.size > 0);
+            UgsUniGraph &u = gd[(size_t)g];
+            u.lo = ptr[g]; u.n = s.n; u.vbase = 0; u.enumerable = d.form;
+            if (d.form == 1) { u.vbase = nv; nv += s.n; }
+            if (d.form == 2) nv_wide += s.n;
+        }
+    }
+    const int64_t nv_mask = nv;
+    const bool wide = check && nv_wide > 0;                              // only the check builds bitmaps
+    if (wide) wbase.assign((size_t)G, -1);
+    for (int64_t g = 0; g < G; ++g) {
+        UgsUniGraph &u = gd[(size_t)g];
+        if (u.enumerable != 2) continue;
+        u.vbase = nv; nv += u.n;
+        if (wide) { wbase[(size_t)g] = adj_words; adj_words += (int64_t)u.n * ((u.n + 63) / 64); }
+    }
+    DeviceCtx dc;
+    if (int rc = device_ctx(dc)) return rc;
+    if (pop_dev >= 0 && pop_dev != dc.id)
+        return fail(UGS_E_BAD_ARG, "the population lives on device " + std::to_string(pop_dev) + ", this call runs on device " + std::to_string(dc.id));
+    const int64_t rows = G * (int64_t)m_per_graph;
+    BlobLayout L;
+    auto take = [&](size_t bytes) { return L.take(bytes); };
+    const BatchInputs in(L, E, G, sizeof(UgsUniGraph), seeds != nullptr);
+    const size_t o_pg = take((size_t)G * sizeof(UgsPopGraph)), o_gz = take((size_t)G * 8), o_wb = wide ? take((size_t)G * 8) : 0;
+    L.end_inputs();
+    const size_t cub_bytes = ugs_uniform_cub_bytes(E, 0, 0);
+    const size_t o_cub = take(cub_bytes), o_ck = take((size_t)E * 4), o_ck2 = take((size_t)E * 4), o_cv = take((size_t)E * 4),
+                 o_cv2 = take((size_t)E * 4), o_cst = take((size_t)(G + 1) * 8), o_pair = take((size_t)E * 4), o_status = take(4 * 8),
+                 o_np = take((size_t)G * 4), o_nl = take((size_t)G * 4), o_dr = take((size_t)rows * 4), o_rk = take((size_t)rows * 8),
+                 o_ec = take((size_t)rows * 4), o_st = take((size_t)ugs_scan_tmp_words(rows) * 8);
+    const size_t o_bp = check ? take((size_t)E * 2) : 0, o_adj = check ? take((size_t)nv * 8) : 0, o_wadj = wide ? take((size_t)adj_words * 8) : 0;
+    std::vector<char> host(L.in_bytes, 0);
+    in.stage(host.data(), edge_index, row_stride, E, ptr, G, gd.data(), sizeof(UgsUniGraph), seeds);
+    if (G > 0) std::memcpy(host.data() + o_pg, pg.data(), (size_t)G * sizeof(UgsPopGraph));
+    if (G > 0) std::memcpy(host.data() + o_gz, gsize.data(), (size_t)G * 8);
+    if (wide) std::memcpy(host.data() + o_wb, wbase.data(), (size_t)G * 8);
+    ugs_job *j = nullptr;
+    if (int rc = side_job(dc, UGS_JOB_UNIFORM_POP, G, m_per_graph, k, mode, L.off, &j)) return rc;
+    char *b = static_cast<char *>(j->blob.p);
+    UgsPopCall p{};
+    UgsUniCall &c = p.c;
+    c.G = G; c.E = E; c.nv = check ? nv : 0; c.rows = rows; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
+    c.seeds = seeds ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
+    c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
+    c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + in.desc);
+    c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
+    c.ckey = reinterpret_cast<uint32_t *>(b + o_ck); c.ckey2 = reinterpret_cast<uint32_t *>(b + o_ck2);
+    c.cval = reinterpret_cast<int32_t *>(b + o_cv); c.cval2 = reinterpret_cast<int32_t *>(b + o_cv2);
+    c.cstart = reinterpret_cast<int64_t *>(b + o_cst); c.status = reinterpret_cast<int64_t *>(b + o_status);
+    c.gsize = reinterpret_cast<int64_t *>(b + o_gz);
+    c.nepos = reinterpret_cast<int32_t *>(b + o_np); c.ne_list = reinterpret_cast<int32_t *>(b + o_nl);
+    c.draws = reinterpret_cast<int32_t *>(b + o_dr); c.ecount = reinterpret_cast<uint32_t *>(b + o_ec);
+    c.scan_tmp = reinterpret_cast<int64_t *>(b + o_st);
+    c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    p.pg = reinterpret_cast<const UgsPopGraph *>(b + o_pg);
+    p.pair = reinterpret_cast<uint32_t *>(b + o_pair); p.rowkey = reinterpret_cast<uint64_t *>(b + o_rk);
+    p.check = check ? 1 : 0; p.any_wide = any_wide ? 1 : 0;
+    p.w.nv_mask = check ? nv_mask : 0; p.w.adj_words = adj_words;
+    if (check) {
+        c.bpair = reinterpret_cast<uint16_t *>(b + o_bp); c.adj = reinterpret_cast<uint64_t *>(b + o_adj);
+    }
+    if (wide) {
+        p.w.wbase = reinterpret_cast<const int64_t *>(b + o_wb); p.w.wadj = reinterpret_cast<uint64_t *>(b + o_wadj);
+        p.w.wpair = p.pair;                                              // uni_wadj writes the wide columns' pairs again, the same values
+    }
+    int64_t status[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemcpyAsync(b, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
+    if (e == hipSuccess) e = ugs_uniform_pop_begin(p, dc.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
+    if (int rc = side_job_total(j, e, "uniform_sampler population pipeline")) return rc;
+    if (status[2]) {
+        free_job(j);
+        return fail(UGS_E_BAD_ARG, "uniform_sampler population: graph " + std::to_string(G - status[2]) +
+                                       " of the batch does not have the adjacency of the graph added in its place");
+    }
+    j->fill = [p, stp](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_uniform_pop_fill(p, edge_index, edge_src, ld, s); };
+    return hand_out(j, job_out, total_edges_out);
+}
+
+int ugs_uniform_population_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
+                                         int64_t *edge_src, int dst_is_device) {
+    if (!job || job->kind != UGS_JOB_UNIFORM_POP) return fail(UGS_E_BAD_ARG, "not a uniform_sampler population job");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src, dst_is_device);
 }
 

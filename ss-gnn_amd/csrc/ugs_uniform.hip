@@ -29,6 +29,13 @@
 //   uni_wesu<COUNT / WRITE>     the same search, one 16-lane group (a DPP row) per item, lane l holding word l of every set
 //   uni_wrows / uni_wfill       the tuple decoded from the key; the mask form's kernels see these graphs as empty
 // A call without wide graphs launches none of these.
+//
+// Population cache (ugs_uniform_population_*): uni_prepare runs once per dataset graph and uni_pop_store keeps its sorted keys, with
+// a fingerprint of its adjacency; a sample call served from them runs only
+//   uni_colgraph + radix sort, uni_bucket, uni_pop_pairs     column buckets and the local endpoints of every sorted column
+//   uni_adj / uni_wadj + uni_pop_check                        (check only) the batch's adjacency against the stored fingerprints
+//   uni_draw / uni_draw_graphs                                from the sizes the host staged
+//   uni_pop_rows / uni_wpop_rows + scan, uni_pop_fill / uni_wpop_fill (finish)    a 16-lane group per row
 #include "ugs_device.h"
 
 #include <hipcub/hipcub.hpp>
@@ -710,6 +717,200 @@ __global__ void uni_wenum_fill(UgsUniCall c, UgsUniWide wd, int64_t *edge_index,
     }
 }
 
+// ---- population cache (ugs_uniform_population_*): the keys of a graph are enumerated once, by uni_prepare, and kept; a sample call
+//      served from them runs column buckets, draws, rows and fill only.  Rows and fill give every row a 16-lane group (one DPP row,
+//      as uni_wesu does): lane l takes the columns l, l + 16, ... of the graph's bucket, the row's edge count is the row-wide sum, and
+//      the fill keeps bucket order by writing each lane's hit at the row-wide exclusive prefix, chunk of 16 columns after chunk. ----
+constexpr int POP_LANES = 16;
+constexpr int POP_GROUPS = UNI_BLOCK / POP_LANES;
+
+__device__ __forceinline__ uint64_t fp_mix(uint64_t word, uint64_t pos) {          // SplitMix64's finaliser over (word, position)
+    uint64_t x = word + 0x9E3779B97F4A7C15ull * (pos + 1);
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// fingerprint of graph g's adjacency bitmap (ugs_device.h), by all UNI_BLOCK lanes of a workgroup; 0 for a graph without one
+__device__ uint64_t pop_fingerprint(const UgsUniCall &c, const UgsUniWide &w, int64_t g, uint64_t *s_sum) {
+    const UgsUniGraph gd = c.graphs[g];
+    uint64_t acc = 0;
+    if (gd.enumerable) {
+        const int64_t words = gd.enumerable == 1 ? (int64_t)gd.n : (int64_t)gd.n * ((gd.n + 63) >> 6);
+        const uint64_t *bm = gd.enumerable == 1 ? c.adj + gd.vbase : w.wadj + w.wbase[g];
+        for (int64_t i = threadIdx.x; i < words; i += UNI_BLOCK) { const uint64_t x = bm[i]; if (x) acc += fp_mix(x, (uint64_t)i); }
+    }
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = UNI_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) s_sum[threadIdx.x] += s_sum[threadIdx.x + off];
+        __syncthreads();
+    }
+    return s_sum[0];
+}
+
+// add: workgroups (g, 0 ... gridDim.y - 1) copy graph g's sorted keys into the population's storage; workgroup (g, 0) writes its fingerprint
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_store(UgsUniCall c, UgsUniWide w, uint64_t *const *dst, uint64_t *fp_out) {
+    __shared__ uint64_t s_sum[UNI_BLOCK];
+    const int64_t g = blockIdx.x;
+    uint64_t *const out = dst[g];
+    if (out) {
+        const uint64_t *in = c.keys_sorted + c.gstart[g];
+        const int64_t n = c.gsize[g];
+        for (int64_t i = (int64_t)blockIdx.y * UNI_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.y * UNI_BLOCK) out[i] = in[i];
+    }
+    if (blockIdx.y == 0) {
+        const uint64_t fp = pop_fingerprint(c, w, g, s_sum);
+        if (threadIdx.x == 0) fp_out[g] = fp;
+    }
+}
+
+__global__ void uni_pop_pairs(UgsPopCall p) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= p.c.E) return;
+    const uint32_t g = p.c.ckey2[q];
+    if (g >= (uint32_t)p.c.G) return;
+    const int64_t col = p.c.cval2[q], lo = p.pg[g].lo;
+    p.pair[q] = (uint32_t)(p.c.src[col] - lo) | ((uint32_t)(p.c.dst[col] - lo) << 16);   // both inside [0, n), n <= 1024 (uni_colgraph)
+}
+
+// check: one workgroup per graph compares the batch's adjacency with the fingerprint stored at add time
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_check(UgsPopCall p) {
+    __shared__ uint64_t s_sum[UNI_BLOCK];
+    const int64_t g = blockIdx.x;
+    const uint64_t fp = pop_fingerprint(p.c, p.w, g, s_sum);
+    if (threadIdx.x == 0 && p.pg[g].form != 0 && fp != p.pg[g].fp)
+        atomicMax((unsigned long long *)&p.c.status[2], (unsigned long long)(p.c.G - g));
+}
+
+// the drawn key of a row, or false: the graph has nothing to draw from (a row of -1)
+__device__ __forceinline__ bool pop_key(const UgsPopCall &p, const UgsPopGraph &pg, int64_t row, int64_t g, uint64_t &key) {
+    if (p.c.gsize[g] <= 0) return false;
+    const int64_t d = p.c.seeds ? row : (int64_t)p.c.nepos[g] * p.c.m + (row - g * p.c.m);
+    key = pg.keys[p.c.draws[d]];
+    return true;
+}
+
+// rows of the mask form and the rows of -1: lane l writes the members among the vertices 4 l ... 4 l + 3
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_rows(UgsPopCall p) {
+    const UgsUniCall &c = p.c;
+    const int64_t row = (int64_t)blockIdx.x * POP_GROUPS + threadIdx.x / POP_LANES;
+    if (row >= c.rows) return;
+    const int l = threadIdx.x & (POP_LANES - 1);
+    const int64_t g = row / c.m;
+    const UgsPopGraph pg = p.pg[g];
+    uint64_t key = 0;
+    const bool live = pop_key(p, pg, row, g, key);
+    if (live && pg.form == 2) return;                               // uni_wpop_rows
+    const uint64_t mask = live ? mask_of(key) : 0ull;
+    if (l == 0) p.rowkey[row] = mask;
+    int64_t *out = c.nodes + row * c.k;
+    uint32_t cnt = 0;
+    if (mask) {
+        int j = __popcll(mask & ((1ull << (4 * l)) - 1));
+        for (uint32_t e = (uint32_t)(mask >> (4 * l)) & 15u; e; e &= e - 1) out[j++] = pg.lo + 4 * l + (__ffs(e) - 1);
+        for (int64_t q = c.cstart[g] + l; q < c.cstart[g + 1]; q += POP_LANES) {
+            const uint32_t uv = p.pair[q];
+            cnt += (uint32_t)((mask >> (uv & 63)) & (mask >> ((uv >> 16) & 63)) & 1);
+        }
+    } else {
+        for (int j = l; j < c.k; j += POP_LANES) out[j] = -1;
+    }
+    const uint32_t tot = row_scan(cnt);
+    if (l == POP_LANES - 1) c.ecount[row] = tot;
+}
+
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_fill(UgsPopCall p, int64_t *edge_index, int64_t *edge_src, int64_t ld) {
+    const UgsUniCall &c = p.c;
+    const int64_t row = (int64_t)blockIdx.x * POP_GROUPS + threadIdx.x / POP_LANES;
+    if (row >= c.rows) return;
+    const int l = threadIdx.x & (POP_LANES - 1);
+    const int64_t g = row / c.m;
+    const UgsPopGraph pg = p.pg[g];
+    if (pg.form == 2 && c.gsize[g] > 0) return;                     // uni_wpop_fill
+    const uint64_t mask = p.rowkey[row];
+    if (!mask) return;
+    int64_t w = c.edge_ptr[row];
+    const int64_t end = c.cstart[g + 1];
+    for (int64_t base = c.cstart[g]; base < end; base += POP_LANES) {   // (the trip count is the group's)
+        const int64_t q = base + l;
+        uint32_t hit = 0;
+        int u = 0, v = 0;
+        if (q < end) {
+            const uint32_t uv = p.pair[q];
+            u = uv & 63; v = (uv >> 16) & 63;
+            hit = (uint32_t)((mask >> u) & (mask >> v) & 1);
+        }
+        const uint32_t incl = row_scan(hit);
+        if (hit) {
+            const int64_t o = w + (incl - hit);                     // hits of the lanes below: bucket order
+            if (c.mode == 0) {
+                edge_index[o] = __popcll(mask & ((1ull << u) - 1));
+                edge_index[ld + o] = __popcll(mask & ((1ull << v) - 1));
+            } else {
+                edge_index[o] = pg.lo + u;
+                edge_index[ld + o] = pg.lo + v;
+            }
+            edge_src[o] = c.cval2[q];
+        }
+        w += (uint32_t)__shfl((int)incl, POP_LANES - 1, POP_LANES);
+    }
+}
+
+// rows of the wide graphs that have keys: lane j < k writes field j
+__global__ __launch_bounds__(UNI_BLOCK) void uni_wpop_rows(UgsPopCall p) {
+    const UgsUniCall &c = p.c;
+    const int64_t row = (int64_t)blockIdx.x * POP_GROUPS + threadIdx.x / POP_LANES;
+    if (row >= c.rows) return;
+    const int l = threadIdx.x & (POP_LANES - 1);
+    const int64_t g = row / c.m;
+    const UgsPopGraph pg = p.pg[g];
+    uint64_t key = 0;
+    if (pg.form != 2 || !pop_key(p, pg, row, g, key)) return;       // uni_pop_rows has the row
+    if (l == 0) p.rowkey[row] = key;
+    const int k = c.k, b = pg.b;
+    if (l < k) c.nodes[row * k + l] = pg.lo + (int64_t)((key >> (b * (k - 1 - l))) & ((1ull << b) - 1));
+    uint32_t cnt = 0;
+    for (int64_t q = c.cstart[g] + l; q < c.cstart[g + 1]; q += POP_LANES) {
+        const uint32_t uv = p.pair[q];
+        cnt += tuple_pos(key, k, b, uv & 0xFFFFu) >= 0 && tuple_pos(key, k, b, uv >> 16) >= 0 ? 1u : 0u;
+    }
+    const uint32_t tot = row_scan(cnt);
+    if (l == POP_LANES - 1) c.ecount[row] = tot;
+}
+
+__global__ __launch_bounds__(UNI_BLOCK) void uni_wpop_fill(UgsPopCall p, int64_t *edge_index, int64_t *edge_src, int64_t ld) {
+    const UgsUniCall &c = p.c;
+    const int64_t row = (int64_t)blockIdx.x * POP_GROUPS + threadIdx.x / POP_LANES;
+    if (row >= c.rows) return;
+    const int l = threadIdx.x & (POP_LANES - 1);
+    const int64_t g = row / c.m;
+    const UgsPopGraph pg = p.pg[g];
+    if (pg.form != 2 || c.gsize[g] <= 0) return;
+    const int k = c.k, b = pg.b;
+    const uint64_t key = p.rowkey[row];
+    int64_t w = c.edge_ptr[row];
+    const int64_t end = c.cstart[g + 1];
+    for (int64_t base = c.cstart[g]; base < end; base += POP_LANES) {
+        const int64_t q = base + l;
+        uint32_t hit = 0, uv = 0;
+        int pu = -1, pv = -1;
+        if (q < end) {
+            uv = p.pair[q];
+            pu = tuple_pos(key, k, b, uv & 0xFFFFu); pv = tuple_pos(key, k, b, uv >> 16);
+            hit = pu >= 0 && pv >= 0 ? 1u : 0u;
+        }
+        const uint32_t incl = row_scan(hit);
+        if (hit) {
+            const int64_t o = w + (incl - hit);
+            edge_index[o] = c.mode == 0 ? (int64_t)pu : pg.lo + (int64_t)(uv & 0xFFFFu);
+            edge_index[ld + o] = c.mode == 0 ? (int64_t)pv : pg.lo + (int64_t)(uv >> 16);
+            edge_src[o] = c.cval2[q];
+        }
+        w += (uint32_t)__shfl((int)incl, POP_LANES - 1, POP_LANES);
+    }
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace
@@ -820,5 +1021,54 @@ hipError_t ugs_uniform_enum_fill(const UgsUniCall &c, const UgsUniWide &w, int64
     if (c.rows <= 0) return hipSuccess;
     if (w.nv_mask > 0) hipLaunchKernelGGL(uni_enum_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, edge_index, edge_src, ld);
     if (c.nv > w.nv_mask) hipLaunchKernelGGL(uni_wenum_fill, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w, edge_index, edge_src, ld);
+    return hipGetLastError();
+}
+
+// ---- population cache ----
+hipError_t ugs_uniform_pop_store(const UgsUniCall &c, const UgsUniWide &w, uint64_t *const *dst, uint64_t *fp_out, hipStream_t s) {
+    if (c.G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(uni_pop_store, dim3((unsigned)c.G, 32), dim3(UNI_BLOCK), 0, s, c, w, dst, fp_out);
+    return hipGetLastError();
+}
+
+hipError_t ugs_uniform_pop_begin(UgsPopCall &p, hipStream_t s) {
+    UgsUniCall &c = p.c;
+    hipError_t e = hipMemsetAsync(c.status, 0, 4 * sizeof(int64_t), s);
+    if (e != hipSuccess) return e;
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) <= c.G) ++bits;                   // keys 0..G
+    if (c.E > 0) {
+        hipLaunchKernelGGL(uni_colgraph, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+        size_t tb = c.cub_bytes;
+        e = hipcub::DeviceRadixSort::SortPairs(c.cub_tmp, tb, c.ckey, c.ckey2, c.cval, c.cval2, (int)c.E, 0, bits, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(uni_bucket, dim3(blocks(c.G + 1, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+    if (c.E > 0) hipLaunchKernelGGL(uni_pop_pairs, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, p);
+    if (p.check && c.G > 0) {                                                  // the batch's adjacency, as uni_prepare builds it
+        if (c.nv > 0) {
+            if ((e = hipMemsetAsync(c.adj, 0, (size_t)c.nv * sizeof(uint64_t), s)) != hipSuccess) return e;
+            if (c.E > 0) hipLaunchKernelGGL(uni_adj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);
+            if (c.nv > p.w.nv_mask) {
+                if ((e = hipMemsetAsync(p.w.wadj, 0, (size_t)p.w.adj_words * sizeof(uint64_t), s)) != hipSuccess) return e;
+                if (c.E > 0) hipLaunchKernelGGL(uni_wadj, dim3(blocks(c.E, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, p.w);
+            }
+        }
+        hipLaunchKernelGGL(uni_pop_check, dim3((unsigned)c.G), dim3(UNI_BLOCK), 0, s, p);
+    }
+    if (c.G > 0) {
+        if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
+        else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
+    }
+    if (c.rows > 0) hipLaunchKernelGGL(uni_pop_rows, dim3(blocks(c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p);
+    if (c.rows > 0 && p.any_wide) hipLaunchKernelGGL(uni_wpop_rows, dim3(blocks(c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return ugs_launch_scan(c.ecount, c.rows, c.edge_ptr, c.scan_tmp, s);
+}
+
+hipError_t ugs_uniform_pop_fill(const UgsPopCall &p, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {
+    if (p.c.rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(uni_pop_fill, dim3(blocks(p.c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p, edge_index, edge_src, ld);
+    if (p.any_wide) hipLaunchKernelGGL(uni_wpop_fill, dim3(blocks(p.c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p, edge_index, edge_src, ld);
     return hipGetLastError();
 }

@@ -58,6 +58,14 @@ def _load():
         "ugs_uniform_enumerate_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int64, vp,
                                         C.POINTER(vp), i64p, i64p],
         "ugs_uniform_enumerate_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
+        "ugs_uniform_population_create": [C.c_int, C.c_int64, C.POINTER(vp)],
+        "ugs_uniform_population_destroy": [vp],
+        "ugs_uniform_population_add": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp],
+        "ugs_uniform_population_sizes": [vp, vp, C.c_int64, vp],
+        "ugs_uniform_population_info": [vp, i64p, i64p, i64p, i64p],
+        "ugs_uniform_population_sample_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp,
+                                                C.POINTER(vp), i64p],
+        "ugs_uniform_population_sample_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
         "ugs_rwr_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
                                         C.POINTER(vp), i64p],
         "ugs_cache_clear": [],
