@@ -145,6 +145,11 @@ int ugs_sample_stream(int64_t handle, int m_per_graph, int k, int edge_mode, int
  * start: early starts that stood / that were thrown away.  UGS_NO_SPECULATION set = always look up first.  ugs_sample_batch_begin does
  * the same for batches of >= 2^21 columns (UGS_SPEC_MIN_COLS overrides the threshold: testing aid) and counts here too. */
 int ugs_stream_stats(int64_t *early_starts_kept, int64_t *early_starts_discarded);
+/* ugs_sample_batch_begin / ugs_sample_graphs_begin run the step of a batch of small graphs at begin, walk + fill into one staging area
+ * sized for 2 k (k - 1) edge entries per row (the packed step).  Counters since process start, bumped once per such step when its
+ * total is known: steps whose outputs fitted the staging (finish only copies out) / steps the kernel refused because repeated columns
+ * pushed the total above the staging (the kernel wrote no edge entry, finish fills the ordinary way).  Either pointer may be NULL. */
+int ugs_step_stats(int64_t *packed_staged, int64_t *packed_refused);
 
 /* LRU of preprocessing handles used by ugs_sample_batch_* (capacity from UGS_CACHE_SIZE, default 1000;
  * reference src/ugs_sampler_batch_extension.cpp:15-38).  Clearing it is the equivalent of a fresh process. */
@@ -206,8 +211,9 @@ int ugs_plan_fill(ugs_plan *plan, int m_per_graph, int k, int mode, int64_t extr
 /* Walk + fill of the same rows as ONE call, for callers that hand over edge buffers of capacity ld up front (no host read-back
  * of the total in between: d_edge_ptr[row_count] holds it afterwards).  Same outputs as ugs_plan_walk followed by ugs_plan_fill
  * (reference src/sampler.cpp:91-290).  Knowing that nobody reads edge_ptr between the two phases, the step of a batch of small
- * graphs runs in two launches instead of three: the fill kernel scans the per-row counts itself (decoupled look-back over tiles
- * of 32 rows; `UGS_NO_FUSED_SCAN` set = the three-launch form).
+ * graphs of up to 131 072 rows runs in two launches instead of three: the fill kernel scans the per-row counts itself.  A block takes
+ * tiles of 32 rows and adds up what lies in front of a tile from the sums of 8 rows that the walk kernel left beside the counts; no
+ * block waits for or talks to another (`UGS_NO_FUSED_SCAN` set = the three-launch form).
  * Concurrent use: several threads may step, walk and fill through one plan (or through plans that the plan cache shares, e.g. two
  * ugs_plan_create_batch of the same batch) at the same time, on one stream or on several; the calls are serialised through the
  * plan's scratch and each gets its own correct outputs.  A step holds the plan's lock from its walk to its fill.  Steps that should
@@ -237,6 +243,11 @@ int ugs_plan_graph_destroy(ugs_graph *graph);
  * (grid, block, LDS bytes) -- used by bench.py to label its roofline line. */
 int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len, int *grid, int *block,
                          int *lds_bytes, int64_t *overflow_rows);
+/* The same for the fill: name, grid and block of the kernel that the last ugs_plan_fill, ugs_plan_step or packed step on this plan
+ * launched to write the edge outputs ("ugs_fill<8>", "ugs_fill<64>", "ugs_fill_scan<8>"; empty before the first).  A fill that
+ * expands the rows the walk staged (ugs_fill_staged) and then reads the leftover rows reports the leftover kernel, the second of its
+ * two launches.  Testing aid: which form of the step ran is not visible in its outputs.  Any out pointer may be NULL. */
+int ugs_plan_last_fill(const ugs_plan *plan, char *name_buf, int name_buf_len, int *grid, int *block);
 
 /* ---- collation of a sharded batch (multi-GPU: SURVEY.md section 8(e); the reference is single-process and has no counterpart).
  *      Rank r samples the contiguous row range [row_off[r], row_off[r+1]) of the G*m rows; the finished batch is collated on

@@ -2287,6 +2287,14 @@ int ugs_plan_last_launch(const ugs_plan *plan, char *name_buf, int name_buf_len,
     return UGS_OK;
 }
 
+int ugs_plan_last_fill(const ugs_plan *plan, char *name_buf, int name_buf_len, int *grid, int *block) {
+    if (!plan) return fail(UGS_E_BAD_ARG, "plan is null");
+    if (name_buf && name_buf_len > 0) { std::snprintf(name_buf, (size_t)name_buf_len, "%s", plan->last_fill.name ? plan->last_fill.name : ""); }
+    if (grid) *grid = plan->last_fill.grid;
+    if (block) *block = plan->last_fill.block;
+    return UGS_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2321,6 +2329,7 @@ struct ugs_job {
 
 namespace {
 std::atomic<int64_t> g_spec_kept{0}, g_spec_wrong{0};              // large calls whose early start stood / was thrown away
+std::atomic<int64_t> g_packed_staged{0}, g_packed_refused{0};      // packed steps whose total fitted the staging / that the kernel refused
 void free_job(ugs_job *j) {
     if (!j) return;
     pool_put(j->nodes);
@@ -2374,6 +2383,7 @@ int packed_fill_locked(ugs_job *j, int64_t cap3) {
     }
     plan->last_overflow = 0;
     j->packed_ok = 3 * j->total <= cap3;
+    (j->packed_ok ? g_packed_staged : g_packed_refused).fetch_add(1);
     return UGS_OK;
 }
 
@@ -2741,6 +2751,12 @@ int stream_rows(ugs_plan *plan, StreamCall &c) {
 int ugs_stream_stats(int64_t *early_starts_kept, int64_t *early_starts_discarded) {
     if (early_starts_kept) *early_starts_kept = g_spec_kept.load();
     if (early_starts_discarded) *early_starts_discarded = g_spec_wrong.load();
+    return UGS_OK;
+}
+
+int ugs_step_stats(int64_t *packed_staged, int64_t *packed_refused) {
+    if (packed_staged) *packed_staged = g_packed_staged.load();
+    if (packed_refused) *packed_refused = g_packed_refused.load();
     return UGS_OK;
 }
 

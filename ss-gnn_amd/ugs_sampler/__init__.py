@@ -373,6 +373,14 @@ def set_batch_pass_max_cols(cols):
     return prev.value
 
 
+def step_stats():
+    """{"packed_staged": packed steps of sample_batch / sample_graphs whose outputs fitted their staging, "packed_refused": packed steps
+    the kernel refused (repeated columns pushed the total above the staging; the ordinary fill ran at finish)} since process start."""
+    a, b = C.c_int64(), C.c_int64()
+    check(lib.ugs_step_stats(C.byref(a), C.byref(b)))
+    return {"packed_staged": a.value, "packed_refused": b.value}
+
+
 def cache_stats():
     s, h, m = C.c_int64(), C.c_int64(), C.c_int64()
     check(lib.ugs_cache_stats(C.byref(s), C.byref(h), C.byref(m)))
@@ -449,6 +457,14 @@ class Plan:
         grid, block, lds, ovf = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
         check(lib.ugs_plan_last_launch(self._h, name, 128, C.byref(grid), C.byref(block), C.byref(lds), C.byref(ovf)))
         return {"kernel": name.value.decode(), "grid": grid.value, "block": block.value, "lds_bytes": lds.value, "overflow_rows": ovf.value}
+
+    def last_fill(self):
+        """{"kernel", "grid", "block"} of the kernel that wrote the edge outputs of the last fill() or step() on this plan (testing
+        aid; a staged fill with leftover rows reports the leftover kernel)."""
+        name = C.create_string_buffer(128)
+        grid, block = C.c_int(), C.c_int()
+        check(lib.ugs_plan_last_fill(self._h, name, 128, C.byref(grid), C.byref(block)))
+        return {"kernel": name.value.decode(), "grid": grid.value, "block": block.value}
 
     def set_walk_share(self, percent):
         """Let the walk kernels occupy only `percent` of every CU's resident-block capacity, so that kernels on other streams (the

@@ -38,6 +38,7 @@ def _load():
         "ugs_sample_batch_stream": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                     vp, vp, vp, vp, vp, i64p],
         "ugs_stream_stats": [i64p, i64p],
+        "ugs_step_stats": [i64p, i64p],
         "ugs_sample_stream": [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, vp, vp, vp, vp, i64p],
         "ugs_apx_sample_batch": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_double, vp, i64p],
         "ugs_apx_gpu_sample_batch": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_double, vp, i64p, vp, vp, C.c_int64],
@@ -92,6 +93,7 @@ def _load():
         "ugs_plan_set_timing": [vp, C.c_int],
         "ugs_plan_get_timing": [vp, C.POINTER(C.c_double), i64p],
         "ugs_plan_last_launch": [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), i64p],
+        "ugs_plan_last_fill": [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
         "ugs_wl_hash": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, vp],
         "ugs_wl_hash_labeled": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp],
         "ugs_wl_feature_labels": [vp, C.c_int64, C.c_int64, C.c_int64, vp],

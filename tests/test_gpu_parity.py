@@ -721,10 +721,12 @@ def test_tier_s_with_16_lanes_per_walk_gives_the_oracle_rows(fused, monkeypatch)
 
 @pytest.mark.parametrize("fused", [True, False])
 def test_step_in_one_call_equals_walk_then_fill(fused, monkeypatch):
-    """Plan.step (walk + fill with the scan folded into the fill kernel for batches of small graphs: tiles of 32 rows in ticket
-    order, decoupled look-back) against the oracle and against walk-then-fill: many consecutive steps on one plan (the ticket
-    counter and the launch epoch move on, no memset in between), row ranges that are no multiple of a tile, a single row, more
-    tiles than one look-back window, every mode; a one-walk-per-wave plan takes the three-launch form behind the same call."""
+    """Plan.step (walk + fill with the scan folded into the fill kernel for batches of small graphs: a block takes tiles of 32
+    rows and adds up what lies in front of a tile from the 8-row sums the walk left; no block talks to another) against the
+    oracle and against walk-then-fill: many consecutive steps on one plan (the sum words of earlier, larger calls stay in the
+    scratch, no memset in between), row ranges that are no multiple of a tile, a single row, more tiles than the grid has
+    blocks, every mode; a one-walk-per-wave plan takes the three-launch form behind the same call.  Which fill kernel ran is
+    asserted: the fused form and the three-launch form give the same outputs."""
     import torch
     import oracle
     import ugs_sampler
@@ -747,6 +749,7 @@ def test_step_in_one_call_equals_walk_then_fill(fused, monkeypatch):
             total = int(eptr[-1].item())
             assert total == tot and torch.equal(nodes, n2) and torch.equal(eptr, p2)
             assert torch.equal(eidx[:, :total], e2) and torch.equal(esrc[:total], s2), (k, m, rb, rc, mode)
+            assert plan.last_fill()["kernel"] == ("ugs_fill_scan<8>" if fused else "ugs_fill<8>"), (k, m, rb, rc)
             if it < 2:
                 want = oracle.sample_batch(ei, ptr, m, k, mode, seed)
                 assert np.array_equal(nodes.cpu().numpy(), np.asarray(want[0])[rb:rb + rc])
@@ -775,6 +778,7 @@ def test_step_in_one_call_equals_walk_then_fill(fused, monkeypatch):
     e2, s2 = plan.fill(500, n2, p2, tot, "global")
     nodes, eptr, eidx, esrc = plan.step(500, "global", 9, edge_capacity=tot)
     assert torch.equal(nodes, n2) and torch.equal(eptr, p2) and torch.equal(eidx, e2) and torch.equal(esrc, s2)
+    assert plan.last_fill()["kernel"] == "ugs_fill<64>"
     plan.close()
 
 
