@@ -13,7 +13,8 @@ The law (include/ugs_mi355.h, ugs_uniform_sample_batch_begin, states it in full)
 
 Pure Python + numpy: `mt19937_64`, `lemire`, two enumerations (`connected_subsets_comb`, the literal definition, and
 `connected_subsets_esu` / `sorted_masks`, extension-set search + sort, fast enough for 64-vertex graphs with ~1e5 subsets) and
-`sample_batch`, the output assembly.
+`sample_batch`, the output assembly.  `census` names the kernel paths of ugs_uniform.hip that a call reaches (CLASSES), from these
+quantities alone; tests/uniform_paths.py chooses its inputs by it.
 """
 import itertools
 
@@ -208,3 +209,180 @@ def draws_blocked(outputs, sizes, block=312):
         if pos == block:
             words, pos = [outputs() for _ in range(block)], 0
     return res
+
+
+# ---- which kernel path an input reaches (ugs_uniform.hip), from the law's own quantities -------------------------------------------
+SMALL_SORT, DRAW_BLOCK, MT_BLOCK, SCAN_ONE_BLOCK, ROW_BLOCK, FLUSH = 8192, 320, 312, 16384, 256, 4096
+
+CLASSES = (
+    # columns
+    "stray_cross", "stray_below", "stray_above", "stray_negative", "empty_graph_first", "empty_graph_middle", "empty_graph_last",
+    "ptr0_nonzero", "G_pow2_with_stray", "loop_column", "duplicate_column", "columns_shuffled",
+    # search
+    "k1", "k2", "k3", "k8", "k9", "k_ge_33", "k_eq_n_64", "root_63", "w0_63", "item_ge_4096", "graph_n_lt_k",
+    # scan
+    "items_le_16384", "items_gt_16384",
+    # sort
+    "bucket_0", "bucket_1", "bucket_2", "bucket_np2", "bucket_pow2", "bucket_8192", "bucket_8193", "small_and_large_in_one_call",
+    # draws, one generator
+    "G_le_320", "G_eq_320", "G_eq_321", "G_gt_640", "empties_between", "eq_312", "eq_313", "eq_624", "eq_625", "m0", "size_1",
+    "seed_0", "seed_all_ones",
+    # draws, per-graph seeds
+    "m_eq_312", "m_eq_313", "m_gt_624", "graph_without_sets",
+    # rows and fill
+    "rows_cross_256", "row_without_edges", "edge_at_vertex_63", "loop_in_subset", "sample", "global",
+)
+
+
+def item_counts(adj, k):
+    """{(root v, first extension w): number of connected k-subsets of that item}: the search of esu_masks, counting at the last
+    level (popcount of the extension set) instead of listing, so that K_30 at k = 6 costs C(30, 5) steps and not C(30, 6)."""
+    n = len(adj)
+    out = {}
+    if k <= 0 or k > n:
+        return out
+    for v in range(n):
+        above = ((1 << n) - 1) & ~((2 << v) - 1)
+        if k == 1:
+            out[(v, 0)] = 1
+            continue
+        ext1, nb1 = adj[v] & above, adj[v] | (1 << v)
+        e1 = ext1
+        while e1:
+            w0 = (e1 & -e1).bit_length() - 1
+            e1 &= e1 - 1
+            cnt = 0
+            stack = [(2, e1 | (adj[w0] & ~nb1 & above), nb1 | adj[w0])]
+            while stack:
+                size, ext, nb = stack.pop()
+                if size == k:
+                    cnt += 1
+                elif size == k - 1:
+                    cnt += bin(ext).count("1")
+                else:
+                    while ext:
+                        w = (ext & -ext).bit_length() - 1
+                        ext &= ext - 1
+                        stack.append((size + 1, ext | (adj[w] & ~nb & above), nb | adj[w]))
+            if cnt:
+                out[(v, w0)] = cnt
+    return out
+
+
+def census(ei, ptr, m, k, seeds_or_seed, per_graph, what="sample", mode=None):
+    """The set of path classes (CLASSES) that the call reaches in ugs_uniform.hip, from the input and the law alone: bucket sizes,
+    item counts, draw totals, the drawn rows.  `what`: "sample" (sample_batch, or sample_graphs when per_graph), "enumerate" (a row
+    per set) or "count" (no sort, no draw, no row).  `seeds_or_seed`: the call's seed, or one seed per graph when per_graph."""
+    ei = np.asarray(ei, np.int64).reshape(2, -1)
+    ptr = np.asarray(ptr, np.int64)
+    src, dst = ei[0], ei[1]
+    G, E = len(ptr) - 1, ei.shape[1]
+    out = set()
+    hit = lambda name, cond=True: out.add(name) if cond else None    # noqa: E731
+    # columns
+    first, last = int(ptr[0]), int(ptr[-1])
+    sizes = np.diff(ptr)
+    gof = lambda x: np.where((x >= first) & (x < last), np.searchsorted(ptr, x, "right") - 1, -1)   # noqa: E731
+    # searchsorted over repeated ptr values returns the last graph starting there, i.e. the non-empty one
+    gu, gv = gof(src), gof(dst)
+    key = np.where((gu == gv) & (gu >= 0), gu, G)
+    stray = key == G
+    hit("stray_cross", ((gu >= 0) & (gv >= 0) & (gu != gv)).any())
+    hit("stray_below", (((src < first) & (src >= 0)) | ((dst < first) & (dst >= 0))).any())
+    hit("stray_above", ((src >= last) | (dst >= last)).any())
+    hit("stray_negative", ((src < 0) | (dst < 0)).any())
+    if G > 0:
+        empty = sizes == 0
+        hit("empty_graph_first", empty[0])
+        hit("empty_graph_last", empty[-1])
+        hit("empty_graph_middle", G > 2 and empty[1:-1].any())
+    hit("ptr0_nonzero", first != 0)
+    hit("G_pow2_with_stray", G in (1, 2, 4, 256) and stray.any())
+    hit("loop_column", ((src == dst) & ~stray).any())
+    inside = np.stack([src[~stray], dst[~stray]], axis=1)
+    hit("duplicate_column", len(np.unique(inside, axis=0)) < len(inside))
+    hit("columns_shuffled", (np.diff(key[~stray]) < 0).any())
+    # search: the graphs that are enumerated hold at least k vertices (k >= 1)
+    adjs = [graph_adjacency(src, dst, int(ptr[g]), int(sizes[g])) for g in range(G)]
+    live = [g for g in range(G) if k >= 1 and sizes[g] >= k]
+    for name, cond in (("k1", k == 1), ("k2", k == 2), ("k3", k == 3), ("k8", k == 8), ("k9", k == 9), ("k_ge_33", k >= 33)):
+        hit(name, cond and bool(live))
+    hit("k_eq_n_64", k == 64 and bool(live))
+    hit("graph_n_lt_k", any(sizes[g] < k for g in range(G)))
+    items = {g: item_counts(adjs[g], k) for g in live}
+    for g in live:
+        if k >= 2 and sizes[g] == 64:
+            hit("root_63", adjs[g][63] != 0)
+            hit("w0_63", any(w0 == 63 for _, w0 in items[g]) or any(adjs[g][v] >> 63 & 1 for v in range(63)))
+        hit("item_ge_4096", any(c >= FLUSH for c in items[g].values()))
+    nv = int(sum(sizes[g] for g in live))
+    if live:
+        hit("items_le_16384", nv * 64 <= SCAN_ONE_BLOCK)
+        hit("items_gt_16384", nv * 64 > SCAN_ONE_BLOCK)
+    gsize = {g: sum(items[g].values()) for g in live}
+    if what == "count":
+        return out
+    # sort: one bucket per root
+    buckets = []
+    for g in live:
+        per_root = [0] * int(sizes[g])
+        for (v, _), c in items[g].items():
+            per_root[v] += c
+        buckets += per_root
+    for n in buckets:
+        hit("bucket_0", n == 0)
+        hit("bucket_1", n == 1)
+        hit("bucket_2", n == 2)
+        hit("bucket_np2", n >= 3 and n & (n - 1) != 0)
+        hit("bucket_pow2", n >= 4 and n & (n - 1) == 0)
+        hit("bucket_8192", n == SMALL_SORT)
+        hit("bucket_8193", n == SMALL_SORT + 1)
+    hit("small_and_large_in_one_call", any(n > SMALL_SORT for n in buckets) and any(2 <= n <= SMALL_SORT for n in buckets) and 1 in buckets)
+    # the sets, and the rows the call emits: (graph, mask)
+    sets = {g: sorted_masks(adjs[g], k) for g in live if gsize[g] > 0}
+    nonempty = sorted(sets)
+    rows = []
+    if what == "enumerate":
+        rows = [(g, int(x)) for g in nonempty for x in sets[g]]
+    elif per_graph:
+        seeds = [int(s) & M64 for s in seeds_or_seed]
+        hit("m_eq_312", m == MT_BLOCK and bool(nonempty))
+        hit("m_eq_313", m == MT_BLOCK + 1 and bool(nonempty))
+        hit("m_gt_624", m > 2 * MT_BLOCK and bool(nonempty))
+        hit("graph_without_sets", m > 0 and len(nonempty) < G)
+        for g in nonempty:
+            gen = mt19937_64(seeds[g])
+            rows += [(g, int(sets[g][lemire(gen, len(sets[g]))])) for _ in range(m)]
+    else:
+        seed = int(seeds_or_seed) & M64
+        hit("G_le_320", G <= DRAW_BLOCK)
+        hit("G_eq_320", G == DRAW_BLOCK)
+        hit("G_eq_321", G == DRAW_BLOCK + 1)
+        hit("G_gt_640", G > 2 * DRAW_BLOCK)
+        hit("empties_between", any(i != g for i, g in enumerate(nonempty)))
+        total = len(nonempty) * m
+        for t in (312, 313, 624, 625):
+            hit(f"eq_{t}", total == t)
+        hit("m0", m == 0 and G > 0)
+        hit("size_1", m > 0 and any(len(sets[g]) == 1 for g in nonempty))
+        hit("seed_0", seed == 0 and total > 0)
+        hit("seed_all_ones", seed == M64 and total > 0)
+        gen = mt19937_64(seed)
+        for g in nonempty:
+            rows += [(g, int(sets[g][lemire(gen, len(sets[g]))])) for _ in range(m)]
+    # rows and fill
+    n_rows = len(rows) if what == "enumerate" else G * m
+    hit("rows_cross_256", n_rows > ROW_BLOCK)
+    if rows and mode is not None:
+        hit("sample", mode == "sample")
+        hit("global", mode != "sample")
+    cols = {}
+    for g in {g for g, _ in rows}:
+        sel = key == g
+        cols[g] = list(zip((src[sel] - ptr[g]).tolist(), (dst[sel] - ptr[g]).tolist()))
+    for g, mask in set(rows):
+        inside = [(u, v) for u, v in cols[g] if mask >> u & mask >> v & 1]
+        hit("row_without_edges", not inside)
+        hit("edge_at_vertex_63", any(u == 63 or v == 63 for u, v in inside))
+        hit("loop_in_subset", any(u == v for u, v in inside))
+    return out
