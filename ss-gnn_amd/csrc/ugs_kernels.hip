@@ -42,6 +42,7 @@
 //     of those rows is a plain expand (ugs_fill_staged); rows that do not fit are listed for the row-reading ugs_fill.
 #include "ugs_device.h"
 #include <cstdlib>
+#include <cstddef>
 
 #define UGS_ALIGNED16 __attribute__((aligned(16)))
 
@@ -1162,6 +1163,7 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
             uint64_t fm = insm;
             if (__builtin_expect(dupm != 0ull, 0)) fm = first_of_repeated(g, w, insm, dupm);
             if (__builtin_amdgcn_inverse_ballot_w64(insm)) ws.HK[slot] = w;                      // the chunk is over for this key: drop kFresh
+            // (Parked relies on this: 2 per staged hit, 1 per self hit)
             ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;         // per lane, summed over the wave at the end of the walk
             if constexpr (STG) stage_hits_mask<SON>(sc, g, im, w, p, size);
             const uint32_t nnew = (uint32_t)__popcll(fm);
@@ -1174,6 +1176,7 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
             uint32_t seen = kEmpty;
             probe_find_lds(ws.HK, ws.hmask, slot, step, w, seen, e.y, root_vi);
             const uint64_t im = __ballot((int)seen < -1);             // a found key with kInS; kEmpty (-1: no candidate, or not seen) is not below -1
+            // (Parked relies on this: 2 per staged hit, 1 per self hit)
             ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;
             if constexpr (STG) stage_hits_mask<SON>(sc, g, im, w, p, size);
         }
@@ -1216,6 +1219,7 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
             dupm &= ~grp;
         }
         if (inserted) ws.HK[slot] = w;                            // the chunk is over for this key: drop kFresh
+        // (Parked relies on this: 2 per staged hit, 1 per self hit)
         if constexpr (GS == 64) ecount += in_s ? (w == v ? 1u : 2u) : 0u;       // per lane, summed over the wave at the end of the walk
         else
         {   // entries to earlier members count twice (the mirror entry), entries to the scanned vertex itself once
@@ -1243,6 +1247,7 @@ __device__ __forceinline__ bool scan_chunk(const Work<SP> &ws, const Grp<GS> &g,
             }
         }
         in_s = (seen & (kKeyMask | kInS)) == (w | kInS);                     // kEmpty (no candidate, or not seen) matches no vertex
+        // (Parked relies on this: 2 per staged hit, 1 per self hit)
         if constexpr (GS == 64) ecount += in_s ? (w == v ? 1u : 2u) : 0u;
         else
         {
@@ -1279,6 +1284,7 @@ __device__ __forceinline__ void scan_chunk_last(const Grp<64> &g, uint32_t v, ui
         }
     }
     // exactly what the probing form feeds: a self entry (w == v) counts once, an entry to an earlier member twice, every repeat again
+    // (Parked relies on this: 2 per staged hit, 1 per self hit)
     ecount += __builtin_amdgcn_inverse_ballot_w64(im) ? (w == v ? 1u : 2u) : 0u;
     stage_hits_mask<SON>(sc, g, im, w, p, size);
 }
@@ -1429,7 +1435,8 @@ __device__ __forceinline__ bool flush_has_hit(uint32_t ne, uint32_t lane) {
 }
 
 __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const uint32_t *SV, uint32_t k, uint4 en, uint32_t ecol, uint2 *out) {
-    const uint32_t lane = (uint32_t)g.lane;
+    uint32_t lane = (uint32_t)g.lane;
+    asm volatile("" : "+v"(lane));          // (opaque, as in do_walk: the lane masks of this routine are made where they are used, not carried through the walks)
     uint32_t ei = 0u;
     if (k <= 8u) {
         // straight-line, from the top: words of SV past the sample are stale, but a hit's member is in the sample and the sample's
@@ -1489,6 +1496,82 @@ __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const
     if (mirror) out[rb] = make_uint2(ecol, ei | (es << 8));
 }
 
+// Batched row epilogue (one walk per wave, dynamic work loop, k <= 8).  A wave takes its walks in chunks of up to four rows; the
+// fast branch above ranks a row's items inside DPP row 0 and leaves lanes 16..63 idle, and its rotations act inside every DPP row
+// alike.  So a walk whose row would take the fast branch (1..8 hits, no self hit, complete, staging on) PARKS its results instead
+// of finishing them, and one epilogue per chunk serves every parked row: DPP row j (lanes 16j..16j+15) ranks and stores the items
+// of the row parked in slot j with the instruction stream of one row, one gather fetches all the hits' columns, lanes 0..31 write
+// the nodes rows (lane l: row l >> 3, word l & 7) and lane 16j the counts word.  The slot of a walk is its distance from the end
+// of its chunk, so the chunk's LAST walk has slot 0.  Where the parked state lives:
+//   - the sample: every walk keeps its sample list in words 0..7 of SV, as it always did; a walk parked in slot j > 0 copies them
+//     to words 8j..8j+7 (32-byte aligned slices), and slot 0 IS the live list: the epilogue runs before the next walk starts;
+//   - the hits: lane 16j + t (t < 8) keeps hit t of EL, its CSR position in px and its member in py, and lane 16j + 8 + t the
+//     scanned vertex's local index in px; EL itself is not sliced;
+//   - the row's scalars ride in py of lanes 16j + 8 ..: the row's index (lo, hi), its node offset (lo, hi) and, in one word, its
+//     hit count (bits 0..3; a word of 0 = nothing parked in this DPP row) and edge-entry count (4..).
+// The epilogue spreads them: a rotation by 8 inside the DPP row gives lanes t and 8 + t the same hit, a lane permute the scalars.
+// Every other row (no edges, incomplete, more than 8 hits, a self hit, degenerate graph, handed on) runs its epilogue on the spot
+// and touches none of this.  A self hit needs no look at the member indices: every hit adds 2 to the row's edge-entry count and a
+// self hit 1 (the `ecount +=` of scan_chunk and scan_chunk_last), so a row has none exactly when its count is twice its hits -- a
+// scalar compare.  THE BATCH RELIES ON IT: it has no `ei == es` test of its own.
+struct Parked { uint32_t px, py; };
+__device__ __forceinline__ uint32_t lane_of(uint32_t v, uint32_t byte_addr) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
+__device__ __forceinline__ void park_row(Parked &pk, const Grp<64> &g, uint32_t slot, uint32_t *SV, const uint4 *EL, uint32_t ne, uint32_t nedges, int64_t row_rel, int64_t off) {
+    uint32_t lane = (uint32_t)g.lane;
+    asm volatile("" : "+v"(lane));                     // (opaque, as in do_walk: nothing derived from the lane index is carried through the walks)
+    if ((lane >> 4) == slot) {
+        const uint4 h = EL[lane & 7u];                                           // (lanes past the hits read entries nobody uses)
+        const uint32_t t = lane & 7u;
+        const uint32_t sc = t == 0u ? (uint32_t)row_rel : (t == 1u ? (uint32_t)((uint64_t)row_rel >> 32) : (t == 2u ? (uint32_t)off :
+                            (t == 3u ? (uint32_t)((uint64_t)off >> 32) : (ne | (nedges << 4)))));
+        const bool lo8 = (lane & 8u) == 0u;
+        pk.px = lo8 ? h.x : h.z;
+        pk.py = lo8 ? h.y : sc;
+        if (slot != 0u && lo8) SV[lane - 8u * slot] = SV[t];                     // lanes 16j..16j+7 -> words 8j..8j+7
+    }
+}
+
+// The four pointers the chunk's epilogue needs.  The loop reads them from the kernel's argument block again, through a pointer the
+// compiler cannot see through: as further uses of the walk's own `a.nodes`, `a.counts`, ... they kept those in scalar registers for
+// the whole kernel and pushed lane masks of the order stages into spill slots (C5 instantiation: 94 scalar spills against 62).
+struct FlushOut { int64_t *nodes; uint32_t *counts; uint2 *stage; const int2 *adjf; };
+__device__ __forceinline__ void flush_parked(const Grp<64> &g_, const FlushOut &a, const uint32_t *SV, uint32_t k, Parked &pk) {
+    Grp<64> g = g_;
+    asm volatile("" : "+v"(g.lane));
+    const uint32_t lane = (uint32_t)g.lane;
+    const uint32_t ib = ((lane & 48u) << 2) + 32u, nb = ((lane & 24u) << 3) + 32u;   // byte address of lane 16j + 8: j = lane >> 4 (items), j = lane >> 3 (nodes)
+    const uint32_t meta = lane_of(pk.py, ib + 16u);
+    const bool have = (lane & 7u) < (meta & 15u);
+    if (!g.any(have)) return;
+    const bool lo8 = (lane & 8u) == 0u;
+    const uint32_t rx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pk.px, 0x128, 0xf, 0xf, false);                  // row_ror:8
+    const uint32_t m = (uint32_t)__builtin_amdgcn_update_dpp((int)pk.py, (int)pk.py, 0x128, 0xf, 0xc, false);         // lanes 8.. of each row only
+    const uint32_t es = lo8 ? rx : pk.px;
+    uint32_t ecol = 0u;
+    if (have) ecol = (uint32_t)a.adjf[lo8 ? pk.px : rx].y;
+    const uint32_t rlo = lane_of(pk.py, ib), rhi = lane_of(pk.py, ib + 4u);
+    const uint32_t nrlo = lane_of(pk.py, nb), nrhi = lane_of(pk.py, nb + 4u), nolo = lane_of(pk.py, nb + 8u), nohi = lane_of(pk.py, nb + 12u);
+    const uint32_t nmeta = lane_of(pk.py, nb + 16u);
+    if (lane < 32u && (lane & 7u) < k && nmeta != 0u) {                          // nodes rows (a parked row is complete: no padding)
+        const int64_t r = (int64_t)(((uint64_t)nrhi << 32) | nrlo), off = (int64_t)(((uint64_t)nohi << 32) | nolo);
+        a.nodes[r * (int64_t)k + (int64_t)(lane & 7u)] = (int64_t)SV[lane] + off;
+    }
+    const int64_t row_rel = (int64_t)(((uint64_t)rhi << 32) | rlo);
+    if ((lane & 15u) == 0u && meta != 0u) a.counts[row_rel] = (meta >> 4) | UGS_COUNT_STAGED;
+    const uint4 *S4 = reinterpret_cast<const uint4 *>(SV + ((lane >> 4) << 3));
+    const uint4 s0 = S4[0], s1 = S4[1];
+    uint32_t ei = 0u;                                                            // (as in stage_flush: the hit's own member has the last word)
+    ei = (s1.w == m) ? 7u : ei; ei = (s1.z == m) ? 6u : ei; ei = (s1.y == m) ? 5u : ei; ei = (s1.x == m) ? 4u : ei;
+    ei = (s0.w == m) ? 3u : ei; ei = (s0.z == m) ? 2u : ei; ei = (s0.y == m) ? 1u : ei; ei = (s0.x == m) ? 0u : ei;
+    const uint32_t col = have ? ecol : 0xFFFFFFFFu;
+    const uint32_t cr = ror_count_less<7>(col);
+    const uint32_t src = lo8 ? es : ei, dst = lo8 ? ei : es;
+    const uint32_t key = have ? src * 8u + cr : 0xFFFFFFFFu;
+    const uint32_t rank = ror_count_less<15>(key);
+    if (have) (a.stage + row_rel * UGS_STAGE_ITEMS)[rank] = make_uint2(ecol, src | (dst << 8));
+    pk.py = 0u;
+}
+
 // One walk.  Returns false on workspace overflow (the row is then redone by the next tier).
 // (Round 4 measured a block-wide LDS copy of the walks' graph for the 8-lane tier -- row pointer, adjacency and root records of the
 // graph that owns the block's 32 consecutive rows: PROTEINS-shaped walk 27.8 against 27.0 us, QM9-shaped 59 against 45 us (two blocks
@@ -1498,10 +1581,16 @@ __device__ __forceinline__ void stage_flush(uint32_t ne, const Grp<64> &g, const
 // UNI: facts that hold for a whole launch, fixed at compile time the way SEEDS is (the launcher picks the instantiation): the plan is ONE
 // graph (no row -> graph division), the walk stages its hits (no `onm` mask ANDed into every chunk's hit mask), and the rows are
 // taken by index (no list of handed-on rows).  Only the 448-candidate tier with padded rows has such an instantiation.
-template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false>
+// BATCH (the dynamic work loop of the one-walk-per-wave LDS tiers): with `park` set -- fixed per launch -- a row that would take
+// stage_flush's fast branch is NOT finished (see Parked): the walk hands its hit count and edge-entry count back in `pk` (px, py;
+// 0 = the row was finished here) and its node offset in `poff`, and the loop parks the row (park_row).  The walk itself carries
+// neither the slot nor the parked registers.
+template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false, bool BATCH = false>
 __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, const UgsWalkArgs &a, int64_t row_rel,
                                         uint32_t *SV /* [UGS_KMAX] group-private */, uint4 *EL /* [UGS_STAGE_ENTRIES] or null */,
-                                        uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */) {
+                                        uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */,
+                                        Parked *pk = nullptr, int64_t *poff = nullptr, bool park = false) {
+    static_assert(!BATCH || (GS == 64 && sizeof(typename SP::TW) == 4), "parked rows: one walk per wave, LDS tiers");
 
     static_assert(!PAD || GS == 64, "padded rows are read by a whole wave");
     static_assert(!UNI || (PAD && !SEEDS && sizeof(typename SP::TW) == 4), "UNI: one graph, one seed, padded rows, staging on");
@@ -1651,7 +1740,7 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
         STAMP_END(2);
         if constexpr (STG) {
             if (size + 1u == (uint32_t)k) {                                   // the last pick (wave-uniform; the one test a growth step pays)
-                SV[size] = w;
+                SV[size] = w;                                                 // (size = k - 1: word 7 at most when rows are parked, see Parked)
                 size += 1;
                 v = w;
                 SP::sync();
@@ -1757,6 +1846,7 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
             if (hit) ws.HK[s] = w | kInS;
             }
             if constexpr (GS == 64) SV[size] = w;                     // every lane, same word, same value: no lane-0 mask to set up
+                                                                      // (size < k: at k <= 8 words 8.. of SV are never written here -- they hold parked rows' lists, see Parked)
             else
             if (g.lane == 0) SV[size] = w;
         }
@@ -1778,6 +1868,13 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     bool flush = false;
     uint4 en = make_uint4(0u, 0u, 0u, 0u);
     uint32_t ecol = 0u;
+    if constexpr (BATCH) {
+        if (park && sc.on && nedges != 0u && sc.ne <= kFlushFast && nedges == 2u * sc.ne) {               // wave-uniform: the row's epilogue waits for its chunk's
+            pk->px = sc.ne; pk->py = nedges; *poff = gd.node_lo + a.extra_node_off;
+            STAMP_END(5);
+            return true;
+        }
+    }
     if constexpr (STG) {
         flush = sc.on && nedges != 0u && sc.ne <= UGS_STAGE_ENTRIES;
         // (rows of at most 8 hits: lanes l and 8 + l both take hit l, see stage_flush)
@@ -1862,16 +1959,47 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         auto chunk_for = [&](int64_t left) -> int64_t { return left > 8 * ngroups ? 4 : (left > 2 * ngroups ? 2 : 1); };
         const int64_t first = chunk_for(total);
         int64_t it = ((int64_t)blockIdx.x * GROUPS + gib) * first, end = it + first;
+        // Rows of a chunk park their epilogue (see Parked): one walk per wave, k <= 8, staging on -- the same answer for every wave
+        // of the launch.  Every chunk ends with the epilogue of its parked rows, the drain's chunks of two and one and a chunk cut
+        // short by `total` included: nothing is parked when the next chunk starts or the kernel returns.
+        constexpr bool BT = GS == 64 && Cfg::ELW != 0;
+        bool park = false;
+        Parked pk{0u, 0u};
+        if constexpr (BT) park = a.k <= 8 && (UNI || a.stage != nullptr);
         while (it < total) {
             if (end > total) end = total;
             for (; it < end; ++it) {
                 const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
-                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI>(ws, g, a, row_rel, SV, EL)) {
+                Parked res{0u, 0u};
+                int64_t off = 0;
+                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI, BT>(ws, g, a, row_rel, SV, EL, nullptr, &res, &off, park)) {
                     if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
+                }
+                if constexpr (BT) {
+                    const uint32_t ne = g.uni(res.px);
+                    if (ne) park_row(pk, g, (uint32_t)end - 1u - (uint32_t)it, SV, EL, ne, g.uni(res.py), row_rel, off);
                 }
             }
             const int64_t chunk = chunk_for(total - it);                 // `it` is close to the counter: the estimate only picks the chunk size
             unsigned long long nxt = 0ull;
+            if constexpr (BT) {
+                if (park) {
+                    STAMP_DECL;
+                    STAMP_BEGIN();
+                    typedef const char __attribute__((address_space(4))) *KArgs;
+                    KArgs kp = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+                    asm volatile("" : "+s"(kp));
+                    FlushOut fo;
+                    fo.nodes = *(int64_t *const __attribute__((address_space(4))) *)(kp + offsetof(UgsWalkArgs, nodes));
+                    fo.counts = *(uint32_t *const __attribute__((address_space(4))) *)(kp + offsetof(UgsWalkArgs, counts));
+                    fo.stage = *(uint2 *const __attribute__((address_space(4))) *)(kp + offsetof(UgsWalkArgs, stage));
+                    fo.adjf = *(const int2 *const __attribute__((address_space(4))) *)(kp + offsetof(UgsWalkArgs, plan) + offsetof(UgsPlanDev, adjf));
+                    flush_parked(g, fo, SV, (uint32_t)*(const int __attribute__((address_space(4))) *)(kp + offsetof(UgsWalkArgs, k)), pk);
+                    STAMP_END(5);                                      // row output + edge staging, as the per-walk epilogue
+                }
+            }
+            // (the counter asked for behind the parked hits' gather instead of here, its round trip beside the gather's, measured
+            // 0.3 % SLOWER on C5 -- 227.1..227.6 against 227.8..228.3 M rows/s, five alternations: the epilogue then waits for both)
             if (g.lane == 0) nxt = atomicAdd(a.work_next, (unsigned long long)chunk);
             const uint32_t lo = g.bcast((uint32_t)nxt, 0), hi = g.bcast((uint32_t)(nxt >> 32), 0);
             it = ngroups * first + (int64_t)(((unsigned long long)hi << 32) | lo);

@@ -72,6 +72,20 @@ __global__ __launch_bounds__(64, 5) void probe_flush(uint32_t *out, const uint32
     stage_flush(c, g, pw.SV, rsel, en, ecol, stage);
     out[threadIdx.x] = lds[(threadIdx.x + c) & 63];
 }
+// the batched row epilogue: what a walk pays to park its row, and what a chunk pays once for up to four parked rows
+__global__ __launch_bounds__(64, 5) void probe_park(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel) {
+    PROBE_PRE
+    Parked pk{in[64 + threadIdx.x], in[128 + threadIdx.x]};
+    park_row(pk, g, c & 3u, pw.SV, pw.EL, rsel & 15u, rsel >> 4, (int64_t)c * (int64_t)rsel, (int64_t)rsel << 20);
+    out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + pk.px + pk.py;
+}
+__global__ __launch_bounds__(64, 5) void probe_flush_parked(uint32_t *out, const uint32_t *in, uint32_t c, uint32_t rsel, UgsWalkArgs a) {
+    PROBE_PRE
+    Parked pk{in[64 + threadIdx.x], in[128 + threadIdx.x]};
+    const FlushOut fo{a.nodes, a.counts, a.stage, a.plan.adjf};
+    flush_parked(g, fo, pw.SV, rsel, pk);
+    out[threadIdx.x] = lds[(threadIdx.x + c) & 63] + pk.py;
+}
 template __global__ void probe_mat<0>(uint32_t *, const uint32_t *, uint32_t, uint32_t);
 template __global__ void probe_mat<1>(uint32_t *, const uint32_t *, uint32_t, uint32_t);
 template __global__ void probe_mat<2>(uint32_t *, const uint32_t *, uint32_t, uint32_t);

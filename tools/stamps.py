@@ -1,6 +1,8 @@
 import os, sys, ctypes, time
 """Per-phase wave-cycle totals of the walk kernel from the diagnostic build (tools/mkvar.sh stamps -DUGS_STAMPS -> ab/lib_stamps.so).
-usage: python tools/stamps.py [workload]"""
+usage: python tools/stamps.py [workload]
+Phase 5 (row output + edge staging) counts a walk's own row epilogue or its parking, and, in the dynamic work loop at k <= 8, the
+chunk's batched epilogue of the parked rows as one more execution per chunk: its executions/walk is then about 1.25."""
 os.environ["UGS_MI355_LIB"] = os.path.abspath(os.environ.get("STAMPS_LIB", "ab/lib_stamps.so"))
 sys.path.insert(0, "ss-gnn_amd")
 import torch, numpy as np, ugs_sampler, ugs_workloads as wl
