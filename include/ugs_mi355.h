@@ -483,6 +483,44 @@ int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, i
                                 int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, double p_restart,
                                 int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
 
+/* ---- uniform_sampler.sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode) / PopulationCache.sample_distinct: sampling
+ *      WITHOUT replacement from the finite population S_g -- m distinct connected k-subsets per graph, every ordered selection
+ *      equally likely, and the whole population, in its order, when it has at most m sets (the "full bag": no sampling variance
+ *      left).  The reference has no such mode; this law is the project's own, and it is counter-based.
+ *      The law.  mix(z) is SplitMix64's finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *      z ^= z >> 31.  gamma = 0x9E3779B97F4A7C15.  All arithmetic mod 2^64.  Graph g has N = |S_g| sets in the population order of
+ *      ugs_uniform_enumerate_begin (item 2 of the law of ugs_uniform_sample_batch_begin), the seed s = seeds[g], and m rows:
+ *        - N <= 0 (k = 0, n < k, a graph refused for its size or with more sets than the budget / max_rows: graph_status[g] != 0 for
+ *          the last two): m rows of -1, nothing consumed, as ugs_uniform_sample_graphs_begin does;
+ *        - m >= N: rows 0 ... N-1 are the population indices 0 ... N-1 -- the rows ugs_uniform_enumerate_begin gives for the graph --
+ *          and rows N ... m-1 are rows of -1;
+ *        - m < N: a partial Fisher-Yates shuffle of the virtual identity array a[0 ... N-1].  For j = 0 ... m-1:
+ *          r_j = the high 64 bits of the 128-bit product mix(mix(s) + (j+1) gamma) * (N - j);  t_j = j + r_j;  swap a[j] and a[t_j];
+ *          row j is population index a[j].  There is no rejection step: the multiply-high maps 2^64 values onto N - j, so an outcome's
+ *          probability is off by less than (N - j) / 2^64 < 2^-39 for N <= 2^25, far below what any test of m rows can see.
+ *      The rows of a graph are distinct sets; row j depends only on (s, N) and the steps up to j, so a call with a smaller m gives a
+ *      prefix.  A row with population index d is written exactly as the row a draw d gives in ugs_uniform_sample_graphs_begin
+ *      (items 4 and 5 of that law); a row of -1 has no edges.  sample_ptr = [0, m, 2m, ..., G m].  valid_out[g] = min(m, max(N, 0)):
+ *      the rows of graph g that are real, always its first ones.  valid_out and graph_status are host arrays of num_graphs entries
+ *      written by begin; the population sizes come back with the status words that travel with the edge total (uncached) or are
+ *      known from the slots (cached), so neither call has a read-back of its own for them.
+ *      Limit: m_per_graph <= 4096 (UGS_E_UNSUPPORTED before any device work): one workgroup per graph (uni_draw_distinct) sorts the
+ *      keys (t_j << 32) | j in LDS -- 32 KiB at the limit -- and reads "a[t_j] as the earlier steps left it" off the sorted keys
+ *      (DESIGN.md section 10.3); there is no global-memory fallback.
+ *      ugs_uniform_distinct_begin is ugs_uniform_sample_graphs_begin with these draws: it enumerates on the call, has the same
+ *      argument errors, budget and per-graph failures, and is finished by ugs_uniform_sample_batch_finish.
+ *      ugs_uniform_population_distinct_begin is ugs_uniform_population_sample_begin (seeds != NULL) with these draws: same slot,
+ *      vertex-count and adjacency checks, under the population's shared lock, finished by ugs_uniform_population_sample_finish.
+ *      With equal seeds the two give identical tensors, graph_status and valid_out.  ugs_sample_batch_finish takes either job.
+ *      Own refusals, checked first: m_per_graph < 0, m_per_graph > 4096, and (num_graphs > 0) a NULL seeds, graph_status or valid_out. */
+int ugs_uniform_distinct_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int m_per_graph, int k, int mode, const uint64_t *seeds, int32_t *graph_status, int64_t *valid_out,
+                               ugs_job **job_out, int64_t *total_edges_out);
+int ugs_uniform_population_distinct_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index,
+                                          int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph,
+                                          int mode, const uint64_t *seeds, int check, int32_t *graph_status, int64_t *valid_out,
+                                          ugs_job **job_out, int64_t *total_edges_out);
+
 /* ---- apx_ugs_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, epsilon): replaces the reference's
  *      src/samplers/apx_ugs_sampler/src/apx_ugs_sampler.cpp:461-519.  First graph only;
  *      ptr[0]:ptr[1] is a range of edge COLUMNS (:15-33).  The reference draws everything from ONE sequential

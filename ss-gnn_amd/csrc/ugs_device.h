@@ -219,6 +219,8 @@ int64_t ugs_ord_words(int stages);
 // ---- uniform_sampler (ugs_uniform.hip): exact uniform connected k-subgraph sampling; graphs of at most 64 vertices as 64-bit
 //      masks, graphs of up to UGS_UNI_WIDE_MAX_N vertices (opt-in: ugs_uniform_set_max_vertices) as packed tuples ----
 #define UGS_UNI_BUDGET ((int64_t)1 << 25)    /* connected k-subsets (64-bit masks) one call may hold on the device */
+#define UGS_UNI_DISTINCT_MAX_M 4096          /* rows per graph of a distinct call: uni_draw_distinct sorts that many 8-byte keys in LDS */
+#define UGS_UNI_NO_KEY (~0ull)               /* row key of a wide graph's row of -1 (k ascending fields never pack to all ones) */
 struct UgsUniGraph {
     int64_t lo;           // ptr[g]
     int64_t vbase;        // first entry of this graph in the enumerated vertices (adj, items >> 6)
@@ -230,7 +232,8 @@ struct UgsUniCall {
     int32_t m, k, mode;                      // mode 0: "sample" (row positions), otherwise batch ids
     uint64_t seed;
     const uint64_t *seeds;                   // [G] per-graph generators (ugs_uniform_sample_graphs_begin); nullptr: one for the call, or no draws
-    int32_t per_graph;                       // the budget bounds every graph's own count (sample_graphs, count, enumerate), not the call's
+    int32_t distinct;                        // with seeds: graph g's m draws are distinct (uni_draw_distinct; ugs_uniform_distinct_begin), -1 past |S_g|
+    int32_t per_graph;                      // the budget bounds every graph's own count (sample_graphs, count, enumerate), not the call's
     int64_t *gcount;                         // [G] per-graph subset count of the count pass (per_graph only; > budget: the graph failed)
     const int64_t *sptr;                     // [G + 1] enumerate only: exclusive scan of gsize in batch graph order (= sample_ptr); rows = sptr[G]
     const int64_t *src, *dst, *ptr;          // the batch, on the device: src[E], dst[E], ptr[G + 1]
@@ -249,7 +252,7 @@ struct UgsUniCall {
     const uint64_t *keys_sorted;             // set by ugs_uniform_begin: keys_a or keys_b
     int64_t *gstart, *gsize;                 // [G] first key and |S_g|
     int32_t *nepos, *ne_list;                // [G] position among the graphs with S_g non-empty (-1: empty) / its inverse
-    int32_t *draws;                          // [G * m] index into S_g of each draw (seeds: draw s of graph g at g * m + s)
+    int32_t *draws;                          // [G * m] index into S_g of each draw (seeds: draw s of graph g at g * m + s); < 0: a row of -1
     uint64_t *rowmask;                       // [rows] subset of each row (0: a row of -1)
     uint32_t *ecount;                        // [rows] edge entries per row
     int64_t *status;                         // [4] running subset count, over-budget flag

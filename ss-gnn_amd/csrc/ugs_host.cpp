@@ -3001,15 +3001,18 @@ int ugs_uniform_set_mask_vertices(int n, int *previous) {
 // UNI_ENUMERATE: m_per_graph = 0, one row per set, *rows_out = their number.  UNI_COUNT: no job; counts_out[g] = |S_g|, -1 where refused.
 // UNI_POPULATE (ugs_uniform_population_add): UNI_ENUMERATE up to its first read-back; `populate` then takes the sorted keys, and no job
 // is handed out.
-enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE };
+// UNI_DISTINCT (ugs_uniform_distinct_begin): UNI_SAMPLE with per-graph seeds and uni_draw_distinct for the draws; valid_out[g] =
+// min(m, |S_g|) from the per-graph counts that come back with the status words.
+enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE, UNI_DISTINCT };
 using UniPopulate = std::function<int(const UgsUniCall &c, const UgsUniWide &w, const std::vector<UgsUniGraph> &gd, const std::vector<int64_t> &gsize,
                                       const int32_t *graph_status, const DeviceCtx &dc)>;
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
                          ugs_job **job_out, int64_t *total_edges_out, int what = UNI_SAMPLE, int64_t cap = UGS_UNI_BUDGET,
-                         int64_t *rows_out = nullptr, int64_t *counts_out = nullptr, const UniPopulate *populate = nullptr) {
+                         int64_t *rows_out = nullptr, int64_t *counts_out = nullptr, const UniPopulate *populate = nullptr,
+                         int64_t *valid_out = nullptr) {
     if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
-        return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+        return fail(UGS_E_BAD_ARG, what == UNI_DISTINCT ? "bad arguments to sample_distinct" : "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     const bool per_graph = seeds != nullptr || what != UNI_SAMPLE;
     if (per_graph && num_graphs >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 2^31 - 1");
@@ -3052,7 +3055,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     }
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
-    const bool sampling = what == UNI_SAMPLE, counting = what == UNI_COUNT;
+    const bool sampling = what == UNI_SAMPLE || what == UNI_DISTINCT, counting = what == UNI_COUNT;
     const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? cap : 0;   // (enumerate: m = 0, its rows come later)
     const int64_t keys = counting ? 0 : budget;                         // counting stores no keys and scans nothing
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
@@ -3092,6 +3095,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     c.G = G; c.E = E; c.nv = nv; c.rows = rows; c.budget = budget; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
     c.seeds = seeds ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
     c.per_graph = per_graph ? 1 : 0;
+    c.distinct = what == UNI_DISTINCT ? 1 : 0;
     c.gcount = per_graph ? reinterpret_cast<int64_t *>(b + o_gc) : nullptr;
     c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
     c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + in.desc);
@@ -3166,6 +3170,8 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
                                             " connected k-subsets (the device budget; " + std::to_string(status[0]) + " counted before stopping)"));
     for (int64_t g = 0; per_graph && g < G; ++g)
         graph_status[g] = too_big[(size_t)g] || (!gcount.empty() && gd[(size_t)g].enumerable && gcount[(size_t)g] > budget) ? 1 : 0;
+    for (int64_t g = 0; valid_out && g < G; ++g)                        // a healthy graph's count is its |S_g|
+        valid_out[g] = graph_status[g] || gcount.empty() || !gd[(size_t)g].enumerable ? 0 : std::min<int64_t>(m_per_graph, gcount[(size_t)g]);
     j->fill = [c, w](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_uniform_fill(c, w, edge_index, edge_src, ld, s); };
     return hand_out(j, job_out, total_edges_out);
 }
@@ -3184,6 +3190,28 @@ int ugs_uniform_sample_graphs_begin(const int64_t *edge_index, int64_t row_strid
     int32_t no_status = 0;
     return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds ? seeds : &no_graphs,
                          graph_status ? graph_status : &no_status, job_out, total_edges_out);
+}
+
+// ---- uniform_sampler.sample_distinct: m distinct sets per graph, the whole population when it has at most m (the law is stated in
+//      include/ugs_mi355.h).  The checks that are this call's own, for both begins, before any device work. ----
+static int distinct_checks(int64_t num_graphs, int m_per_graph, const uint64_t *seeds, const int32_t *graph_status, const int64_t *valid_out) {
+    if (m_per_graph < 0) return fail(UGS_E_BAD_ARG, "m_per_graph must be >= 0");
+    if (m_per_graph > UGS_UNI_DISTINCT_MAX_M)
+        return fail(UGS_E_UNSUPPORTED, "uniform_sampler sample_distinct: m_per_graph must be <= " + std::to_string(UGS_UNI_DISTINCT_MAX_M) +
+                                           " (got " + std::to_string(m_per_graph) + "): a graph's draws are resolved in one workgroup's LDS");
+    if (num_graphs > 0 && (!seeds || !graph_status || !valid_out)) return fail(UGS_E_BAD_ARG, "sample_distinct needs seeds, graph_status and valid");
+    return UGS_OK;
+}
+
+int ugs_uniform_distinct_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int m_per_graph, int k, int mode, const uint64_t *seeds, int32_t *graph_status, int64_t *valid_out,
+                               ugs_job **job_out, int64_t *total_edges_out) {
+    if (int rc = distinct_checks(num_graphs, m_per_graph, seeds, graph_status, valid_out)) return rc;
+    static const uint64_t no_graphs = 0;                                // num_graphs <= 0: nothing is read or written through these
+    int32_t no_status = 0;
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds ? seeds : &no_graphs,
+                         graph_status ? graph_status : &no_status, job_out, total_edges_out, UNI_DISTINCT, UGS_UNI_BUDGET, nullptr, nullptr,
+                         nullptr, valid_out);
 }
 
 int ugs_uniform_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
@@ -3350,10 +3378,14 @@ int ugs_uniform_population_info(ugs_uniform_population *pop, int64_t *slots_out,
     return UGS_OK;
 }
 
-int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
-                                        int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, uint64_t seed,
-                                        const uint64_t *seeds, int check, int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out) {
-    if (!pop || !job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
+// valid_out != nullptr: the distinct call (ugs_uniform_population_distinct_begin) -- uni_draw_distinct draws, valid_out[g] = min(m, |S_g|)
+// from the slots
+static int population_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                            int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, uint64_t seed,
+                            const uint64_t *seeds, int check, int32_t *graph_status, int64_t *valid_out, ugs_job **job_out,
+                            int64_t *total_edges_out) {
+    if (!pop || !job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
+        return fail(UGS_E_BAD_ARG, valid_out ? "bad arguments to sample_distinct" : "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     if (num_graphs > 0 && !slots) return fail(UGS_E_BAD_ARG, "population sample needs one slot per graph");
     if (seeds && num_graphs > 0 && !graph_status) return fail(UGS_E_BAD_ARG, "sample_graphs needs seeds and graph_status");
@@ -3389,6 +3421,7 @@ int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64
             UgsPopGraph &d = pg[(size_t)g];
             d.keys = s.keys; d.lo = ptr[g]; d.fp = s.fp; d.n = s.n; d.form = s.size < 0 ? 0 : s.form; d.b = s.b;
             gsize[(size_t)g] = s.size > 0 ? s.size : 0;
+            if (valid_out) valid_out[g] = std::min<int64_t>(m_per_graph, gsize[(size_t)g]);
             any_wide = any_wide || (d.form == 2 && s.size > 0);
             UgsUniGraph &u = gd[(size_t)g];
             u.lo = ptr[g]; u.n = s.n; u.vbase = 0; u.enumerable = d.form;
@@ -3433,6 +3466,7 @@ int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64
     UgsUniCall &c = p.c;
     c.G = G; c.E = E; c.nv = check ? nv : 0; c.rows = rows; c.m = m_per_graph; c.k = k; c.mode = mode; c.seed = seed;
     c.seeds = seeds ? reinterpret_cast<const uint64_t *>(b + in.seeds) : nullptr;
+    c.distinct = valid_out ? 1 : 0;
     c.src = reinterpret_cast<const int64_t *>(b + in.src); c.dst = reinterpret_cast<const int64_t *>(b + in.dst);
     c.ptr = reinterpret_cast<const int64_t *>(b + in.ptr); c.graphs = reinterpret_cast<const UgsUniGraph *>(b + in.desc);
     c.cub_tmp = b + o_cub; c.cub_bytes = cub_bytes;
@@ -3467,6 +3501,24 @@ int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64
     }
     j->fill = [p, stp](int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) { return ugs_uniform_pop_fill(p, edge_index, edge_src, ld, s); };
     return hand_out(j, job_out, total_edges_out);
+}
+
+int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                                        int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, uint64_t seed,
+                                        const uint64_t *seeds, int check, int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out) {
+    return population_begin(pop, slots, edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, mode, seed, seeds, check, graph_status,
+                            nullptr, job_out, total_edges_out);
+}
+
+int ugs_uniform_population_distinct_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                                          int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode,
+                                          const uint64_t *seeds, int check, int32_t *graph_status, int64_t *valid_out, ugs_job **job_out,
+                                          int64_t *total_edges_out) {
+    if (int rc = distinct_checks(num_graphs, m_per_graph, seeds, graph_status, valid_out)) return rc;
+    static const uint64_t no_graphs = 0;
+    int64_t no_valid = 0;
+    return population_begin(pop, slots, edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, mode, 0, seeds ? seeds : &no_graphs,
+                            check, graph_status, valid_out ? valid_out : &no_valid, job_out, total_edges_out);
 }
 
 int ugs_uniform_population_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,

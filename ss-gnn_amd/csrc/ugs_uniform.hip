@@ -20,6 +20,8 @@
 //   uni_sort_small / segmented  per-root buckets sorted ascending by key (bitonic in LDS; large buckets: rocPRIM)
 //   uni_draw                    one workgroup: mt19937_64 + libstdc++'s Lemire step, draws in blocks of 312
 //   uni_draw_graphs             (per-graph seeds) the same, one workgroup and one generator per graph
+//   uni_draw_distinct           (ugs_uniform_distinct_begin) m distinct draws per graph, or all of S_g and -1 behind it: a
+//                               counter-based partial Fisher-Yates shuffle resolved through a key sort in LDS
 //   uni_rows + scan             rows (node ids) and per-row edge counts -> edge_ptr
 //   uni_fill (finish)           edge_index / edge_src
 //
@@ -351,6 +353,79 @@ __global__ __launch_bounds__(DRAW_BLOCK) void uni_draw_graphs(UgsUniCall c) {
     mt_draws(mt, (int64_t)c.m, [&](int64_t) { return N; }, c.draws + g * (int64_t)c.m, s_wave, &s_first);
 }
 
+// ---- distinct draws (ugs_uniform_distinct_begin; the law stands in include/ugs_mi355.h): graph g's rows are the first m places of
+//      a Fisher-Yates shuffle of 0 ... N - 1, step j swapping a[j] with a[t_j], t_j = j + hi64(mix(mix(seed) + (j + 1) gamma) (N - j)).
+//      The targets are counter-based, so every lane computes its own; what is serial in the law is only "a[t_j] as earlier steps left
+//      it", and that is read off the sorted keys (t_j << 32) | j:
+//        pred(t, j) = the greatest step i < j with t_i == t: the entry just below (t << 32) | j, if its t matches;
+//        place t >= j is touched before step j only by such steps, and step i leaves there what stood at place i before it:
+//        w(i) = pred(i, i) exists ? w(pred(i, i)) : i  (a strictly decreasing chain, nearly always empty);
+//        row j = pred(t_j, j) exists ? w(pred(t_j, j)) : t_j.
+//      The entry below a key is found by binary search over the m sorted keys (log2 m LDS reads), so the keys are the only array:
+//      8 P bytes of LDS, P = m rounded up to a power of two, 32 KiB at the limit of 4096 rows. ----
+__device__ __forceinline__ uint64_t sm_mix(uint64_t z) {                           // SplitMix64's finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint32_t distinct_target(uint64_t s0, uint64_t N, uint32_t j) {   // t_j, s0 = mix(seed); j < N < 2^32
+    return j + (uint32_t)__umul64hi(sm_mix(s0 + (uint64_t)(j + 1) * 0x9E3779B97F4A7C15ull), N - j);
+}
+// pred(t, j) over the ascending keys[0 ... m), or -1
+__device__ __forceinline__ int distinct_pred(const uint64_t *keys, int m, uint32_t t, uint32_t j) {
+    const uint64_t key = ((uint64_t)t << 32) | j;
+    int lo = 0, hi = m;                                             // first position whose key is >= key
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
+    if (lo == 0) return -1;
+    const uint64_t below = keys[lo - 1];
+    return (uint32_t)(below >> 32) == t ? (int)(uint32_t)below : -1;
+}
+
+// One workgroup per graph writes draws[g * m + j], j < m: q = min(m, N) distinct indices into S_g, then -1.  m >= N (N <= 0
+// included) is the whole population in its order and needs no key; otherwise P = m rounded up to a power of two keys are sorted
+// (bitonic, pair form: lane q of a stage with stride s holds places i = 2 q - (q & (s - 1)) and i + s; the padding sorts last).
+// Dynamic LDS: 8 P bytes (the host passes it), m <= UGS_UNI_DISTINCT_MAX_M.
+__global__ __launch_bounds__(UNI_BLOCK) void uni_draw_distinct(UgsUniCall c) {
+    extern __shared__ uint64_t s_keys[];
+    const int64_t g = blockIdx.x;
+    const int m = c.m, tid = threadIdx.x;
+    if (m == 0) return;
+    int32_t *out = c.draws + g * (int64_t)m;
+    const int64_t N = c.status[1] ? 0 : c.gsize[g];
+    if (N <= m) {
+        for (int j = tid; j < m; j += UNI_BLOCK) out[j] = j < N ? j : -1;
+        return;
+    }
+    int P = 1;
+    while (P < m) P <<= 1;
+    const uint64_t s0 = sm_mix(c.seeds[g]);
+    for (int j = tid; j < P; j += UNI_BLOCK) s_keys[j] = j < m ? ((uint64_t)distinct_target(s0, (uint64_t)N, (uint32_t)j) << 32) | (uint32_t)j : ~0ull;
+    __syncthreads();
+    for (int width = 2; width <= P; width <<= 1)
+        for (int stride = width >> 1; stride > 0; stride >>= 1) {
+            for (int q = tid; q < (P >> 1); q += UNI_BLOCK) {
+                const int i = 2 * q - (q & (stride - 1)), l = i + stride;
+                const uint64_t a = s_keys[i], b = s_keys[l];
+                if ((a > b) == ((i & width) == 0)) { s_keys[i] = b; s_keys[l] = a; }
+            }
+            __syncthreads();
+        }
+    for (int j = tid; j < m; j += UNI_BLOCK) {
+        const uint32_t t = distinct_target(s0, (uint64_t)N, (uint32_t)j);
+        int x = distinct_pred(s_keys, m, t, (uint32_t)j);
+        uint32_t r = t;
+        if (x >= 0) {                                               // w(x): what stood at place x before step x
+            for (;;) {
+                const int y = distinct_pred(s_keys, m, (uint32_t)x, (uint32_t)x);
+                if (y < 0) break;
+                x = y;
+            }
+            r = (uint32_t)x;
+        }
+        out[j] = (int32_t)r;
+    }
+}
+
 // row b = g * m + s: the drawn subset's vertices ascending (or -1) and its edge count over the graph's column bucket
 __global__ void uni_rows(UgsUniCall c) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -360,7 +435,8 @@ __global__ void uni_rows(UgsUniCall c) {
     uint64_t mask = 0;
     if (!c.status[1] && c.gsize[g] > 0) {
         const int64_t d = c.seeds ? row : (int64_t)c.nepos[g] * c.m + s;   // per-graph seeds: graph g's draws at g * m
-        mask = mask_of(c.keys_sorted[c.gstart[g] + c.draws[d]]);
+        const int32_t draw = c.draws[d];                            // negative (a distinct call past |S_g|): a row of -1
+        if (draw >= 0) mask = mask_of(c.keys_sorted[c.gstart[g] + draw]);
     }
     c.rowmask[row] = mask;
     uint32_t cnt = 0;
@@ -593,7 +669,9 @@ __global__ void uni_wrows(UgsUniCall c, UgsUniWide wd) {
     const UgsUniGraph gd = c.graphs[g];
     const int k = c.k, b = field_bits(gd.n);
     const int64_t d = c.seeds ? row : (int64_t)c.nepos[g] * c.m + s;
-    const uint64_t key = c.keys_sorted[c.gstart[g] + c.draws[d]];
+    const int32_t draw = c.draws[d];
+    if (draw < 0) { wd.rowkey[row] = UGS_UNI_NO_KEY; return; }      // (a distinct call past |S_g|) uni_rows has written the row of -1
+    const uint64_t key = c.keys_sorted[c.gstart[g] + draw];
     wd.rowkey[row] = key;
     int64_t *out = c.nodes + row * k;
     for (int j = 0; j < k; ++j) out[j] = gd.lo + (int64_t)((key >> (b * (k - 1 - j))) & ((1ull << b) - 1));
@@ -613,6 +691,7 @@ __global__ void uni_wfill(UgsUniCall c, UgsUniWide wd, int64_t *edge_index, int6
     const UgsUniGraph gd = c.graphs[g];
     const int k = c.k, b = field_bits(gd.n);
     const uint64_t key = wd.rowkey[row];
+    if (key == UGS_UNI_NO_KEY) return;                              // a row of -1 inside a live graph
     int64_t w = c.edge_ptr[row];
     for (int64_t p = c.cstart[g]; p < c.cstart[g + 1]; ++p) {
         const uint32_t uv = wd.wpair[p];
@@ -783,11 +862,13 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_pop_check(UgsPopCall p) {
         atomicMax((unsigned long long *)&p.c.status[2], (unsigned long long)(p.c.G - g));
 }
 
-// the drawn key of a row, or false: the graph has nothing to draw from (a row of -1)
+// the drawn key of a row, or false: the graph has nothing to draw from, or the draw is negative (a distinct call past |S_g|) -- a row of -1
 __device__ __forceinline__ bool pop_key(const UgsPopCall &p, const UgsPopGraph &pg, int64_t row, int64_t g, uint64_t &key) {
     if (p.c.gsize[g] <= 0) return false;
     const int64_t d = p.c.seeds ? row : (int64_t)p.c.nepos[g] * p.c.m + (row - g * p.c.m);
-    key = pg.keys[p.c.draws[d]];
+    const int32_t draw = p.c.draws[d];
+    if (draw < 0) return false;
+    key = pg.keys[draw];
     return true;
 }
 
@@ -803,7 +884,8 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_pop_rows(UgsPopCall p) {
     const bool live = pop_key(p, pg, row, g, key);
     if (live && pg.form == 2) return;                               // uni_wpop_rows
     const uint64_t mask = live ? mask_of(key) : 0ull;
-    if (l == 0) p.rowkey[row] = mask;
+    // (a wide graph with keys hands its rows' keys to uni_wpop_fill: its row of -1 is marked, 0 being a key)
+    if (l == 0) p.rowkey[row] = !live && pg.form == 2 && c.gsize[g] > 0 ? UGS_UNI_NO_KEY : mask;
     int64_t *out = c.nodes + row * c.k;
     uint32_t cnt = 0;
     if (mask) {
@@ -889,6 +971,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wpop_fill(UgsPopCall p, int64_t
     if (pg.form != 2 || c.gsize[g] <= 0) return;
     const int k = c.k, b = pg.b;
     const uint64_t key = p.rowkey[row];
+    if (key == UGS_UNI_NO_KEY) return;                              // a row of -1 inside a live graph (the whole group leaves)
     int64_t w = c.edge_ptr[row];
     const int64_t end = c.cstart[g + 1];
     for (int64_t base = c.cstart[g]; base < end; base += POP_LANES) {
@@ -912,6 +995,14 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wpop_fill(UgsPopCall p, int64_t
 }
 
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+// uni_draw_distinct over every graph of the call; the sort's width, and with it the LDS, follows m, not the limit
+inline void launch_draw_distinct(const UgsUniCall &c, hipStream_t s) {
+    if (c.m <= 0 || c.m > UGS_UNI_DISTINCT_MAX_M) return;          // (the begins refuse a larger m before any device work)
+    size_t P = 1;
+    while (P < (size_t)c.m) P <<= 1;
+    hipLaunchKernelGGL(uni_draw_distinct, dim3((unsigned)c.G), dim3(UNI_BLOCK), P * sizeof(uint64_t), s, c);
+}
 
 }  // namespace
 
@@ -990,7 +1081,8 @@ hipError_t ugs_uniform_begin(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) 
     if (nv_wide > 0) cm.gsize = w.gsize_mask;
     if (c.G > 0) {
         if (nv_wide > 0) hipLaunchKernelGGL(uni_wsizes, dim3(blocks(c.G, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, w);
-        if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
+        if (c.seeds && c.distinct) launch_draw_distinct(c, s);
+        else if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
         else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
     }
     if (c.rows > 0) hipLaunchKernelGGL(uni_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
@@ -1057,7 +1149,8 @@ hipError_t ugs_uniform_pop_begin(UgsPopCall &p, hipStream_t s) {
         hipLaunchKernelGGL(uni_pop_check, dim3((unsigned)c.G), dim3(UNI_BLOCK), 0, s, p);
     }
     if (c.G > 0) {
-        if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
+        if (c.seeds && c.distinct) launch_draw_distinct(c, s);
+        else if (c.seeds) hipLaunchKernelGGL(uni_draw_graphs, dim3((unsigned)c.G), dim3(DRAW_BLOCK), 0, s, c);
         else hipLaunchKernelGGL(uni_draw, dim3(1), dim3(DRAW_BLOCK), 0, s, c);
     }
     if (c.rows > 0) hipLaunchKernelGGL(uni_pop_rows, dim3(blocks(c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p);

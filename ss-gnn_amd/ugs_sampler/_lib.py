@@ -67,6 +67,10 @@ def _load():
         "ugs_uniform_population_sample_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp,
                                                 C.POINTER(vp), i64p],
         "ugs_uniform_population_sample_finish": [vp, vp, vp, vp, vp, vp, C.c_int],
+        "ugs_uniform_distinct_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                       C.POINTER(vp), i64p],
+        "ugs_uniform_population_distinct_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, vp,
+                                                  C.POINTER(vp), i64p],
         "ugs_rwr_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
                                         C.POINTER(vp), i64p],
         "ugs_cache_clear": [],

@@ -25,6 +25,12 @@ ugs_uniform_enumerate_begin.
 PopulationCache(k, device) keeps those populations on the device: every dataset graph is enumerated once (add / add_many), and
 pop.sample_batch / pop.sample_graphs over any batch of added graphs equal the module's sample_batch / sample_graphs bit for bit
 while running only column buckets, draws, rows and fill.  Law at ugs_uniform_population_create.
+
+sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode="sample") -> the 5-tuple + failed[G] + valid[G], and
+pop.sample_distinct: sampling WITHOUT replacement -- m distinct sets per graph (m <= 4096), uniform over all such selections, and the
+whole population in enumerate_graphs' order when it has at most m sets; the rows past valid[g] = min(m, |S_g|) are rows of -1.  The
+law (a counter-based partial Fisher-Yates shuffle, the project's own: the reference only draws with replacement) stands at
+ugs_uniform_distinct_begin.
 """
 import ctypes as C
 
@@ -34,7 +40,7 @@ import torch
 from ugs_sampler import _graphs
 from ugs_sampler._lib import check, lib
 
-__all__ = ["sample_batch", "sample_graphs", "enumerate_graphs", "count_graphs", "set_max_vertices", "max_vertices", "PopulationCache"]
+__all__ = ["sample_batch", "sample_graphs", "sample_distinct", "enumerate_graphs", "count_graphs", "set_max_vertices", "max_vertices", "PopulationCache"]
 
 
 def set_max_vertices(n):
@@ -79,6 +85,41 @@ def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", device
     """sample_graphs with `failed` left on the host and the outputs on `device` (PresampleCache.add_many)"""
     return _graphs.sample_graphs(lambda batch, md, sd, st, out: lib.ugs_uniform_sample_graphs_begin(*batch, md, sd, st, *out),
                                  lib.ugs_uniform_sample_batch_finish, edge_index, ptr, m_per_graph, k, seeds, mode, device)
+
+
+DISTINCT_MAX_M = 4096                 # rows per graph of a distinct call (UGS_UNI_DISTINCT_MAX_M)
+
+
+def _distinct_seeds(seeds, offsets):
+    """The seeds of a distinct call: one per graph (as _graphs.seed_array takes them), or one integer s, graph g then getting
+    s + offsets[g] mod 2^64."""
+    if isinstance(seeds, (int, np.integer)) and not isinstance(seeds, bool):
+        return np.array([(int(seeds) + int(o)) & _graphs.M64 for o in offsets], dtype=np.uint64)
+    return _graphs.seed_array(seeds, len(offsets))
+
+
+def sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode="sample"):
+    """m distinct connected k-subsets per graph, uniform over all ordered selections (sampling without replacement); a graph with at
+    most m sets gives all of them, in enumerate_graphs' order, and rows of -1 behind them.  Row j of graph g is row
+    sample_ptr_e[g] + d of enumerate_graphs, d the j-th place of the shuffle the law at ugs_uniform_distinct_begin defines from
+    (seeds[g], |S_g|); a smaller m gives a prefix.  m_per_graph <= 4096 (RuntimeError otherwise, before any device work).
+    seeds: G integers (sequence or tensor, mod 2^64), or one integer s, which stands for s + g for graph g.
+    Failures, devices, streams and pinned host outputs are those of sample_graphs.
+    Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src, failed, valid): valid[g] = min(m, |S_g|) (0 for a failed graph), int64,
+    the number of graph g's rows that are real -- always its first ones."""
+    status, valid = [], []
+
+    def begin(batch, out):
+        G = max(batch[4], 0)
+        sd = _distinct_seeds(seeds, range(G))
+        status.append(np.zeros(max(G, 1), dtype=np.int32))
+        valid.append(np.zeros(max(G, 1), dtype=np.int64))
+        return lib.ugs_uniform_distinct_begin(*batch, 0 if mode == "sample" else 1, sd.ctypes.data, status[0].ctypes.data,
+                                              valid[0].ctypes.data, *out)
+
+    five = _graphs.run_job(begin, lib.ugs_uniform_sample_batch_finish, edge_index, ptr, m_per_graph, k)
+    G, dev = ptr.numel() - 1, five[0].device
+    return five + (torch.from_numpy(status[0][:G] != 0).to(dev), torch.from_numpy(valid[0][:G].copy()).to(dev))
 
 
 def enumerate_graphs(edge_index, ptr, k, mode="sample", *, max_rows=1 << 22, device=None):
@@ -254,21 +295,30 @@ class PopulationCache:
                                        f"the graph added in its place has {self._slot[i][1]}")
         return gi, out
 
-    def _job(self, graph_idx, ptr, edge_index, m_per_graph, mode, seed, seeds, check_graphs, device):
+    def _job(self, graph_idx, ptr, edge_index, m_per_graph, mode, seed, seeds, check_graphs, device, distinct=False):
         _graphs.check_int64(edge_index, ptr)
         _graphs._edge_index_view(edge_index)
         gi, slots = self._slots(graph_idx, ptr)
         pop = self._handle()
         md = 0 if mode == "sample" else 1
         status = np.zeros(max(len(gi), 1), np.int32)
-        sd = _graphs.seed_array(seeds, len(gi)) if seeds is not None else None
+        if distinct:
+            sd = _distinct_seeds(seeds, gi)
+            valid = np.zeros(max(len(gi), 1), np.int64)
+        else:
+            sd = _graphs.seed_array(seeds, len(gi)) if seeds is not None else None
 
         def begin(batch, out):
+            if distinct:
+                return lib.ugs_uniform_population_distinct_begin(pop, slots.ctypes.data, *batch[:6], md, sd.ctypes.data, 1 if check_graphs else 0,
+                                                                 status.ctypes.data, valid.ctypes.data, *out)
             return lib.ugs_uniform_population_sample_begin(pop, slots.ctypes.data, *batch[:6], md, C.c_uint64(int(seed) & _graphs.M64),
                                                            sd.ctypes.data if sd is not None else None, 1 if check_graphs else 0,
                                                            status.ctypes.data if sd is not None else None, *out)
 
         five = _graphs.run_job(begin, lib.ugs_uniform_population_sample_finish, edge_index, ptr, m_per_graph, self.k, device)
+        if distinct:
+            return five, status[:len(gi)], valid[:len(gi)]
         return five, status[:len(gi)]
 
     def sample_batch(self, graph_idx, ptr, batch_edge_index, m_per_graph, mode="sample", seed=42, *, check=True, device=None):
@@ -284,6 +334,17 @@ class PopulationCache:
         it was added gives m rows of -1 and failed[g] = True."""
         five, status = self._job(graph_idx, ptr, batch_edge_index, m_per_graph, mode, 0, seeds, check, device)
         return five + (torch.from_numpy(status != 0).to(five[0].device),)
+
+    def sample_distinct(self, graph_idx, ptr, batch_edge_index, m_per_graph, seeds, mode="sample", *, check=True, device=None):
+        """uniform_sampler.sample_distinct for such a batch, all seven tensors: m distinct sets per graph, or the graph's whole
+        population (the full bag, served from the cache on every step) and rows of -1 behind it where it has at most m sets.
+        seeds: one per graph of the batch, or one integer s, which here stands for s + graph_idx[g] -- a graph's seed follows its
+        dataset index, not its place, so its bag does not depend on which batch it lands in (the uncached call, which knows no
+        dataset index, takes s + g; it equals this call when given seeds = [s + i for i in graph_idx]).
+        Errors, check, device and stream as sample_graphs; m_per_graph <= 4096."""
+        five, status, valid = self._job(graph_idx, ptr, batch_edge_index, m_per_graph, mode, 0, seeds, check, device, distinct=True)
+        dev = five[0].device
+        return five + (torch.from_numpy(status != 0).to(dev), torch.from_numpy(valid.copy()).to(dev))
 
     def sizes(self, graph_idx):
         """|S_g| of the graphs added under graph_idx (host int64 [G]); -1 for a failed graph"""
