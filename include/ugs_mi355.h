@@ -190,6 +190,13 @@ int ugs_plan_release(ugs_plan *plan);
  * (src/sampler.cpp:121-150).  Arrays hold `capacity` entries; any pointer may be NULL.  Synchronises with the device. */
 int ugs_plan_graph_roots(ugs_plan *plan, int64_t graph, int64_t capacity, int32_t *level, int32_t *num_nodes, int32_t *num_viable,
                          double *prob, int32_t *alias, int32_t *v_self, int32_t *v_alias, int32_t *viable_vi, int32_t *viable_v);
+/* The CSR rows the kernels read for graph `graph` of a plan, copied back from HBM (read-only, diagnostic: parity tests of the device
+ * batch pass, whose build kernel writes these arrays itself).  rowptr: num_nodes + 1 values relative to the graph's first entry;
+ * per entry the neighbour w and rank(w) (adj) and w and the batch column (adjf).  rowptr holds node_capacity + 1 values, the
+ * entry arrays entry_capacity; any pointer may be NULL.  A degenerate graph (n <= 0 or n < k) reports num_nodes = 0.
+ * Synchronises with the device. */
+int ugs_plan_graph_csr(ugs_plan *plan, int64_t graph, int64_t node_capacity, int64_t entry_capacity, int32_t *num_nodes,
+                       int64_t *num_entries, int64_t *rowptr, int32_t *nbr, int32_t *nbr_rank, int32_t *nbr_f, int32_t *nbr_col);
 /* A second plan over the same device arrays with private scratch (a plan's scratch serves one stream at a time): two steps in
  * flight on two streams go through a plan and its twin alternately.  Release both; the arrays live until the last one goes. */
 int ugs_plan_twin(ugs_plan *plan, int k, ugs_plan **twin_out);

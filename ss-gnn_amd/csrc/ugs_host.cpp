@@ -1808,6 +1808,41 @@ int ugs_plan_graph_roots(ugs_plan *plan, int64_t graph, int64_t capacity, int32_
     return UGS_OK;
 }
 
+int ugs_plan_graph_csr(ugs_plan *plan, int64_t graph, int64_t node_capacity, int64_t entry_capacity, int32_t *num_nodes, int64_t *num_entries,
+                       int64_t *rowptr, int32_t *nbr, int32_t *nbr_rank, int32_t *nbr_f, int32_t *nbr_col) {
+    if (!plan || graph < 0 || graph >= plan->G) return fail(UGS_E_BAD_ARG, "graph index outside the plan");
+    HIP_TRY(hipSetDevice(plan->device));
+    UgsGraphDesc d{};
+    {
+        std::lock_guard<std::mutex> lk(plan->mu);
+        if (plan->last_valid) HIP_TRY(hipEventSynchronize(plan->last_ev));
+        HIP_TRY(hipMemcpy(&d, plan->dev.graphs + graph, sizeof(d), hipMemcpyDeviceToHost));
+    }
+    if (d.level < 0 || d.n <= 0) { if (num_nodes) *num_nodes = 0; if (num_entries) *num_entries = 0; return UGS_OK; }
+    std::vector<int64_t> rp((size_t)d.n + 1);
+    HIP_TRY(hipMemcpy(rp.data(), plan->dev.rowptr + d.rbase, rp.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t nnz = rp[(size_t)d.n] - rp[0];
+    if (num_nodes) *num_nodes = d.n;
+    if (num_entries) *num_entries = nnz;
+    if (rowptr) {
+        if (node_capacity < d.n) return fail(UGS_E_BAD_ARG, "capacity below the graph's vertex count");
+        for (int32_t x = 0; x <= d.n; ++x) rowptr[x] = rp[(size_t)x] - rp[0];
+    }
+    if (nnz > 0 && (nbr || nbr_rank || nbr_f || nbr_col)) {
+        if (entry_capacity < nnz) return fail(UGS_E_BAD_ARG, "capacity below the graph's entry count");
+        std::vector<int2> a((size_t)nnz), f((size_t)nnz);
+        HIP_TRY(hipMemcpy(a.data(), plan->dev.adj + rp[0], a.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(f.data(), plan->dev.adjf + rp[0], f.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        for (int64_t e = 0; e < nnz; ++e) {
+            if (nbr) nbr[e] = a[(size_t)e].x;
+            if (nbr_rank) nbr_rank[e] = a[(size_t)e].y;
+            if (nbr_f) nbr_f[e] = f[(size_t)e].x;
+            if (nbr_col) nbr_col[e] = f[(size_t)e].y;
+        }
+    }
+    return UGS_OK;
+}
+
 int ugs_plan_info(const ugs_plan *plan, int k, int64_t *num_graphs, int64_t *num_vertices, int64_t *nnz, int64_t *device_bytes, int *tier) {
     if (!plan) return fail(UGS_E_BAD_ARG, "plan is null");
     if (num_graphs) *num_graphs = plan->G;

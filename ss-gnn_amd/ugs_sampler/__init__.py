@@ -447,6 +447,19 @@ class Plan:
         d.update(level=lvl.value, num_nodes=n.value, num_viable=nvia.value)
         return d
 
+    def graph_csr(self, graph):
+        """The CSR rows the kernels read for one graph of the plan, copied back from HBM (testing aid): rowptr relative to the
+        graph's first entry, and per entry nbr / nbr_rank (adj) and nbr_f / nbr_col (adjf).  A degenerate graph has num_nodes 0."""
+        import numpy as np
+        n, nnz = C.c_int32(), C.c_int64()
+        check(lib.ugs_plan_graph_csr(self._h, int(graph), 0, 0, C.byref(n), C.byref(nnz), None, None, None, None, None))
+        d = {"rowptr": np.zeros(n.value + 1, np.int64), "nbr": np.zeros(nnz.value, np.int32), "nbr_rank": np.zeros(nnz.value, np.int32),
+             "nbr_f": np.zeros(nnz.value, np.int32), "nbr_col": np.zeros(nnz.value, np.int32)}
+        if n.value > 0:
+            check(lib.ugs_plan_graph_csr(self._h, int(graph), n.value, nnz.value, C.byref(n), C.byref(nnz), *[v.ctypes.data for v in d.values()]))
+        d.update(num_nodes=n.value, num_entries=nnz.value)
+        return d
+
     def info(self):
         g, nv, nnz, nb, tier = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
         check(lib.ugs_plan_info(self._h, self.k, C.byref(g), C.byref(nv), C.byref(nnz), C.byref(nb), C.byref(tier)))
