@@ -186,6 +186,61 @@ struct Rng {
     }
 };
 
+// A work chunk's random numbers, drawn across the lanes (launch-uniform walk, dynamic work loop; see do_walk's DRAWS).  Everything
+// a walk draws depends on (seed, row) alone, and every lane of the wave used to compute the same nine numbers per walk.  A chunk is
+// up to four consecutive rows and a DPP row has 16 lanes: lane 16 r + j computes output j + 1 of the generator of the chunk's row r,
+// once per chunk.  The chain s1 -> s2 -> ... runs along the DPP row: in every iteration a lane applies the xorshift step to its left
+// neighbour's value (row_shr:1), and the lane without one (j = 0) to the row's seed, which the shift leaves in place as `old`.
+// After t iterations lanes j < t hold s(j+1) and keep it -- their inputs no longer change -- so no lane is masked; k + 1 numbers
+// take k + 1 iterations (nine unrolled at k <= 8), and one multiply at the end turns every state into its output.  Rows of a
+// chunk cut short by the row count compute numbers nobody reads.  The pass also finishes the root's numbers while it has
+// the lanes (the graph is a launch constant): lane (r, 0) reduces its number to the root index (`lo`), and at level 0 lane (r, 1)
+// turns its number into the alias draw's double; at relaxed levels lane (r, 1) stays raw, the first pick reads it.
+// Sixteen lanes per row: k + 1 <= 16, decided per launch by the launcher (launch_lds: an instantiation of its own, DRAWS); above
+// that it launches the walk as it was, every walk running the generator itself.
+struct ChunkDraws { uint32_t lo, hi; };
+// what lane t holds, in scalar registers (t is wave-uniform)
+__device__ __forceinline__ uint32_t draw_lo(const ChunkDraws *cd, uint32_t t) { return (uint32_t)__builtin_amdgcn_readlane((int)cd->lo, (int)t); }
+__device__ __forceinline__ uint64_t draw64(const ChunkDraws *cd, uint32_t t) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cd->hi, (int)t) << 32) | draw_lo(cd, t);
+}
+constexpr int kDrawLanes = 16;
+__device__ __forceinline__ void chunk_draws(ChunkDraws &cd, uint64_t seed_base, int64_t row0, int numbers, const UgsGraphDesc *gdp) {
+    uint32_t lane = threadIdx.x & 63u;
+    asm volatile("" : "+v"(lane));                     // (opaque, as in do_walk: nothing derived from the lane index is carried through the walks)
+    uint64_t s0 = seed_base + (uint64_t)(row0 + (int64_t)(lane >> 4)) * 0x9e3779b97f4a7c15ull;
+    s0 = s0 ? s0 : 1ull;                               // Rng::init, per row
+    const uint32_t s0lo = (uint32_t)s0, s0hi = (uint32_t)(s0 >> 32);
+    uint32_t xlo = s0lo, xhi = s0hi;                   // (what a lane holds before its turn is never used)
+    auto step = [&]() {
+        const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp((int)s0lo, (int)xlo, 0x111, 0xf, 0xf, false);   // row_shr:1
+        const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp((int)s0hi, (int)xhi, 0x111, 0xf, 0xf, false);
+        uint64_t x = ((uint64_t)phi << 32) | plo;
+        x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+        xlo = (uint32_t)x; xhi = (uint32_t)(x >> 32);
+    };
+    if (numbers <= 9) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) step();
+    } else {
+        for (int t = 0; t < numbers; ++t) step();
+    }
+    const uint64_t x = (((uint64_t)xhi << 32) | xlo) * 2685821657736338717ull;
+    cd.lo = (uint32_t)x; cd.hi = (uint32_t)(x >> 32);
+    const UgsGraphDesc gd = *gdp;
+    const uint32_t jl = lane & 15u;
+    if (gd.level == 0) {
+        const uint32_t j = mod64_root(x, (uint32_t)gd.n);
+        const double u = (double)x * 0x1p-64;
+        const uint64_t ub = (uint64_t)__double_as_longlong(u);
+        cd.lo = jl == 0u ? j : (jl == 1u ? (uint32_t)ub : cd.lo);
+        cd.hi = jl == 1u ? (uint32_t)(ub >> 32) : cd.hi;
+    } else if (gd.level > 0) {
+        const uint32_t idx = mod64_root(x, (uint32_t)gd.n_viable);
+        cd.lo = jl == 0u ? idx : cd.lo;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // sub-wave group of GS lanes
 // ------------------------------------------------------------------------------------------------------------------
@@ -1585,12 +1640,17 @@ __device__ __forceinline__ void flush_parked(const Grp<64> &g_, const FlushOut &
 // stage_flush's fast branch is NOT finished (see Parked): the walk hands its hit count and edge-entry count back in `pk` (px, py;
 // 0 = the row was finished here) and its node offset in `poff`, and the loop parks the row (park_row).  The walk itself carries
 // neither the slot nor the parked registers.
-template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false, bool BATCH = false>
+// DRAWS (the launch-uniform walk in the dynamic work loop, k + 1 <= 16: the launcher picks the instantiation): the walk's random
+// numbers were drawn for its whole chunk (chunk_draws); number t of this row is read from lane dcur + t into scalar registers and
+// the generator is not run.
+template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false, bool BATCH = false, bool DRAWS = false>
 __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, const UgsWalkArgs &a, int64_t row_rel,
                                         uint32_t *SV /* [UGS_KMAX] group-private */, uint4 *EL /* [UGS_STAGE_ENTRIES] or null */,
                                         uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */,
-                                        Parked *pk = nullptr, int64_t *poff = nullptr, bool park = false) {
+                                        Parked *pk = nullptr, int64_t *poff = nullptr, bool park = false,
+                                        const ChunkDraws *cd = nullptr, uint32_t dcur = 0u /* lane of this row's first number */) {
     static_assert(!BATCH || (GS == 64 && sizeof(typename SP::TW) == 4), "parked rows: one walk per wave, LDS tiers");
+    static_assert(!DRAWS || (UNI && BATCH), "lane-parallel draws: the launch-uniform walk in the dynamic work loop");
 
     static_assert(!PAD || GS == 64, "padded rows are read by a whole wave");
     static_assert(!UNI || (PAD && !SEEDS && sizeof(typename SP::TW) == 4), "UNI: one graph, one seed, padded rows, staging on");
@@ -1620,11 +1680,13 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     }
     STAMP_DECL;
     STAMP_BEGIN();
-    Rng rng;
-    uint64_t seed_base;
-    if constexpr (SEEDS) seed_base = a.seeds[gi];          // one generator base per graph (UgsWalkArgs::seeds)
-    else seed_base = a.seed_ptr ? *a.seed_ptr : a.seed64;
-    rng.init(seed_base + (uint64_t)i * 0x9e3779b97f4a7c15ull);
+    [[maybe_unused]] Rng rng;                              // (DRAWS: no generator, the numbers wait in the lanes)
+    if constexpr (!DRAWS) {
+        uint64_t seed_base;
+        if constexpr (SEEDS) seed_base = a.seeds[gi];      // one generator base per graph (UgsWalkArgs::seeds)
+        else seed_base = a.seed_ptr ? *a.seed_ptr : a.seed64;
+        rng.init(seed_base + (uint64_t)i * 0x9e3779b97f4a7c15ull);
+    }
     // Root draw.  The root record is fetched first and the membership hash is reset while it is in flight; the root's row is
     // requested as soon as the root is known, before the root is entered into the hash and the sample list.
     uint32_t root_vi, root_v;
@@ -1633,11 +1695,19 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     UgsRootRec rr{};
     int2 vr = make_int2(0, 0);
     if (gd.level == 0) {      // alias draw: two numbers (reference include/sampler.hpp:72-77)
+        if constexpr (DRAWS) {     // both finished by the chunk's pass: the index, and the double in the next lane
+            j = draw_lo(cd, dcur);
+            u = __longlong_as_double((long long)draw64(cd, dcur + 1u));
+            dcur += 2u;
+        } else {
         j = mod64_root(rng.next(), (uint32_t)gd.n);
         u = (double)rng.next() * 0x1p-64;           // == / (double)UINT64_MAX (which is 2^64): exact scaling
+        }
         rr = P.roots[gd.vbase + j];
     } else {                  // relaxed: uniform over the viable list, one number (reference src/sampler.cpp:169-172)
-        const uint32_t idx = mod64_root(rng.next(), (uint32_t)gd.n_viable);
+        uint32_t idx;
+        if constexpr (DRAWS) idx = draw_lo(cd, dcur++);
+        else idx = mod64_root(rng.next(), (uint32_t)gd.n_viable);
         vr = P.viable[gd.viable_base + idx];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1726,7 +1796,9 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
             if (!ok) return false;
             if (step >= k - 1 || c == 0) break;                               // complete, or growth failed: partial row
         }
-        const uint32_t rsel = g.uni(mod64_by<sizeof(typename SP::TW) == 4, sizeof(typename SP::TW) == 4 && GS == 64>(rng.next(), c));
+        uint64_t xsel;
+        if constexpr (DRAWS) xsel = draw64(cd, dcur++); else xsel = rng.next();
+        const uint32_t rsel = g.uni(mod64_by<sizeof(typename SP::TW) == 4, sizeof(typename SP::TW) == 4 && GS == 64>(xsel, c));
         STAMP_END(4);
         const Pick pick = select_any<GS, MAXPER>(ws, g, c, rsel, nvalid);
         const uint32_t w = pick.w;
@@ -1915,7 +1987,10 @@ template <int CAP> struct TierCfg {
 // admits 18 one-wave blocks per CU (5,5,4,4 per SIMD).  With a STATIC split of the rows 18 blocks/CU was slower than 16
 // (10.63 vs 10.43 ms: a launch ended with the waves of the fuller SIMDs); with the shared work counter the extra waves are
 // pure throughput: 8.81 -> 8.51 ms.  Spilling further to reach more waves costs more than it brings (30 % in an early build).
-template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false, bool UNI = false>
+// DRAWS: the launch-uniform walk with its chunks' random numbers drawn across the lanes (chunk_draws; launch_lds picks it).  A
+// parameter of the one kernel template, so that every instantiation keeps the code it had: a body shared by two kernels through
+// an inlined function compiled the other tiers to different register allocations (the 32-candidate tier 95 -> 97 VGPRs).
+template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false, bool UNI = false, bool DRAWS = false>
 __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 5 : (CAP == 704 ? 3 : (CAP <= 64 || CAP == 1024 || CAP == 1408 ? 2 : 1)))) void ugs_walk_lds(UgsWalkArgs a) {
     using Cfg = TierCfg<CAP>;
     constexpr int GROUPS = BLOCK / GS;
@@ -1966,13 +2041,20 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         bool park = false;
         Parked pk{0u, 0u};
         if constexpr (BT) park = a.k <= 8 && (UNI || a.stage != nullptr);
+        // DRAWS: the launch-uniform walk draws a chunk's random numbers across the lanes (chunk_draws); a DPP row holds a walk's k + 1.
+        static_assert(!DRAWS || (BT && UNI), "lane-parallel draws: the launch-uniform walk");
+        ChunkDraws cd{0u, 0u};
         while (it < total) {
             if (end > total) end = total;
+            uint32_t dcur = 0u;
+            if constexpr (DRAWS) chunk_draws(cd, a.seed_ptr ? *a.seed_ptr : a.seed64, a.row_begin + it, a.k + 1, a.plan.graphs);
             for (; it < end; ++it) {
                 const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
                 Parked res{0u, 0u};
                 int64_t off = 0;
-                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI, BT>(ws, g, a, row_rel, SV, EL, nullptr, &res, &off, park)) {
+                const uint32_t dlane = dcur;
+                dcur += (uint32_t)kDrawLanes;
+                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI, BT, DRAWS>(ws, g, a, row_rel, SV, EL, nullptr, &res, &off, park, &cd, dlane)) {
                     if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
                 }
                 if constexpr (BT) {
@@ -2514,8 +2596,13 @@ static hipError_t launch_lds(const UgsWalkArgs &a, int cus, int blocks_per_cu, h
     constexpr bool kCanUni = GS == 64 && CAP == 448;
     if constexpr (kCanUni) {
         if (pad && !a.seeds && a.stage && a.plan.num_graphs == 1 && !a.in_list) {
+            // (with the dynamic work loop and k + 1 <= 16 numbers per walk: the chunk's numbers drawn across the lanes, see chunk_draws)
+            // (the launch record names that instantiation "...,draws>": nothing else tells the two apart from outside)
+            const bool draws = a.work_next && a.k + 1 <= kDrawLanes;
+            if (draws) hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanUni, false, kCanUni, kCanUni>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
+            else
             hipLaunchKernelGGL((ugs_walk_lds<GS, CAP, BLOCK, kCanUni, false, kCanUni>), dim3((unsigned)grid), dim3(BLOCK), 0, s, a);
-            if (info) { info->name = name; info->grid = (int)grid; info->block = BLOCK; info->lds_bytes = GROUPS * TierCfg<CAP>::WORDS * 4; }
+            if (info) { info->name = draws ? "ugs_walk_lds<64,448,draws>" : name; info->grid = (int)grid; info->block = BLOCK; info->lds_bytes = GROUPS * TierCfg<CAP>::WORDS * 4; }
             return hipGetLastError();
         }
     }

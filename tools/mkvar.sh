@@ -11,6 +11,6 @@ FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -x hip"
 /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-sched-strategy=${SCHED:-max-ilp} "$@" -I$HERE -c ${KSRC:-$HERE/ugs_kernels.hip} -o $W/ugs_kernels.o &
 /opt/rocm/bin/hipcc $FL "$@" -c $HERE/ugs_host.cpp -o $W/ugs_host.o &
 wait
-for f in ugs_eps ugs_uniform ugs_rwr ugs_preproc ugs_apx ugs_apx_gpu ugs_collate ugs_batch; do [ -f $HERE/$f.o ] || { echo "missing $HERE/$f.o (run build.py)"; exit 1; }; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/ab/lib_$NAME.so $W/ugs_kernels.o $W/ugs_host.o $HERE/ugs_eps.o $HERE/ugs_uniform.o $HERE/ugs_rwr.o $HERE/ugs_preproc.o $HERE/ugs_apx.o $HERE/ugs_apx_gpu.o $HERE/ugs_collate.o $HERE/ugs_batch.o
+for f in ugs_eps ugs_uniform ugs_rwr ugs_preproc ugs_apx ugs_apx_gpu ugs_collate ugs_batch ugs_wl; do [ -f $HERE/$f.o ] || { echo "missing $HERE/$f.o (run build.py)"; exit 1; }; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/ab/lib_$NAME.so $W/ugs_kernels.o $W/ugs_host.o $HERE/ugs_eps.o $HERE/ugs_uniform.o $HERE/ugs_rwr.o $HERE/ugs_preproc.o $HERE/ugs_apx.o $HERE/ugs_apx_gpu.o $HERE/ugs_collate.o $HERE/ugs_batch.o $HERE/ugs_wl.o
 echo built ab/lib_$NAME.so
