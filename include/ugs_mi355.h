@@ -490,6 +490,37 @@ int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, i
                                 int64_t num_graphs, int m_per_graph, int k, int mode, const uint64_t *seeds, double p_restart,
                                 int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
 
+/* ---- rwr_sampler.sample_batch / sample_graphs(..., streams="row"): random walk with restart with one generator per ROW, so that
+ *      every walk is independent of every other.  The reference has no such mode; with more than one OpenMP thread it has no
+ *      reproducible law at all (above).  This law is the project's own: same output distribution, reproducible, parallel by
+ *      construction, and pinned to the reference row by row (below).
+ *      The law is the one at ugs_rwr_sample_batch_begin with its points 1, 3, 4 and 5 unchanged (adjacency; n < k; the walk; rows,
+ *      edges and sample_ptr) and this point 2.  Let sg be the graph's seed: seed + g (seeds == NULL), or seeds[g].  Row s of graph g
+ *      (0 <= s < m) owns a SplitMix64 seeded with
+ *          row_seed(sg, s) = mix((sg + (s + 1) * 0x9e3779b97f4a7c15) mod 2^64)
+ *      which is output s of the graph's own generator in its counter form, 0-based: SplitMix's usual way of seeding children from
+ *      a parent.  Output 0 is the one output the per-graph law never uses (its draws are 1-based).  The row's walk is the walk of
+ *      point 4 on that stream from its first draw.  (sg + s * gamma itself would not do as a row seed: row s + 1 would then be
+ *      the walk that starts one draw into row s's stream.)
+ *      Consequences:
+ *        - row (g, s) is bit for bit row 0 of ugs_rwr_sample_batch_begin for the same edge_index with the one-graph ptr
+ *          {ptr[g], ptr[g+1]}, m = 1 and seed = row_seed(sg, s), node ids left as batch ids -- one call of the reference with one
+ *          thread;
+ *        - a row depends on (sg, s) and its graph only: not on m, not on other rows, and on other graphs only through the position
+ *          g in seed + g.  The first m rows of a call with m' > m are the rows of the call with m;
+ *        - a row whose result the law fixes without walking is written without walking, since no later row depends on its length:
+ *          a seed vertex in a component of fewer than k vertices (a row of -1), and p_restart == 1.0 with k > 1 (every step
+ *          restarts: every row of a graph with n >= k is -1);
+ *        - edge_src is -1 and sample_ptr = [0, m, ..., G m].
+ *      seeds == NULL: sg = seed + g; arguments, errors and limits of ugs_rwr_sample_batch_begin (k > 64 and a graph with n >= k
+ *      and 10 n k > INT_MAX are refused); graph_status must be NULL.  seeds != NULL: sg = seeds[g] and the semantics of
+ *      ugs_rwr_sample_graphs_begin: such a graph fails alone (m rows of -1, graph_status[g] != 0), graph_status is required.
+ *      On the device (ugs_rwr.hip) the CSR is built as before; one kernel then walks every row, one row per lane, a workgroup
+ *      serving rows of one graph from LDS.  Finish with ugs_rwr_sample_batch_finish. */
+int ugs_rwr_sample_rows_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                              int64_t num_graphs, int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds,
+                              double p_restart, int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
+
 /* ---- uniform_sampler.sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode) / PopulationCache.sample_distinct: sampling
  *      WITHOUT replacement from the finite population S_g -- m distinct connected k-subsets per graph, every ordered selection
  *      equally likely, and the whole population, in its order, when it has at most m sets (the "full bag": no sampling variance

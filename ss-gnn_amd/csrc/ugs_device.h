@@ -323,6 +323,9 @@ struct UgsRwrGraph {
 struct UgsRwrCall {
     int64_t G, E, NV, rows;                  // graphs, columns, batch vertices ptr[G] - ptr[0], G * m rows
     int32_t m, k, mode, spec;                // mode 0: "sample" (row positions), otherwise batch ids; window = spec * block offsets
+    int32_t row_streams;                     // != 0: one generator per row (ugs_rwr_sample_rows_begin), set by ugs_rwr_row_streams with:
+    int32_t row_wgs;                         //   workgroups of rwr_row_walks per graph
+    int32_t row_lds_ints;                    //   CSR words of the largest graph that walks from LDS: the launch's dynamic LDS
     uint64_t seed;
     const uint64_t *seeds;                   // [G] generator of each graph (ugs_rwr_sample_graphs_begin); nullptr: seed + g
     double p;                                // p_restart
@@ -334,12 +337,14 @@ struct UgsRwrCall {
     int32_t *rs;                             // [NV + 1] CSR row starts (rows in (column, side) order of their half-edges)
     int32_t *parent, *csize;                 // [NV] union-find over the columns, component sizes at the roots
     uint8_t *doomed;                         // [NV] the vertex's component has fewer than k vertices: every walk seeded there fails
-    int64_t *rstart;                         // [rows] draws of the graph's stream consumed before the row's walk; -1: a row of -1
+    int64_t *rstart;                         // [rows] draws of the graph's stream consumed before the row's walk (row streams: 0); -1: a row of -1
     uint32_t *ecount;                        // [rows] edge entries per row
     int64_t *scan_tmp;                       // ugs_scan_tmp_words(rows)
     int64_t *nodes, *edge_ptr;               // outputs: [rows, k], [rows + 1]
 };
 size_t ugs_rwr_cub_bytes(int64_t E);
+// makes c a row-streams call; graphs[G] and half_edges[G] (twice the columns inside each graph) are host arrays
+void ugs_rwr_row_streams(UgsRwrCall &c, const UgsRwrGraph *graphs, const int64_t *half_edges);
 hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s);
 hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 

@@ -3565,9 +3565,10 @@ int ugs_uniform_population_sample_finish(ugs_job *job, int64_t *nodes, int64_t *
 // ---- rwr_sampler.sample_batch (reference src/samplers/rwr_sampler/src/rwr_sampler.cpp, one OpenMP thread) ----
 // seeds == nullptr: sample_batch, graph g seeded with seed + g; otherwise sample_graphs: graph g seeded with seeds[g], and a graph
 // whose one-graph call would be refused (n >= k and 10 n k > INT_MAX) fails alone, graph_status[g] = 1.
+// row_streams: one generator per row (ugs_rwr_sample_rows_begin) in place of one per graph.
 static int rwr_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                      int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status, double p_restart,
-                     ugs_job **job_out, int64_t *total_edges_out) {
+                     ugs_job **job_out, int64_t *total_edges_out, bool row_streams = false) {
     const bool per_graph = seeds != nullptr;
     if (!job_out || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index)) return fail(UGS_E_BAD_ARG, "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
@@ -3623,6 +3624,17 @@ static int rwr_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_
     c.rstart = reinterpret_cast<int64_t *>(b + o_rst); c.ecount = reinterpret_cast<uint32_t *>(b + o_ec);
     c.scan_tmp = reinterpret_cast<int64_t *>(b + o_st);
     c.nodes = static_cast<int64_t *>(j->nodes.p); c.edge_ptr = j->d_eptr;
+    if (row_streams) {
+        // half-edges inside each graph, as rwr_halfedges keeps them: they size the walk kernel's LDS.  Columns mostly follow their graphs.
+        std::vector<int64_t> half((size_t)G, 0);
+        int64_t g = 0;
+        for (int64_t x = 0; x < E && G > 0; ++x) {
+            const int64_t u = edge_index[x], v = edge_index[row_stride + x];
+            if (!(ptr[g] <= u && u < ptr[g + 1])) g = std::min<int64_t>(std::upper_bound(ptr + 1, ptr + G + 1, u) - (ptr + 1), G - 1);
+            if (ptr[g] <= u && u < ptr[g + 1] && ptr[g] <= v && v < ptr[g + 1]) half[(size_t)g] += 2;
+        }
+        ugs_rwr_row_streams(c, gd.data(), half.data());
+    }
     hipError_t e = hipMemcpyAsync(b, host.data(), L.in_bytes, hipMemcpyHostToDevice, dc.stream);
     if (e == hipSuccess) e = ugs_rwr_begin(c, dc.stream);
     if (int rc = side_job_total(j, e, "rwr_sampler pipeline")) return rc;
@@ -3646,6 +3658,21 @@ int ugs_rwr_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, i
     int32_t no_status = 0;
     return rwr_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds ? seeds : &no_graphs,
                      graph_status ? graph_status : &no_status, p_restart, job_out, total_edges_out);
+}
+
+int ugs_rwr_sample_rows_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                              int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, double p_restart,
+                              int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out) {
+    static const uint64_t no_graphs = 0;                                // no graphs, no seeds: graph_status alone asks for the per-graph form
+    if (!seeds && num_graphs == 0 && graph_status) seeds = &no_graphs;
+    if (!seeds) {
+        if (graph_status) return fail(UGS_E_BAD_ARG, "sample_rows without seeds takes no graph_status");
+        return rwr_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, seed, nullptr, nullptr, p_restart, job_out,
+                         total_edges_out, true);
+    }
+    if (!graph_status) return fail(UGS_E_BAD_ARG, "sample_rows with seeds needs graph_status");
+    return rwr_begin(edge_index, row_stride, num_cols, ptr, num_graphs, m_per_graph, k, mode, 0, seeds, graph_status, p_restart, job_out,
+                     total_edges_out, true);
 }
 
 int ugs_rwr_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,

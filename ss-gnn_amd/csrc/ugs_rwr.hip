@@ -18,6 +18,9 @@
 //   rwr_resolve                 one workgroup per graph: speculate / resolve windows -> rstart[row] (-1: a row of -1)
 //   rwr_rows + scan             the chosen walks again: rows (node ids) and per-row edge counts -> edge_ptr
 //   rwr_fill (finish)           edge_index / edge_src
+// streams = "row" (ugs_rwr_sample_rows_begin: one generator per row, seeded with output s of the graph's) runs rwr_init ...
+// rwr_rowstart as above, then rwr_row_walks in place of rwr_resolve + rwr_rows -- every walk is independent, there is no chain
+// to follow and no doomed walk to measure -- then the same scan and rwr_fill.
 //
 // Doomed walks (seed in a component smaller than k) always run all 10 n k iterations.  Speculation stops them after the seed
 // draw; when the chain reaches one, its length comes from the RNG alone (rwr_doomed_len): without edges every iteration takes one
@@ -33,6 +36,10 @@ constexpr int RWR_WMAX = 4 * RWR_BLOCK;         // largest speculation window (s
 constexpr int RWR_LDS_INTS = 8192;              // graphs whose CSR (+ doomed bytes) fits in 32 KiB walk from LDS
 constexpr uint64_t SPEC_CAP = 64;              // speculation gives up on a walk at this many draws (lane 0 redoes it if needed)
 constexpr uint64_t GAMMA = 0x9e3779b97f4a7c15ull;
+constexpr int RWR_ROW_LANES = 64;               // rwr_row_walks: a workgroup is one wave, one row of its graph per lane
+
+// LDS words of a graph of n vertices and D half-edges: row starts, targets, doomed bytes
+__host__ __device__ __forceinline__ int64_t rwr_csr_words(int32_t n, int64_t D) { return (int64_t)n + 1 + D + (n + 3) / 4; }
 
 __device__ __forceinline__ uint64_t mix(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -81,30 +88,50 @@ __device__ __forceinline__ RwrView global_view(const UgsRwrCall &c, int64_t g, c
     return w;
 }
 
+// One row's generator in a streams = "row" call (law at ugs_rwr_sample_rows_begin): output s (0-based) of the graph's own
+// generator, the one output -- draw 0 -- that the per-graph law never uses.  The row's walk is the walk after c = 0 draws of it.
+__device__ __forceinline__ RwrView row_view(RwrView w, int32_t s) { w.sg = mix(w.sg + ((uint64_t)s + 1) * GAMMA); return w; }
+
+// The seed draw of the walk that starts after c draws: chosen = {seed}; z is left at the state of that draw.
+template <int KM>
+__device__ __forceinline__ int32_t rwr_walk_seed(const RwrView &w, uint64_t c, Chosen<KM> &ch, uint64_t &z) {
+    z = w.sg + (c + 2) * GAMMA;                                     // state of draw c + 1
+    const int32_t seed = (int32_t)(mix(z) % (uint64_t)w.n);
+    ch.cnt = 0;
+    ch.add(seed);
+    return seed;
+}
+
+// One iteration of the walk's loop (reference :166-189); returns the draws it took, 1 or 2.
+template <int KM>
+__device__ __forceinline__ uint32_t rwr_walk_step(const RwrView &w, int32_t seed, int32_t &cur, Chosen<KM> &ch, uint64_t &z) {
+    uint32_t L = 1;
+    z += GAMMA;
+    const double r = to_double(mix(z));
+    const int32_t b = w.rs[cur], e = w.rs[cur + 1];
+    if (r < w.p || b == e) {
+        cur = seed;
+    } else {
+        z += GAMMA; ++L;
+        cur = w.tg[b + (int32_t)(mix(z) % (uint64_t)(uint32_t)(e - b))];
+    }
+    if (!ch.has(cur)) ch.add(cur);
+    return L;
+}
+
 // The walk that starts after c draws (reference :162-190).  Returns the draws it consumed, or 0 when its seed is doomed (the
 // caller knows it fails and takes its length from rwr_doomed_len), or ~0 once it has taken `cap` draws without ending.
 // ch holds the chosen vertices; ch.cnt == k: success.
 template <int KM>
 __device__ uint64_t rwr_walk(const RwrView &w, uint64_t c, Chosen<KM> &ch, uint64_t cap = ~0ull) {
-    uint64_t z = w.sg + (c + 2) * GAMMA;                            // state of draw c + 1
-    const int32_t seed = (int32_t)(mix(z) % (uint64_t)w.n);
-    ch.cnt = 0;
-    ch.add(seed);
+    uint64_t z;
+    const int32_t seed = rwr_walk_seed<KM>(w, c, ch, z);
     if (w.doomed[seed]) return 0;
     uint64_t L = 1;
     int32_t cur = seed;
     for (int32_t it = 0; ch.cnt < w.k && it < w.T; ++it) {
         if (L >= cap) return ~0ull;
-        z += GAMMA; ++L;
-        const double r = to_double(mix(z));
-        const int32_t b = w.rs[cur], e = w.rs[cur + 1];
-        if (r < w.p || b == e) {
-            cur = seed;
-        } else {
-            z += GAMMA; ++L;
-            cur = w.tg[b + (int32_t)(mix(z) % (uint64_t)(uint32_t)(e - b))];
-        }
-        if (!ch.has(cur)) ch.add(cur);
+        L += rwr_walk_step<KM>(w, seed, cur, ch, z);
     }
     return L;
 }
@@ -300,23 +327,17 @@ __global__ __launch_bounds__(RWR_BLOCK) void rwr_resolve(UgsRwrCall c) {
     }
 }
 
-// row = g * m + s: the walk at rstart[row] again, its vertices and its edge count (:204-245)
-template <int KM>
-__global__ __launch_bounds__(RWR_BLOCK) void rwr_rows(UgsRwrCall c) {
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= c.rows) return;
+// a row of -1 without edges
+__device__ __forceinline__ void rwr_row_failed(const UgsRwrCall &c, int64_t row) {
     int64_t *out = c.nodes + row * c.k;
-    const int64_t st = c.rstart[row];
-    if (st < 0) {
-        for (int j = 0; j < c.k; ++j) out[j] = -1;
-        c.ecount[row] = 0;
-        return;
-    }
-    const int64_t g = row / c.m;
-    const UgsRwrGraph gd = c.graphs[g];
-    const RwrView w = global_view(c, g, gd);
-    Chosen<KM> ch;
-    (void)rwr_walk<KM>(w, (uint64_t)st, ch);
+    for (int j = 0; j < c.k; ++j) out[j] = -1;
+    c.ecount[row] = 0;
+}
+
+// the row of a walk that found its k vertices: their ids and the row's edge count (:204-245)
+template <int KM>
+__device__ __forceinline__ void rwr_row_found(const UgsRwrCall &c, const RwrView &w, const UgsRwrGraph &gd, int64_t row, const Chosen<KM> &ch) {
+    int64_t *out = c.nodes + row * c.k;
     uint32_t cnt = 0;
 #pragma unroll
     for (int j = 0; j < KM; ++j) {
@@ -327,6 +348,69 @@ __global__ __launch_bounds__(RWR_BLOCK) void rwr_rows(UgsRwrCall c) {
         }
     }
     c.ecount[row] = cnt;
+}
+
+// row = g * m + s: the walk at rstart[row] again, its vertices and its edge count
+template <int KM>
+__global__ __launch_bounds__(RWR_BLOCK) void rwr_rows(UgsRwrCall c) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= c.rows) return;
+    const int64_t st = c.rstart[row];
+    if (st < 0) { rwr_row_failed(c, row); return; }
+    const int64_t g = row / c.m;
+    const UgsRwrGraph gd = c.graphs[g];
+    const RwrView w = global_view(c, g, gd);
+    Chosen<KM> ch;
+    (void)rwr_walk<KM>(w, (uint64_t)st, ch);
+    rwr_row_found<KM>(c, w, gd, row, ch);
+}
+
+// streams = "row" (law at ugs_rwr_sample_rows_begin): every row owns a generator, so every walk is independent and this kernel
+// stands in for rwr_resolve + rwr_rows.  A workgroup is one wave and serves RWR_ROW_LANES rows of ONE graph, one row per lane;
+// it stages the graph's CSR and doomed bytes in LDS once (dynamic: the launch is sized to the largest graph under the
+// RWR_LDS_INTS rule; larger graphs walk from global memory).  Walk lengths are long-tailed: every iteration of the loop is one
+// step of each lane's walk, so the lanes run the same instructions whatever row they are in, and a wave lasts as long as its
+// longest walk.  (Letting a finished lane take another row of the workgroup from a counter in LDS was measured and lost: the
+// calls are bound by their longest walk, and a second row on its lane lengthens that)
+// Rows the law fixes without walking are written without walking: n < k (T == 0), p_restart == 1 with k > 1 (every step
+// restarts: no second vertex), and a seed in a component of fewer than k vertices -- nothing depends on such a walk's length here.
+// rstart[row]: 0, or -1 for a row of -1 (all rwr_fill asks).
+template <int KM>
+__global__ __launch_bounds__(RWR_ROW_LANES) void rwr_row_walks(UgsRwrCall c) {
+    extern __shared__ __attribute__((aligned(16))) int32_t row_csr[];
+    const int tid = threadIdx.x;
+    const int64_t g = blockIdx.x / c.row_wgs;
+    const int64_t s = (int64_t)(blockIdx.x % c.row_wgs) * RWR_ROW_LANES + tid;
+    const int64_t row = g * (int64_t)c.m + s;
+    const UgsRwrGraph gd = c.graphs[g];
+    if (gd.T == 0 || (c.p >= 1.0 && c.k > 1)) {
+        if (s < c.m) { rwr_row_failed(c, row); c.rstart[row] = -1; }
+        return;
+    }
+    RwrView w = global_view(c, g, gd);
+    const int32_t rs0 = c.rs[gd.vbase], D = c.rs[gd.vbase + gd.n] - rs0;
+    if (rwr_csr_words(gd.n, D) <= c.row_lds_ints) {
+        int32_t *lrs = row_csr, *ltg = row_csr + gd.n + 1;
+        uint8_t *ldm = reinterpret_cast<uint8_t *>(ltg + D);
+        for (int v = tid; v <= gd.n; v += RWR_ROW_LANES) lrs[v] = c.rs[gd.vbase + v] - rs0;
+        for (int q = tid; q < D; q += RWR_ROW_LANES) ltg[q] = c.hval2[rs0 + q];
+        for (int v = tid; v < gd.n; v += RWR_ROW_LANES) ldm[v] = c.doomed[gd.vbase + v];
+        __syncthreads();
+        w.rs = lrs; w.tg = ltg; w.doomed = ldm;
+    }
+    if (s >= c.m) return;
+    Chosen<KM> ch;
+    uint64_t z;
+    const int32_t seed = rwr_walk_seed<KM>(row_view(w, (int32_t)s), 0, ch, z);     // the row's seed draw, on its own generator
+    bool found = false;
+    if (!w.doomed[seed]) {
+        int32_t cur = seed;
+        for (int32_t it = 0; ch.cnt < w.k && it < w.T; ++it) (void)rwr_walk_step<KM>(w, seed, cur, ch, z);
+        found = ch.cnt >= w.k;
+    }
+    if (found) rwr_row_found<KM>(c, w, gd, row, ch);
+    else rwr_row_failed(c, row);
+    c.rstart[row] = found ? 0 : -1;
 }
 
 template <int KM>
@@ -367,7 +451,24 @@ void launch_walks(const UgsRwrCall &c, hipStream_t s) {
     hipLaunchKernelGGL((rwr_rows<KM>), dim3(blocks(c.rows, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
 }
 
+template <int KM>
+void launch_row_walks(const UgsRwrCall &c, hipStream_t s) {
+    const size_t lds = (size_t)c.row_lds_ints * sizeof(int32_t);
+    hipLaunchKernelGGL((rwr_row_walks<KM>), dim3((unsigned)(c.G * c.row_wgs)), dim3(RWR_ROW_LANES), lds, s, c);
+}
+
 }  // namespace
+
+void ugs_rwr_row_streams(UgsRwrCall &c, const UgsRwrGraph *graphs, const int64_t *half_edges) {
+    c.row_streams = 1;
+    c.row_wgs = (int32_t)(((int64_t)c.m + RWR_ROW_LANES - 1) / RWR_ROW_LANES);
+    c.row_lds_ints = 0;
+    const bool walks = !(c.p >= 1.0 && c.k > 1);
+    for (int64_t g = 0; walks && g < c.G; ++g) {
+        const int64_t words = rwr_csr_words(graphs[g].n, half_edges[g]);
+        if (graphs[g].T > 0 && words <= RWR_LDS_INTS && words > c.row_lds_ints) c.row_lds_ints = (int32_t)words;
+    }
+}
 
 size_t ugs_rwr_cub_bytes(int64_t E) {
     size_t a = 0;
@@ -389,7 +490,13 @@ hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s) {
     }
     if (c.NV > 0) hipLaunchKernelGGL(rwr_compress, dim3(blocks(c.NV, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
     hipLaunchKernelGGL(rwr_rowstart, dim3(blocks(c.NV + 1, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
-    if (c.rows > 0) {
+    if (c.rows > 0 && c.row_streams) {
+        if (c.G * c.row_wgs > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+        if (c.k <= 8) launch_row_walks<8>(c, s);
+        else if (c.k <= 16) launch_row_walks<16>(c, s);
+        else if (c.k <= 32) launch_row_walks<32>(c, s);
+        else launch_row_walks<64>(c, s);
+    } else if (c.rows > 0) {
         if (c.k <= 8) launch_walks<8>(c, s);
         else if (c.k <= 16) launch_walks<16>(c, s);
         else if (c.k <= 32) launch_walks<32>(c, s);

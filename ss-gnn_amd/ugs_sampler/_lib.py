@@ -73,6 +73,8 @@ def _load():
                                                   C.POINTER(vp), i64p],
         "ugs_rwr_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
                                         C.POINTER(vp), i64p],
+        "ugs_rwr_sample_rows_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_double, vp,
+                                      C.POINTER(vp), i64p],
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],

@@ -5,6 +5,10 @@ of --iters calls after --warmup, one JSON line per shape (also written to --out)
 from the CPU restatement (tests/rwr_law.py).
 
     python tools/rwr_bench.py [--only proteins_k6] [--iters 50] [--warmup 5] [--out profiles/rwr_bench.json]
+    python tools/rwr_bench.py --streams both --rounds 5 --out profiles/rwr_row_streams.json
+
+--streams row times the streams="row" law (one generator per row); --streams both takes the two laws in turn, --rounds medians
+each, and says per shape whether the row law's range lies below the per-graph law's with the medians two spreads apart.
 
 With --reference MODULE.so (a hand-built reference rwr_sampler, see tools/make_golden_rwr.py; run with OMP_NUM_THREADS=1) it
 times that module on the CPU instead, labelled as such.
@@ -62,14 +66,35 @@ def median_ms(fn, iters, warmup, sync):
     return statistics.median(ts)
 
 
+def series(rwr_sampler, e, p, m, k, streams, a, sync):
+    """--rounds medians per value of `streams`, the values taken in turn inside every round"""
+    out = {st: [] for st in streams}
+    for _ in range(a.rounds):
+        for st in streams:
+            out[st].append(round(median_ms(lambda: rwr_sampler.sample_batch(e, p, m, k, streams=st), a.iters, a.warmup, sync), 4))
+    return out
+
+
+def verdict(graph, row):
+    """The issue's test of a shape: row's range below graph's range, medians at least two of the wider spread apart."""
+    spread = max(max(graph) - min(graph), max(row) - min(row))
+    gap = statistics.median(graph) - statistics.median(row)
+    return dict(row_below_graph=max(row) < min(graph), spread_ms=round(spread, 4), median_gap_ms=round(gap, 4),
+                passes=bool(max(row) < min(graph) and gap >= 2 * spread))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--streams", choices=("graph", "row", "both"), default="graph",
+                    help="the law: one generator per graph (default), one per row, or both in turn (--rounds times)")
+    ap.add_argument("--rounds", type=int, default=1, help="medians taken per value of --streams, alternating")
     ap.add_argument("--reference", default="", help="time this hand-built reference module on the CPU instead")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    streams = ("graph", "row") if a.streams == "both" else (a.streams,)
     lines = []
     if a.reference:
         spec = importlib.util.spec_from_file_location("rwr_sampler", a.reference)
@@ -89,12 +114,19 @@ def main():
         else:
             sync = torch.cuda.synchronize
             e_d, p_d = e_h.cuda(), p_h.cuda()
-            host = median_ms(lambda: rwr_sampler.sample_batch(e_h, p_h, m, k), a.iters, a.warmup, sync)
-            dev = median_ms(lambda: rwr_sampler.sample_batch(e_d, p_d, m, k), a.iters, a.warmup, sync)
-            out = rwr_sampler.sample_batch(e_h, p_h, m, k)
-            line.update(draws_per_walk=draws_per_walk(ei, ptr, m, k), failed_rows=int((out[0][:, 0] < 0).sum()),
-                        edge_entries=int(out[1].shape[1]), dropin_ms=round(host, 4), device_ms=round(dev, 4), iters=a.iters,
+            host = series(rwr_sampler, e_h, p_h, m, k, streams, a, sync)
+            dev = series(rwr_sampler, e_d, p_d, m, k, streams, a, sync)
+            line.update(draws_per_walk=draws_per_walk(ei, ptr, m, k), iters=a.iters, rounds=a.rounds,
                         device=torch.cuda.get_device_name(0))
+            for st in streams:
+                out = rwr_sampler.sample_batch(e_h, p_h, m, k, streams=st)
+                tag = "" if st == "graph" else "row_"
+                line.update({tag + "failed_rows": int((out[0][:, 0] < 0).sum()), tag + "edge_entries": int(out[1].shape[1]),
+                             tag + "dropin_ms": statistics.median(host[st]), tag + "device_ms": statistics.median(dev[st])})
+                if a.rounds > 1:
+                    line.update({tag + "dropin_ms_rounds": host[st], tag + "device_ms_rounds": dev[st]})
+            if len(streams) == 2 and a.rounds > 1:
+                line.update(dropin_verdict=verdict(host["graph"], host["row"]), device_verdict=verdict(dev["graph"], dev["row"]))
         print(json.dumps(line), flush=True)
         lines.append(line)
     if a.out:
