@@ -66,7 +66,11 @@ int ugs_set_device(int device);
 int ugs_set_stream(void *stream, int use);
 
 /* ---- preprocessing handles: replaces create_preproc / destroy_preproc / has_graphlets / get_preproc_info
- *      (reference src/preproc.cpp:262-314, pybind names src/extension.cpp:7-10) -------------------------------- */
+ *      (reference src/preproc.cpp:262-314, pybind names src/extension.cpp:7-10) --------------------------------
+ *      k is not limited here, like the reference's: the k <= 32 limit belongs to the sampling entries.  A graph of >= 2^21 columns
+ *      (UGS_DEVICE_PREPROC=1: any graph with a column; =0: none) is preprocessed by the kernels of ugs_preproc.hip when a device
+ *      is present and has room, but only for k <= 32: their breadth-first list has 32 slots, so a larger k always takes the host
+ *      stages.  Both give the reference's values for every k; k <= 0 behaves like k = 1 (every root reaches, every weight is 1). */
 int ugs_create_preproc(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, int64_t num_nodes, int k,
                        int64_t *handle_out);
 int ugs_destroy_preproc(int64_t handle);                       /* unknown handles are ignored, like the reference */
@@ -155,6 +159,13 @@ int ugs_step_stats(int64_t *packed_staged, int64_t *packed_refused);
  * reference src/ugs_sampler_batch_extension.cpp:15-38).  Clearing it is the equivalent of a fresh process. */
 int ugs_cache_clear(void);
 int ugs_cache_stats(int64_t *size, int64_t *hits, int64_t *misses);
+/* Which path preprocessed the graphs of ugs_create_preproc and of the batch calls' LRU misses.  Counters since process start: graphs
+ * whose CSR and root stages ran in ugs_preproc.hip / graphs preprocessed by the host stages (no device, no room, fewer than 2^21
+ * columns, k > 32, no column or no vertex, UGS_DEVICE_PREPROC=0) / plan pieces whose adjacency arrays were written on the device from
+ * the CSR such a graph left in HBM (the first plan assembled from it; a graph without entries counts, there is nothing to write)
+ * instead of being copied from the host.  Graphs the device batch pass builds are counted by ugs_batch_pass_stats, not here.
+ * Any pointer may be NULL. */
+int ugs_preproc_stats(int64_t *device_graphs, int64_t *host_graphs, int64_t *device_pieces);
 /* The input side of ugs_sample_batch_begin / ugs_plan_create_batch for batches of small graphs runs on the device (SURVEY.md
  * 8(f) N4): one pass over edge_index + ptr replaces the reference's per-graph slicing (src/ugs_sampler_batch_extension.cpp:41-75),
  * hashing (include/cache.hpp:81-109) and CSR construction (src/preproc.cpp:32-86); the host replays the LRU on the G keys that

@@ -269,6 +269,10 @@ void graph_fingerprint(const int64_t *u, const int64_t *v, int64_t cols, int64_t
 
 int preprocess_on_device(Graph &G, const int64_t *src, const int64_t *dst, int64_t E, int k, bool &done);   // below, after the device helpers
 
+// which path preprocessed / assembled what (ugs_preproc_stats): graphs through ugs_preproc.hip, graphs through the host stages of
+// make_graph, plan pieces handed to ugs_devpre_assemble
+std::atomic<int64_t> g_pre_device_graphs{0}, g_pre_host_graphs{0}, g_pre_device_pieces{0};
+
 int make_graph(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int k, std::shared_ptr<Graph> &out) {
     if (n < 0) return fail(UGS_E_BAD_ARG, "num_nodes must be >= 0");
     if (n >= ((int64_t)1 << 30) - 1 || E >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "graph too large: num_nodes must be < 2^30 - 1 and columns < 2^31 - 1");
@@ -280,6 +284,7 @@ int make_graph(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int
     if (int rc = preprocess_on_device(*G, src, dst, E, k, on_device)) return rc;
     if (!on_device) {
         Lap lap;
+        g_pre_host_graphs.fetch_add(1);
         build_adjacency(*G, src, dst, E);
         if (G->nnz >= (int64_t)INT32_MAX) return fail(UGS_E_UNSUPPORTED, "graph too large: CSR entries must be < 2^31 - 1");
         const double t_csr = lap();
@@ -559,6 +564,7 @@ int preprocess_on_device(Graph &G, const int64_t *src, const int64_t *dst, int64
     if (env && env[0] == '0') return UGS_OK;
     const bool forced = env && env[0] == '1';
     if (G.n < 1 || E < 1 || E >= ((int64_t)1 << 30)) return UGS_OK;
+    if (k > UGS_KMAX) return UGS_OK;       // pre_roots keeps the <= k reached vertices in UGS_KMAX private slots; the host form has no bound on k
     if (!forced && E < ((int64_t)1 << 21)) return UGS_OK;
     DeviceCtx dc;
     {
@@ -588,6 +594,7 @@ int preprocess_on_device(Graph &G, const int64_t *src, const int64_t *dst, int64
                      "CSR download %.3fs\n", (long long)G.n, (long long)E, t_csr, t_order, t_roots, lap());
     ugs_devpre_trim(d);
     { std::lock_guard<std::mutex> lk(G.pre_mu); G.devpre = d; G.devpre_dev = dc.id; d = nullptr; }
+    g_pre_device_graphs.fetch_add(1);
     done = true;
     return UGS_OK;
 }
@@ -658,6 +665,7 @@ int assemble_plan(const std::vector<PlanPiece> &pieces, const DeviceCtx &dc, ugs
                 const int64_t *cm = pc.colmap;
                 if (cm) { bool ident = true; for (int64_t c = 0; c < pc.ncols && ident; ++c) ident = cm[c] == c; if (ident) cm = nullptr; }
                 e = ugs_devpre_assemble(dp, cm, pc.ncols, d_adj, d_adjf, dc.stream);
+                if (e == hipSuccess) g_pre_device_pieces.fetch_add(1);
             } else if (g.nnz > 0) {
                 tmp_a.resize((size_t)g.nnz); tmp_f.resize((size_t)g.nnz);
                 fill_adj(pc, tmp_a.data(), tmp_f.data());
@@ -1598,6 +1606,13 @@ int64_t ugs_batch_pass_max_cols(void) { return batch_pass_max_cols(); }
 int ugs_batch_pass_stats(int64_t *device_plans, int64_t *general_path) {
     if (device_plans) *device_plans = g_bp_plans.load();
     if (general_path) *general_path = g_bp_fallbacks.load();
+    return UGS_OK;
+}
+
+int ugs_preproc_stats(int64_t *device_graphs, int64_t *host_graphs, int64_t *device_pieces) {
+    if (device_graphs) *device_graphs = g_pre_device_graphs.load();
+    if (host_graphs) *host_graphs = g_pre_host_graphs.load();
+    if (device_pieces) *device_pieces = g_pre_device_pieces.load();
     return UGS_OK;
 }
 

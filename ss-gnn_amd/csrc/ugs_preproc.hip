@@ -169,6 +169,7 @@ hipError_t ugs_devpre_csr(UgsDevPre **out, const int64_t *h_src, const int64_t *
 hipError_t ugs_devpre_roots(UgsDevPre *d, const int32_t *h_order, const int32_t *h_rank, int k, int32_t *h_sdeg, uint8_t *h_reach) {
     const int64_t n = d->n, n1 = n > 0 ? n : 1;
     hipStream_t s = d->stream;
+    if (k > UGS_KMAX) return hipErrorInvalidValue;         // pre_roots' list has UGS_KMAX slots: the caller keeps larger k on the host
     PRE_TRY(hipMalloc(&d->order, (size_t)n1 * 4));
     PRE_TRY(hipMalloc(&d->rank, (size_t)n1 * 4));
     PRE_TRY(hipMalloc(&d->sdeg, (size_t)n1 * 4));

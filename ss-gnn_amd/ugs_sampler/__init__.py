@@ -357,6 +357,14 @@ def batch_pass_stats():
     return {"device_plans": a.value, "general_path": b.value}
 
 
+def preproc_stats():
+    """{"device_graphs": graphs whose CSR and root stages ran in the preprocessing kernels, "host_graphs": graphs the host stages
+    preprocessed, "device_pieces": plan pieces whose adjacency was written on the device from such a graph's CSR} since process start."""
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.ugs_preproc_stats(C.byref(a), C.byref(b), C.byref(c)))
+    return {"device_graphs": a.value, "host_graphs": b.value, "device_pieces": c.value}
+
+
 def batch_pass_max_cols():
     """Columns per graph up to which the device batch pass applies (default 1000, or UGS_BATCH_PASS_MAX_COLS from the environment)."""
     return int(lib.ugs_batch_pass_max_cols())

@@ -78,6 +78,7 @@ def _load():
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
+        "ugs_preproc_stats": [i64p, i64p, i64p],
         "ugs_set_batch_pass_max_cols": [C.c_int64, i64p],
         "ugs_uniform_set_max_vertices": [C.c_int, C.POINTER(C.c_int)],
         "ugs_uniform_set_mask_vertices": [C.c_int, C.POINTER(C.c_int)],

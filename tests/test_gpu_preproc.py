@@ -61,9 +61,14 @@ def _cases():
 
 
 def test_device_preprocessing_equals_host_and_oracle(forced_device):
+    import ugs_sampler
+    count = lambda: tuple(ugs_sampler.preproc_stats()[x] for x in ("device_graphs", "host_graphs", "device_pieces"))
     for ei, n, k in _cases():
+        d0, h0, p0 = count()
         dev, idev = _dump(ei, n, k, "1")
+        assert count() == (d0 + 1, h0, p0), (n, k, "the forced device path did not take the graph")
         host, ihost = _dump(ei, n, k, "0")
+        assert count() == (d0 + 1, h0 + 1, p0), (n, k, "the host path did not take the graph")
         P = oracle.Preproc(ei, n, k)
         want = P.dump()
         for key in want:
