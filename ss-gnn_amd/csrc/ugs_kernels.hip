@@ -60,9 +60,17 @@ __device__ unsigned long long ugs_stamp_buffer[32];
 #define STAMP_END(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); \
     if ((threadIdx.x & 63) == 0) { atomicAdd(&ST_[i], t1_ - st_t0); atomicAdd(&ST_[16 + (i)], 1ull); } st_t0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 // a routine inside the select phase: its time moves from slot 2 to slot i
+// (-DUGS_STAMPS_FLAT beside -DUGS_STAMPS: no nested stamps, a routine stays in its phase's slot.  The nested stamps cost a walk more than
+// a fifth of its cycles -- two s_memtime between scheduling barriers and three LDS atomics per routine, most of it charged to the parent
+// slot -- so a phase's share without its routines is read from the two builds together: profiles/step_glue_stamps_flat.txt.)
+#ifdef UGS_STAMPS_FLAT
+#define STAMP_SUB_BEGIN() do {} while (0)
+#define STAMP_SUB_END_OF(parent, i) do {} while (0)
+#else
 #define STAMP_SUB_BEGIN() __builtin_amdgcn_sched_barrier(0); const unsigned long long sti_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
 #define STAMP_SUB_END_OF(parent, i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); \
     if ((threadIdx.x & 63) == 0) { atomicAdd(&ST_[i], t1_ - sti_); atomicAdd(&ST_[parent], sti_ - t1_); atomicAdd(&ST_[16 + (i)], 1ull); } __builtin_amdgcn_sched_barrier(0); } while (0)
+#endif
 #define STAMP_SUB_END(i) STAMP_SUB_END_OF(2, i)
 #else
 #define STAMP_DECL
@@ -1643,12 +1651,38 @@ __device__ __forceinline__ void flush_parked(const Grp<64> &g_, const FlushOut &
 // DRAWS (the launch-uniform walk in the dynamic work loop, k + 1 <= 16: the launcher picks the instantiation): the walk's random
 // numbers were drawn for its whole chunk (chunk_draws); number t of this row is read from lane dcur + t into scalar registers and
 // the generator is not run.
+// The launch-uniform walk (UNI) runs one graph for the whole launch: its descriptor is read ONCE per kernel instead of once per walk,
+// where it was a vector load with a full wait in front of every walk and a second pair of loads behind it.  The plan's descriptors
+// are written before the launch and by nobody during it, so they are read as constant memory: scalar loads, the words land in scalar
+// registers (a plain load of the struct goes through the vector unit and keeps the derived bases in vector register pairs).
+// What a walk derives from the descriptor is folded in here: the graph's first vertex goes into the bases of the padded rows, the
+// root records and the viable list (`vbase` and `viable_base` are zero from here on: a row's address is one shift of the vertex).
+struct UniLaunch {
+    UgsPlanDev plan;
+    UgsGraphDesc gd;
+    __device__ __forceinline__ void init(const UgsWalkArgs &a) {
+        plan = a.plan;
+        static_assert(sizeof(UgsGraphDesc) == 48 && offsetof(UgsGraphDesc, n) == 32 && offsetof(UgsGraphDesc, n_viable) == 40, "read word by word below");
+        const uint64_t __attribute__((address_space(4))) *q = (const uint64_t __attribute__((address_space(4))) *)(uintptr_t)a.plan.graphs;
+        const uint64_t nl = q[4];
+        gd.node_lo = (int64_t)q[0]; gd.rbase = (int64_t)q[1]; gd.vbase = (int64_t)q[2]; gd.viable_base = (int64_t)q[3];
+        gd.n = (int32_t)(uint32_t)nl; gd.level = (int32_t)(uint32_t)(nl >> 32); gd.n_viable = (int32_t)(uint32_t)q[5]; gd.pad = 0;
+        // (the padded rows of a plan span less than 4 GB, prow_entry: the 32-bit entry index of vbase + v splits without a carry)
+        plan.prow += (uint32_t)gd.vbase << plan.prow_shift;
+        plan.roots += gd.vbase;
+        plan.viable += gd.viable_base;
+        gd.vbase = 0;
+        gd.viable_base = 0;
+    }
+};
+
 template <int GS, class SP, int MAXPER, bool PAD, bool SEEDS = false, bool UNI = false, bool BATCH = false, bool DRAWS = false>
 __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, const UgsWalkArgs &a, int64_t row_rel,
                                         uint32_t *SV /* [UGS_KMAX] group-private */, uint4 *EL /* [UGS_STAGE_ENTRIES] or null */,
                                         uint32_t *nedges_out = nullptr /* the row's edge-entry count (0 if the walk is handed on) */,
                                         Parked *pk = nullptr, int64_t *poff = nullptr, bool park = false,
-                                        const ChunkDraws *cd = nullptr, uint32_t dcur = 0u /* lane of this row's first number */) {
+                                        const ChunkDraws *cd = nullptr, uint32_t dcur = 0u /* lane of this row's first number */,
+                                        const UniLaunch *ul = nullptr /* UNI: the launch's plan and graph */) {
     static_assert(!BATCH || (GS == 64 && sizeof(typename SP::TW) == 4), "parked rows: one walk per wave, LDS tiers");
     static_assert(!DRAWS || (UNI && BATCH), "lane-parallel draws: the launch-uniform walk in the dynamic work loop");
 
@@ -1664,12 +1698,12 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
         asm volatile("" : "+s"(on32));
         sc.onm = 0ull - (uint64_t)on32;
     }
-    const UgsPlanDev &P = a.plan;
+    const UgsPlanDev &P = UNI ? ul->plan : a.plan;
     const int64_t row = a.row_begin + row_rel;
     int64_t gi, i;
     if (UNI || P.num_graphs == 1) { gi = 0; i = row; }
     else { gi = row / a.m; i = row - gi * a.m; }
-    const UgsGraphDesc gd = P.graphs[gi];
+    const UgsGraphDesc gd = UNI ? ul->gd : P.graphs[gi];
     const int k = a.k;
     int64_t *out = a.nodes + row_rel * k;
     if (nedges_out) *nedges_out = 0u;
@@ -2018,6 +2052,8 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
     ws.ST = stamps;
     struct Flush { unsigned long long *st; __device__ ~Flush() { __syncthreads(); if (threadIdx.x < 32) atomicAdd(&ugs_stamp_buffer[threadIdx.x], st[threadIdx.x]); } } flush_{stamps};
 #endif
+    [[maybe_unused]] UniLaunch ul;
+    if constexpr (UNI) ul.init(a);
     const int64_t total = (!UNI && a.in_list) ? (int64_t)*a.in_count : a.row_count;
     const int64_t ngroups = (int64_t)gridDim.x * GROUPS;
     // Work distribution.  Dynamic (a.work_next, launches with many more walks than resident groups): chunks of UGS_WORK_CHUNK
@@ -2047,14 +2083,14 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         while (it < total) {
             if (end > total) end = total;
             uint32_t dcur = 0u;
-            if constexpr (DRAWS) chunk_draws(cd, a.seed_ptr ? *a.seed_ptr : a.seed64, a.row_begin + it, a.k + 1, a.plan.graphs);
+            if constexpr (DRAWS) chunk_draws(cd, a.seed_ptr ? *a.seed_ptr : a.seed64, a.row_begin + it, a.k + 1, &ul.gd);
             for (; it < end; ++it) {
                 const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
                 Parked res{0u, 0u};
                 int64_t off = 0;
                 const uint32_t dlane = dcur;
                 dcur += (uint32_t)kDrawLanes;
-                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI, BT, DRAWS>(ws, g, a, row_rel, SV, EL, nullptr, &res, &off, park, &cd, dlane)) {
+                if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI, BT, DRAWS>(ws, g, a, row_rel, SV, EL, nullptr, &res, &off, park, &cd, dlane, &ul)) {
                     if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
                 }
                 if constexpr (BT) {
@@ -2123,7 +2159,7 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
     }
     for (int64_t it = (int64_t)blockIdx.x * GROUPS + gib; it < total; it += ngroups) {
         const int64_t row_rel = (!UNI && a.in_list) ? a.in_list[it] : it;
-        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI>(ws, g, a, row_rel, SV, EL)) {
+        if (!do_walk<GS, LdsSpace, (CAP + GS - 1) / GS, PAD, SEEDS, UNI>(ws, g, a, row_rel, SV, EL, nullptr, nullptr, nullptr, false, nullptr, 0u, &ul)) {
             if (g.lane == 0 && a.ovf_list) { uint32_t pos = atomicAdd(a.ovf_count, 1u); a.ovf_list[pos] = row_rel; }
         }
     }
