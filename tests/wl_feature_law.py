@@ -8,7 +8,7 @@ sit on a BLAKE2b block boundary."""
 import hashlib
 from collections import Counter
 
-from wl_law import STATUS_BAD_ENDPOINT, STATUS_EMPTY, STATUS_OK, _h, final_text, row_masks
+from wl_law import STATUS_BAD_ENDPOINT, STATUS_EMPTY, STATUS_OK, _h, bad_range, final_text, row_masks
 
 STATUS_BAD_LABEL = 3
 
@@ -53,13 +53,20 @@ def wl_feature_row(nodes_row, src, dst, labels, iterations=3):
     return hx, STATUS_OK, lens, flen
 
 
-def wl_feature_rows(nodes, edge_index, edge_ptr, labels, iterations=3):
+def wl_feature_rows(nodes, edge_index, edge_ptr, labels, iterations=3, num_cols=None):
     """The law over a sampler's three outputs and the labels by vertex id (a list of ints, e.g. labels_of(x)).
-    Returns (hexdigests: list of str or None, statuses: list of int, reports: list of (message lengths, final length))."""
+    Returns (hexdigests: list of str or None, statuses: list of int, reports: list of (message lengths, final length)).
+    Rule 4 of ugs_wl_hash as in wl_law.wl_rows: an edge_ptr range that is no range of [0, num_cols] gives status 2 whatever the
+    row's ids and labels, status 1 where the row has no vertex."""
+    num_cols = len(edge_index[0]) if num_cols is None else int(num_cols)
     hexes, stats, reports = [], [], []
     for i in range(len(nodes)):
         lo, hi = int(edge_ptr[i]), int(edge_ptr[i + 1])
-        hx, st, lens, flen = wl_feature_row(nodes[i], edge_index[0][lo:hi], edge_index[1][lo:hi], labels, iterations)
+        if bad_range(lo, hi, num_cols):
+            empty = not any(int(x) >= 0 for x in nodes[i])
+            hx, st, lens, flen = None, STATUS_EMPTY if empty else STATUS_BAD_ENDPOINT, [], 0
+        else:
+            hx, st, lens, flen = wl_feature_row(nodes[i], edge_index[0][lo:hi], edge_index[1][lo:hi], labels, iterations)
         hexes.append(hx)
         stats.append(st)
         reports.append((lens, flen))
