@@ -532,6 +532,60 @@ int ugs_rwr_sample_rows_begin(const int64_t *edge_index, int64_t row_stride, int
                               int64_t num_graphs, int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds,
                               double p_restart, int32_t *graph_status, ugs_job **job_out, int64_t *total_edges_out);
 
+/* ---- rwr_sampler.GraphCache: the CSR of every dataset graph -- row starts, targets in (column, side) row order, doomed bytes --
+ *      built once by the stages of ugs_rwr_sample_batch_begin and kept on one device; a sample call over any batch of added graphs
+ *      runs only the walks, the scan and the fill.  A cache is fixed to one k: doomed[v] says "v's component has fewer than k
+ *      vertices".
+ *      create(k, reserve_vertices, reserve_columns): no device work; k as ugs_rwr_sample_batch_begin checks it.  The storage is
+ *      allocated at the first add, on the calling thread's device, with room for at least the reservation (vertices: the graphs'
+ *      vertices plus one entry per add), and grows by reallocation and a device-to-device copy to at least twice its size.  Each
+ *      allocation is a generation: a job holds the one it walked on until it is finished or cancelled, so an add never invalidates
+ *      a job in flight, and destroy may be called with jobs in flight.
+ *      add(edge_index, ptr, G): a batch of graphs, vertices [ptr[g], ptr[g+1]).  Every column must lie inside one graph and the
+ *      columns must come graph by graph, in the order of the graphs (UGS_E_BAD_ARG otherwise): each graph's columns are stored as
+ *      given, in their order.  slots_out[g] is the graph's slot (never reused; adding a graph again gives a new one, the old
+ *      bytes stay until destroy).  A graph with n >= k and 10 n k > INT_MAX gets a slot marked failed, status_out[g] = 1, and takes
+ *      no storage.  Limits, UGS_E_UNSUPPORTED with the cache left as it was: the half-edges of all adds < 2^31 (row starts are
+ *      32-bit offsets into one target array), vertices plus adds < 2^31, 2^30 columns per add.  Synchronous.  Adds are exclusive
+ *      among themselves; any number of threads may sample meanwhile.
+ *      info: slots, entries of the row-start array, half-edges held, bytes of the current generation, generations so far (any may
+ *      be NULL).
+ *      sample_begin.  THE CONTRACT.  Let B be the batch whose columns are, for g = 0 ... G-1 in order, the columns stored for
+ *      slots[g], each shifted by ptr[g] -- what collating the added graphs in that order produces.  The call, finished with
+ *      ugs_rwr_sample_batch_finish, gives bit for bit what these calls give on (B, ptr) with the cache's k:
+ *        - seeds == NULL, row_streams == 0: ugs_rwr_sample_batch_begin (graph g seeded with seed + g, g the batch position);
+ *        - seeds != NULL, row_streams == 0: ugs_rwr_sample_graphs_begin (seeds[g]);
+ *        - row_streams != 0: ugs_rwr_sample_rows_begin in the matching form;
+ *      all five tensors, and graph_status in the per-graph-seed forms (a failed slot: m rows of -1, graph_status[g] = 1; with
+ *      seeds == NULL such a slot is UGS_E_UNSUPPORTED with the uncached call's text).  The walk, row and fill kernels are the
+ *      uncached call's own: they read a graph only through its descriptor {lo, vbase, n, T}, the row starts and doomed bytes at
+ *      vbase and the target array, so vbase = the slot's vertex offset in the store serves them unchanged.
+ *      Before any device work: every slot exists, ptr[g+1] - ptr[g] is the slot's vertex count (UGS_E_BAD_ARG naming the graph and
+ *      both counts), and, when edge_index is given or check != 0, num_cols equals the slots' column counts together
+ *      (UGS_E_BAD_ARG "the batch has E columns, the added graphs have S").
+ *      check != 0: the batch's edge_index goes up with the descriptors and one kernel compares every column e, of the graph g with
+ *      coff[g] <= e < coff[g+1] (coff: prefix sums of the slots' column counts), with the stored column; the smallest g with a
+ *      column that differs comes back in the read-back of the edge total, and the call fails with UGS_E_BAD_ARG "graph g of the
+ *      batch differs from the graph added in its place".  The check is exact, not a fingerprint: it can never accept a batch that
+ *      is not B.  It is stricter than the equality above needs -- it also refuses a batch whose columns are permuted in a way
+ *      that leaves every adjacency row as it was (columns of different graphs interleaved, two columns without a common vertex
+ *      swapped).  A failed slot stores no columns and its part of the batch is not compared: its rows are -1 whatever they are.
+ *      check == 0: edge_index is not read and may be NULL (num_cols is then ignored); for a batch that is not B the result is
+ *      that of B (never a fault: nothing of the batch but ptr is read).
+ *      Host work is O(G); the blob holds descriptors, seeds, the check's columns and the walks' scratch -- no half-edge arrays,
+ *      no sort scratch.  Same job protocol, stream rules and ugs_job_cancel as the other jobs. */
+typedef struct ugs_rwr_cache ugs_rwr_cache;
+int ugs_rwr_cache_create(int k, int64_t reserve_vertices, int64_t reserve_columns, ugs_rwr_cache **cache_out);
+int ugs_rwr_cache_destroy(ugs_rwr_cache *cache);
+int ugs_rwr_cache_add(ugs_rwr_cache *cache, const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                      int64_t num_graphs, int64_t *slots_out, int32_t *status_out);
+int ugs_rwr_cache_info(ugs_rwr_cache *cache, int64_t *graphs_out, int64_t *vertices_out, int64_t *half_edges_out, int64_t *bytes_out,
+                       int64_t *generations_out);
+int ugs_rwr_cache_sample_begin(ugs_rwr_cache *cache, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                               int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, uint64_t seed,
+                               const uint64_t *seeds, double p_restart, int row_streams, int check, int32_t *graph_status,
+                               ugs_job **job_out, int64_t *total_edges_out);
+
 /* ---- uniform_sampler.sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode) / PopulationCache.sample_distinct: sampling
  *      WITHOUT replacement from the finite population S_g -- m distinct connected k-subsets per graph, every ordered selection
  *      equally likely, and the whole population, in its order, when it has at most m sets (the "full bag": no sampling variance

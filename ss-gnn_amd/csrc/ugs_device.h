@@ -345,7 +345,25 @@ struct UgsRwrCall {
 size_t ugs_rwr_cub_bytes(int64_t E);
 // makes c a row-streams call; graphs[G] and half_edges[G] (twice the columns inside each graph) are host arrays
 void ugs_rwr_row_streams(UgsRwrCall &c, const UgsRwrGraph *graphs, const int64_t *half_edges);
-hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s);
+hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s);      // ugs_rwr_build, then ugs_rwr_walks
+hipError_t ugs_rwr_build(const UgsRwrCall &c, hipStream_t s);      // rwr_init ... rwr_rowstart: rs, hval2 and doomed of the batch
+hipError_t ugs_rwr_walks(const UgsRwrCall &c, hipStream_t s);      // the walks and the scan, from whatever rs, hval2 and doomed point at
+// rwr_sampler.GraphCache: the store is one "batch of all added graphs".  An add occupies NV + 1 entries of
+// rs (absolute offsets into tg) and of doomed, 2E of tg and E of cols; a graph's vbase is its vertex offset in rs.
+struct UgsRwrStore {
+    int32_t *rs, *tg; uint8_t *doomed; int2 *cols;       // the storage generation being written
+    int64_t rs_base, tg_base, col_base;                  // where this add goes: behind everything the store holds
+};
+hipError_t ugs_rwr_store_append(const UgsRwrCall &c, const UgsRwrStore &st, hipStream_t s);     // after ugs_rwr_build(c)
+struct UgsRwrCheck {
+    int64_t E, G;
+    const int64_t *src, *dst;                            // the batch's columns
+    const UgsRwrGraph *graphs;                           // [G] (lo = ptr[g])
+    const int64_t *coff, *col0;                          // [G + 1] prefix sums of the slots' column counts; [G] first stored column, -1: none
+    const int2 *cols;                                    // the store's columns
+    int32_t *first_bad;                                  // atomicMin of the graphs with a column that differs
+};
+hipError_t ugs_rwr_store_check(const UgsRwrCheck &k, hipStream_t s);
 hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 
 // ---- epsilon_uniform_sampler (ugs_eps.hip): one launcher for the walk (fill = 0: nodes and per-row counts) and the fill ----

@@ -21,6 +21,9 @@
 // streams = "row" (ugs_rwr_sample_rows_begin: one generator per row, seeded with output s of the graph's) runs rwr_init ...
 // rwr_rowstart as above, then rwr_row_walks in place of rwr_resolve + rwr_rows -- every walk is independent, there is no chain
 // to follow and no doomed walk to measure -- then the same scan and rwr_fill.
+// rwr_sampler.GraphCache runs rwr_init ... rwr_rowstart once per dataset graph (ugs_rwr_build) and
+// rwr_store_append copies the result into a store laid out as one batch of all added graphs; a cached call then runs only
+// rwr_store_check and the walks, scan and fill (ugs_rwr_walks, ugs_rwr_fill) with rs / hval2 / doomed pointing into the store.
 //
 // Doomed walks (seed in a component smaller than k) always run all 10 n k iterations.  Speculation stops them after the seed
 // draw; when the chain reaches one, its length comes from the RNG alone (rwr_doomed_len): without edges every iteration takes one
@@ -28,6 +31,8 @@
 #include "ugs_device.h"
 
 #include <hipcub/hipcub.hpp>
+
+#include <algorithm>
 
 namespace {
 
@@ -443,6 +448,41 @@ __global__ __launch_bounds__(RWR_BLOCK) void rwr_fill(UgsRwrCall c, int64_t *edg
     }
 }
 
+// ---- rwr_sampler.GraphCache: the CSRs of a dataset's graphs, built once by the stages above ----
+// Appends the batch that rwr_init ... rwr_rowstart have just built to the store, behind everything it holds: row starts made
+// absolute offsets into the store's targets (the walk, row and fill kernels read a graph only through rs + vbase, the targets
+// and doomed + vbase, so they serve a store laid out as one batch of all added graphs), targets, doomed bytes, and every column
+// narrowed to a pair of local vertex ids, in the order given (what rwr_store_check compares a batch with).  The host has made
+// room, and has seen that every column lies inside one graph: no half-edge was dropped, the sorted targets are all 2E.
+__global__ __launch_bounds__(RWR_BLOCK) void rwr_store_append(UgsRwrCall c, UgsRwrStore st) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x <= c.NV) st.rs[st.rs_base + x] = c.rs[x] + (int32_t)st.tg_base;
+    if (x < c.NV) st.doomed[st.rs_base + x] = c.doomed[x];
+    if (x < 2 * c.E) st.tg[st.tg_base + x] = c.hval2[x];
+    if (x < c.E) {
+        const int64_t u = c.src[x], v = c.dst[x];
+        int64_t lo = 0, hi = c.G;                                   // the graph that holds u, as rwr_halfedges finds it
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (c.ptr[mid + 1] <= u) lo = mid + 1; else hi = mid; }
+        const int64_t glo = c.ptr[lo < c.G ? lo : c.G];
+        st.cols[st.col_base + x] = make_int2((int32_t)(u - glo), (int32_t)(v - glo));
+    }
+}
+
+// The check of a cached call: batch column e belongs to the graph g with coff[g] <= e < coff[g + 1] and must be, shifted by
+// ptr[g], the column stored at col0[g] + e - coff[g].  first_bad: the smallest g with a column that is not (host: set to a
+// value above every g).  col0[g] < 0: a graph without stored columns (it failed when it was added; it is never walked).
+__global__ __launch_bounds__(RWR_BLOCK) void rwr_store_check(UgsRwrCheck k) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= k.E) return;
+    int64_t lo = 0, hi = k.G - 1;                                   // the last g with coff[g] <= e (coff[0] = 0, coff[G] = E > e)
+    while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (k.coff[mid] <= e) lo = mid; else hi = mid - 1; }
+    const int64_t c0 = k.col0[lo];
+    if (c0 < 0) return;
+    const int2 want = k.cols[c0 + e - k.coff[lo]];
+    const int64_t base = k.graphs[lo].lo;
+    if (k.src[e] - base != (int64_t)want.x || k.dst[e] - base != (int64_t)want.y) atomicMin(k.first_bad, (int32_t)lo);
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 template <int KM>
@@ -477,7 +517,7 @@ size_t ugs_rwr_cub_bytes(int64_t E) {
     return a;
 }
 
-hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s) {
+hipError_t ugs_rwr_build(const UgsRwrCall &c, hipStream_t s) {
     hipError_t e;
     if (c.NV > 0) hipLaunchKernelGGL(rwr_init, dim3(blocks(c.NV, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
     if (c.E > 0) {
@@ -490,6 +530,11 @@ hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s) {
     }
     if (c.NV > 0) hipLaunchKernelGGL(rwr_compress, dim3(blocks(c.NV, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
     hipLaunchKernelGGL(rwr_rowstart, dim3(blocks(c.NV + 1, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c);
+    return hipSuccess;
+}
+
+hipError_t ugs_rwr_walks(const UgsRwrCall &c, hipStream_t s) {
+    hipError_t e;
     if (c.rows > 0 && c.row_streams) {
         if (c.G * c.row_wgs > (int64_t)INT32_MAX) return hipErrorInvalidValue;
         if (c.k <= 8) launch_row_walks<8>(c, s);
@@ -504,6 +549,23 @@ hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s) {
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ugs_launch_scan(c.ecount, c.rows, c.edge_ptr, c.scan_tmp, s);
+}
+
+hipError_t ugs_rwr_begin(const UgsRwrCall &c, hipStream_t s) {
+    if (hipError_t e = ugs_rwr_build(c, s); e != hipSuccess) return e;
+    return ugs_rwr_walks(c, s);
+}
+
+hipError_t ugs_rwr_store_append(const UgsRwrCall &c, const UgsRwrStore &st, hipStream_t s) {
+    const int64_t n = std::max<int64_t>(c.NV + 1, 2 * c.E);
+    hipLaunchKernelGGL(rwr_store_append, dim3(blocks(n, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, c, st);
+    return hipGetLastError();
+}
+
+hipError_t ugs_rwr_store_check(const UgsRwrCheck &k, hipStream_t s) {
+    if (k.E <= 0 || k.G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rwr_store_check, dim3(blocks(k.E, RWR_BLOCK)), dim3(RWR_BLOCK), 0, s, k);
+    return hipGetLastError();
 }
 
 hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s) {

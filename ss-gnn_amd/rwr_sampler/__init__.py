@@ -14,13 +14,21 @@ seeded with seeds[g] instead of seed + g (the presample loop batched; law at ugs
 Both take the keyword streams="graph" (the default: the law above, unchanged) or streams="row": one SplitMix64 per ROW, seeded
 with output s of the graph's generator, so that every walk is independent -- same distribution, reproducible, a row independent of
 m and of the other rows, and each row still row 0 of a one-graph, m = 1 call of the reference (law at ugs_rwr_sample_rows_begin).
+
+GraphCache(k, device) builds the CSR of every dataset graph once (add / add_many) and keeps it on the device: cache.sample_batch /
+cache.sample_graphs over any batch of added graphs equal the module's calls bit for bit, with either `streams`, while running
+only the walks, the scan and the fill.  Contract at ugs_rwr_cache_sample_begin.
 """
 import ctypes as C
 
+import numpy as np
+import torch
+
 from ugs_sampler import _graphs
+from ugs_sampler._lib import check as _check
 from ugs_sampler._lib import lib
 
-__all__ = ["sample_batch", "sample_graphs"]
+__all__ = ["sample_batch", "sample_graphs", "GraphCache"]
 
 
 def _row_streams(streams):
@@ -56,3 +64,201 @@ def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", p_rest
     else:
         begin = lambda batch, md, sd, st, out: lib.ugs_rwr_sample_graphs_begin(*batch, md, sd, p, st, *out)
     return _graphs.sample_graphs(begin, lib.ugs_rwr_sample_batch_finish, edge_index, ptr, m_per_graph, k, seeds, mode, device)
+
+
+# add_many's call bound: columns and vertices per device call (the build's scratch is 56 bytes per column)
+CHUNK_COLUMNS = 1 << 24
+
+
+class GraphCache:
+    """The CSRs of a dataset's graphs, built once and kept on `device`, for one k.
+
+        cache = GraphCache(k, "cuda:0")
+        cache.add_many(range(len(dataset)), [(d.edge_index, d.num_nodes) for d in dataset])          # start-up
+        five = cache.sample_batch(batch.graph_idx, batch.ptr, batch.edge_index, m, mode, seed)       # every step
+
+    If the batch's columns are, graph by graph in batch order, the columns of the graphs added under graph_idx[g], each shifted
+    by ptr[g] -- what collating those graphs produces -- cache.sample_batch equals rwr_sampler.sample_batch(edge_index, ptr, m, k,
+    mode, seed, p_restart, streams=streams) in all five tensors and cache.sample_graphs equals rwr_sampler.sample_graphs in all six.
+    check=True (the default) uploads the batch's edge_index and compares every column with the stored one, exactly: any other
+    batch raises RuntimeError, also one whose columns are merely permuted.  check=False reads nothing of the batch but ptr
+    (edge_index may be None): the result is that of the added graphs, whatever the batch holds.
+
+    A graph with n >= k and 10 n k past the reference's int is recorded in `failed` and takes no storage: sample_batch on a batch
+    that names it raises the uncached call's RuntimeError, sample_graphs gives it m rows of -1 and failed[g] = True.  Adding an
+    index again replaces it (the old bytes stay until close).  reserve=(vertices, columns) sizes the first allocation; the storage
+    grows by doubling, and a call begun before an add finishes on the buffers it started with.  Adds are exclusive; any number of
+    threads may sample at once."""
+
+    def __init__(self, k, device, *, reserve=(0, 0)):
+        self.k = int(k)
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise ValueError("device must be a GPU device")
+        rv, rc = (int(x) for x in reserve)
+        if rv < 0 or rc < 0:
+            raise ValueError(f"reserve must be two counts >= 0, got {reserve}")
+        self.failed = set()
+        self._slot = {}                 # graph index -> (slot, vertices, columns)
+        self._cache = C.c_void_p()
+        _check(lib.ugs_rwr_cache_create(self.k, rv, rc, C.byref(self._cache)))
+
+    def close(self):
+        """Frees the storage (once the jobs still sampling from it have finished); the object cannot be used afterwards."""
+        if getattr(self, "_cache", None):
+            lib.ugs_rwr_cache_destroy(self._cache)
+            self._cache = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001  (interpreter shutdown: the library may be gone already)
+            pass
+
+    def _handle(self):
+        if not self._cache:
+            raise RuntimeError("the cache is closed")
+        return self._cache
+
+    def add(self, index, edge_index, num_nodes):
+        """One graph; same effect as add_many of one.  Returns False if the graph failed."""
+        self.add_many([index], [(edge_index, num_nodes)])
+        return int(index) not in self.failed
+
+    def add_many(self, indices, graphs):
+        """`graphs` holds (edge_index, num_nodes) per index, local vertex ids as a dataset stores them.  A column with an endpoint
+        outside [0, num_nodes) raises ValueError naming the index, and nothing of the call is added: in a batch such a column
+        could fall into a neighbouring graph, where the uncached call would keep it.  A few batched device calls."""
+        indices = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
+        graphs = list(graphs)
+        if len(indices) != len(graphs):
+            raise ValueError("indices and graphs must have the same length")
+        cols = []
+        for i, (ei, n) in zip(indices, graphs):
+            if not torch.is_tensor(ei):
+                raise RuntimeError("edge_index must be a tensor")
+            _graphs.check_int64(ei, torch.empty(0, dtype=torch.int64))
+            if ei.dim() != 2 or ei.size(0) != 2:
+                raise RuntimeError("edge_index must have shape [2, E]")
+            if int(n) < 0:
+                raise ValueError("num_nodes must be >= 0")
+            a = ei.detach().cpu().numpy()
+            if a.size and (a.min() < 0 or a.max() >= int(n)):
+                raise ValueError(f"graph {i} has a column with an endpoint outside [0, {int(n)})")
+            cols.append(a)
+        self._handle()
+        run, ne, nv = [], 0, 0
+        for i, a, (_, n) in zip(indices, cols, graphs):
+            if run and (ne + a.shape[1] > CHUNK_COLUMNS or nv + int(n) > CHUNK_COLUMNS):
+                self._batched(run)
+                run, ne, nv = [], 0, 0
+            run.append((i, a, int(n)))
+            ne, nv = ne + a.shape[1], nv + int(n)
+        self._batched(run)
+
+    def _batched(self, run):
+        if not run:
+            return
+        G = len(run)
+        ptr = np.zeros(G + 1, np.int64)
+        np.cumsum([g[2] for g in run], out=ptr[1:])
+        ei = np.ascontiguousarray(np.concatenate([a + ptr[g] for g, (_, a, _) in enumerate(run)], axis=1))
+        slots, status = np.zeros(G, np.int64), np.zeros(G, np.int32)
+        _graphs._select_device(self.dev)
+        _check(lib.ugs_rwr_cache_add(self._handle(), ei.ctypes.data, ei.shape[1], ei.shape[1], ptr.ctypes.data, G, slots.ctypes.data,
+                                     status.ctypes.data))
+        for (i, a, n), s, st in zip(run, slots.tolist(), status.tolist()):
+            self._slot[i] = (s, n, a.shape[1])
+            if st:
+                self.failed.add(i)
+            else:
+                self.failed.discard(i)
+
+    def _out_device(self, device, ptr, edge_index):
+        """Where the outputs go: `device`, else the device of a GPU ptr (or edge_index), else None (pinned host tensors)."""
+        if device is None:
+            for t in (ptr, edge_index):
+                if t is not None and t.device.type == "cuda":
+                    device = t.device
+                    break
+            else:
+                return None
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device= must be a GPU device (or None for pinned host tensors)")
+        if dev.index is not None and self.dev.index is not None and dev.index != self.dev.index:
+            raise ValueError(f"the cache lives on {self.dev}, not on {dev}")
+        return self.dev
+
+    def _job(self, graph_idx, ptr, edge_index, m_per_graph, mode, seed, seeds, p_restart, streams, check, device):
+        rows = _row_streams(streams)
+        if edge_index is None:
+            if check:
+                raise ValueError("edge_index=None needs check=False: the check compares the batch's columns")
+        else:
+            _graphs.check_int64(edge_index, ptr)
+            _graphs._edge_index_view(edge_index)
+        if ptr.dtype != torch.int64:
+            raise RuntimeError("ptr must be int64")
+        dev = self._out_device(device, ptr, edge_index)
+        gi = graph_idx.cpu().flatten().tolist() if torch.is_tensor(graph_idx) else [int(i) for i in graph_idx]
+        G = ptr.numel() - 1
+        if len(gi) != G:
+            raise ValueError(f"graph_idx names {len(gi)} graphs, ptr holds {G}")
+        slots = np.zeros(max(G, 1), np.int64)
+        have, total = ptr.cpu().tolist(), 0
+        for g, i in enumerate(gi):
+            if i not in self._slot:
+                raise KeyError(i)
+            slots[g], n, ncol = self._slot[i]
+            if have[g + 1] - have[g] != n:
+                raise RuntimeError(f"rwr_sampler cache: graph {g} of the batch has {have[g + 1] - have[g]} vertices, "
+                                   f"the graph added in its place has {n}")
+            total += ncol
+        if edge_index is not None and edge_index.size(1) != total:
+            raise RuntimeError(f"rwr_sampler cache: the batch has {edge_index.size(1)} columns, the added graphs have {total}")
+        if seeds is None:
+            for g, i in enumerate(gi):
+                if i in self.failed:
+                    raise RuntimeError(f"rwr_sampler: graph {g} has {have[g + 1] - have[g]} vertices; "
+                                       "10 n k must fit the reference's int iteration limit")
+        cache = self._handle()
+        md, p = 0 if mode == "sample" else 1, C.c_double(float(p_restart))
+        sd = _graphs.seed_array(seeds, G) if seeds is not None else None
+        status = np.zeros(max(G, 1), np.int32)
+        given = edge_index is not None and bool(check)                   # without the check the columns stay where they are
+
+        def begin(batch, out):
+            ei = batch[:3] if given else (None, 0, 0)
+            return lib.ugs_rwr_cache_sample_begin(cache, slots.ctypes.data, *ei, *batch[3:6], md, C.c_uint64(int(seed) & _graphs.M64),
+                                                  sd.ctypes.data if sd is not None else None, p, 1 if rows else 0, 1 if check else 0,
+                                                  status.ctypes.data if sd is not None else None, *out)
+
+        batch_ei = edge_index if given else torch.empty((2, 0), dtype=torch.int64)
+        five = _graphs.run_job(begin, lib.ugs_rwr_sample_batch_finish, batch_ei.cpu() if given else batch_ei, ptr, m_per_graph, self.k,
+                               dev, host_job_device=self.dev)
+        return five, status[:G]
+
+    def sample_batch(self, graph_idx, ptr, edge_index, m_per_graph, mode="sample", seed=42, p_restart=0.2, *, streams="graph",
+                     check=True, device=None):
+        """rwr_sampler.sample_batch(edge_index, ptr, m_per_graph, k, mode, seed, p_restart, streams=streams) for a batch whose graph g
+        is the graph added under graph_idx[g].  Pinned host tensors by default; with device= or a GPU ptr, tensors on the cache's
+        device, on torch's current stream.  Before any device work: KeyError for an index never added, ValueError if graph_idx and
+        ptr disagree in length, if the device is not the cache's, if streams is neither value and for edge_index=None without
+        check=False, RuntimeError for a wrong vertex count or column count and for a failed graph.  With check, after the device
+        work: RuntimeError "graph g of the batch differs from the graph added in its place", g the smallest such."""
+        return self._job(graph_idx, ptr, edge_index, m_per_graph, mode, seed, None, p_restart, streams, check, device)[0]
+
+    def sample_graphs(self, graph_idx, ptr, edge_index, m_per_graph, seeds, mode="sample", p_restart=0.2, *, streams="graph", check=True,
+                      device=None):
+        """rwr_sampler.sample_graphs for such a batch: the five tensors and failed [G] (on their device); a graph that failed when
+        it was added gives m rows of -1 and failed[g] = True."""
+        five, status = self._job(graph_idx, ptr, edge_index, m_per_graph, mode, 0, seeds, p_restart, streams, check, device)
+        return five + (torch.from_numpy(status != 0).to(five[0].device),)
+
+    def info(self):
+        """graphs (indices held), vertices (entries of the row-start array: vertices plus one per add), half_edges, bytes of the
+        device storage and generations (allocations so far); what replaced graphs held stays counted until close"""
+        v = [C.c_int64() for _ in range(5)]
+        _check(lib.ugs_rwr_cache_info(self._handle(), *[C.byref(x) for x in v]))
+        return {"graphs": len(self._slot), "vertices": v[1].value, "half_edges": v[2].value, "bytes": v[3].value, "generations": v[4].value}

@@ -72,12 +72,12 @@ def check_int64(edge_index, ptr):
         raise RuntimeError("ptr must be int64")
 
 
-def run_job(begin, finish, edge_index, ptr, m_per_graph, k, device=None):
+def run_job(begin, finish, edge_index, ptr, m_per_graph, k, device=None, host_job_device=None):
     """The two-phase call of a side sampler: begin (walks and edge counts), five tensors sized by its total, finish (fill and copy).
     `begin(batch, out)` calls the sampler's ugs_*_begin with batch = (ei, row_stride, num_cols, ptr, G, m, k), its own arguments
     behind them, and out = (job, total) last; it returns the status.  A batch on a GPU (or `device`) gives device tensors and runs on
-    torch's current stream of that device; a host batch gives pinned host tensors.  Returns (nodes, edge_index, edge_ptr,
-    sample_ptr, edge_src)."""
+    torch's current stream of that device; a host batch gives pinned host tensors, and its job runs on torch's current device, or on
+    `host_job_device` (a call tied to storage on one device).  Returns (nodes, edge_index, edge_ptr, sample_ptr, edge_src)."""
     check_int64(edge_index, ptr)
     in_dev = torch.device(device) if device is not None else edge_index.device
     keep, p, stride, e = _edge_index_view(edge_index.cpu())
@@ -85,7 +85,10 @@ def run_job(begin, finish, edge_index, ptr, m_per_graph, k, device=None):
     G = pt.numel() - 1
     m, k = int(m_per_graph), int(k)
     dev = in_dev if in_dev.type == "cuda" else None
-    _select_device(dev, jobs=True)
+    if dev is None and host_job_device is not None:
+        _select_device(host_job_device)
+    else:
+        _select_device(dev, jobs=True)
     job, total = vp(), C.c_int64()
     check(begin((p, stride, e, pt.data_ptr(), G, m, k), (C.byref(job), C.byref(total))))
     try:

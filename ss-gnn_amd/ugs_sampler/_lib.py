@@ -75,6 +75,12 @@ def _load():
                                         C.POINTER(vp), i64p],
         "ugs_rwr_sample_rows_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_double, vp,
                                       C.POINTER(vp), i64p],
+        "ugs_rwr_cache_create": [C.c_int, C.c_int64, C.c_int64, C.POINTER(vp)],
+        "ugs_rwr_cache_destroy": [vp],
+        "ugs_rwr_cache_add": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp],
+        "ugs_rwr_cache_info": [vp, i64p, i64p, i64p, i64p, i64p],
+        "ugs_rwr_cache_sample_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, vp, C.c_double,
+                                       C.c_int, C.c_int, vp, C.POINTER(vp), i64p],
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
