@@ -214,6 +214,16 @@ int ugs_plan_twin(ugs_plan *plan, int k, ugs_plan **twin_out);
 /* num_graphs, total vertices, total CSR entries, bytes resident in HBM, walk-kernel tier chosen for k */
 int ugs_plan_info(const ugs_plan *plan, int k, int64_t *num_graphs, int64_t *num_vertices, int64_t *nnz,
                   int64_t *device_bytes, int *tier);
+/* The first-pick table of a plan, copied back from HBM (testing aid).  Plans of one graph keep, beside their padded rows and built
+ * with them at the first walk of a one-walk-per-wave tier, 64 bytes per vertex: byte r of vertex v is the position, in the candidate
+ * list D1(v) that the scan of v's row leaves when v is the root (the distinct neighbours that pass the suffix filter, in
+ * first-occurrence order), of the candidate at position r of the iteration order of the reference's unordered_set built from D1(v)
+ * (reference src/sampler.cpp:55-80); defined for r < |D1(v)| <= 64, and for the vertices a root can be (every vertex of a graph
+ * whose roots are drawn by weight; the viable list of a relaxed one).  The launch-uniform walk takes a walk's first pick from it.
+ * num_vertices: the plan's vertices, or 0 when the plan has no table (not built yet, several graphs, UGS_NO_FIRST_PICK_TABLE=1).
+ * c1[v] = |D1(v)| (-1: more than the 448-candidate tier holds; 0 for a vertex no root can be), ord1 = the table; both hold
+ * `capacity` vertices, either may be NULL.  Synchronises with the device. */
+int ugs_plan_first_pick_table(ugs_plan *plan, int64_t capacity, int64_t *num_vertices, int32_t *c1, uint8_t *ord1);
 /* Walk phase for rows [row_begin, row_begin+row_count) of the G*m rows: writes d_nodes[row_count,k] and
  * d_edge_ptr[row_count+1] (exclusive scan of the per-row edge-entry counts, starting at 0).
  * If total_edges_host is not NULL the stream is synchronised and the total is returned there. */

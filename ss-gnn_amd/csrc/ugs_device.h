@@ -22,6 +22,11 @@
 //                                    of two (row pointer, then row), and no line is fetched for a row-pointer pair.  Only the lines
 //                                    a typical visited row fills are fetched with the header (prow_first entries); the block's
 //                                    remaining lines follow for the rows that reach into them.
+//   ord1    uint8[n << 6]            FIRST-PICK TABLE of a plan of ONE graph, behind the padded rows in their allocation and built with
+//                                    them (ugs_build_ord1): byte r of vertex v = position, in the candidate list the scan of v's row
+//                                    leaves when v is the root, of the candidate at iteration position r of the reference's
+//                                    unordered_set built from that list -- defined for r < c <= 64.  Handed to the walk as
+//                                    UgsWalkArgs::ord1, not as a member of UgsPlanDev (see there).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +107,11 @@ struct UgsWalkArgs {
     // gi draw from seeds[gi] instead of seed64 / *seed_ptr.  Last member, and read only by the walk kernels' SEEDS instantiations
     // (ugs_launch_walk picks them when it is set): the kernels of every other call are the code they were without it.
     const uint64_t *seeds;
+    // first-pick table of a single-graph plan (NULL = off): 64 bytes per plan vertex, built once with the padded rows
+    // (ugs_build_ord1).  Byte r of vertex v = position in D of the candidate at iteration position r of the candidate list that the
+    // scan of v's row leaves when v is the root (defined for r < c <= 64).  Read only by the launch-uniform walk (do_walk's UNI
+    // instantiation); behind every other member, so that the argument offsets of every other kernel stay what they were.
+    const uint8_t *ord1;
 };
 #define UGS_COUNT_STAGED 0x80000000u
 #define UGS_STAGE_ENTRIES 32    /* undirected hits a walk can hold in LDS */
@@ -158,6 +168,10 @@ static constexpr int UGS_TIER_HASH_LIMIT[UGS_LDS_TIERS] = {96, 448, 896, 1536, 1
 
 hipError_t ugs_launch_walk(const UgsWalkArgs &a, int tier, int device_cus, int share_percent, hipStream_t s, UgsLaunchInfo *info);
 hipError_t ugs_launch_build_prow(const UgsPlanDev &plan, int64_t num_vertices, int2 *prow, int shift, int device_cus, hipStream_t s);
+// first-pick table (UgsWalkArgs::ord1) of a plan of ONE graph whose padded rows are built: one wave per root.  c1 (or NULL): the
+// candidates the root's row leaves, per plan vertex (-1: the row outgrows the 448-candidate tier); both arrays zeroed by the caller.
+#define UGS_ORD1_BYTES 64
+hipError_t ugs_launch_build_ord1(const UgsPlanDev &plan, int64_t num_vertices, uint8_t *ord1, int32_t *c1, int device_cus, hipStream_t s);
 #define UGS_COLLATE_MAX_WORLD 64
 hipError_t ugs_launch_collate_unpack(const void *d_msgs, int world, int64_t msg_bytes, const int64_t *row_off, int k, int node_b, int eidx_b,
                                      int esrc_b, int64_t rows_cap, int64_t edge_cap, const int64_t *section_off4, int64_t *d_nodes,

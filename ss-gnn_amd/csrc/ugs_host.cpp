@@ -49,6 +49,7 @@ struct Lap {   // UGS_DEBUG=1: wall-clock of the host stages of a large preproce
 };
 
 bool debug_on() { static const bool on = [] { const char *e = std::getenv("UGS_DEBUG"); return e && std::string(e) == "1"; }(); return on; }
+bool env_is_one(const char *name) { const char *e = std::getenv(name); return e && e[0] == '1'; }     // read at every call: tests and A/Bs toggle these
 
 // ---------------------------------------------------------------------------------------------------------------
 // per-graph preprocessing result (host copy; the device plan is assembled from these)
@@ -525,6 +526,8 @@ struct ugs_plan {
     PoolBuf prow;                         // padded rows (ugs_device.h), built on the device by the first walk in a one-walk-per-wave tier
     std::atomic<size_t> prow_bytes{0};    // their size, readable by the plan cache without this plan's mutex
     bool prow_pooled = false, prow_failed = false;
+    size_t prow_asked = 0;                // bytes asked for (rows + table): what ugs_plan_info reports, as blob_bytes is the bytes asked for
+    const uint8_t *ord1 = nullptr;        // first-pick table (UgsWalkArgs::ord1): the tail of the padded rows' allocation, 64 bytes per vertex
     int walk_share = 100;                 // ugs_plan_set_walk_share
     bool stg_valid = false;
     const void *stg_nodes = nullptr;
@@ -727,7 +730,7 @@ void destroy_plan(ugs_plan *p) {
     pool_put(p->counts); pool_put(p->ovf1); pool_put(p->ovf2); pool_put(p->ovfcnt); pool_put(p->scantmp);
     pool_put(p->stage); pool_put(p->ulist); pool_put(p->work); pool_put(p->tiles);
     pin_slot_put(p->pin_slot);
-    if (p->prow.p) { if (p->prow_pooled) pool_put(p->prow); else (void)hipFree(p->prow.p); p->prow = PoolBuf(); }
+    if (p->prow.p) { if (p->prow_pooled) pool_put(p->prow); else (void)hipFree(p->prow.p); p->prow = PoolBuf(); p->ord1 = nullptr; }
     if (p->gws.p) { (void)hipFree(p->gws.p); p->gws = PoolBuf(); }
     ugs_plan *owner = p->twin_of;
     delete p;
@@ -1001,8 +1004,14 @@ int ensure_prow(ugs_plan *plan, hipStream_t s) {
     int shift = 3;
     while (shift < 6 && (double)((1 << shift) - 1) < sb + 3.0 * std::sqrt(sb) + 1.0) ++shift;
     if (const char *e = std::getenv("UGS_PROW_SHIFT")) { const int f = std::atoi(e); if (f >= 3 && f <= 6) shift = f; }
-    const size_t bytes = ((size_t)plan->nverts << shift) * sizeof(int2);
-    if (bytes >= ((size_t)1 << 32)) { plan->prow_failed = true; return UGS_OK; }       // the walk kernels address a block by a 32-bit byte offset
+    const size_t row_bytes = ((size_t)plan->nverts << shift) * sizeof(int2);
+    if (row_bytes >= ((size_t)1 << 32)) { plan->prow_failed = true; return UGS_OK; }   // the walk kernels address a block by a 32-bit byte offset
+    // First-pick table (ugs_device.h, UgsWalkArgs::ord1) behind the rows, in the same allocation: it lives and dies with them, is
+    // shared with them (ugs_plan_twin, captured steps) and counts with them in ugs_plan_info and against the plan cache's bytes.
+    // Only the launch-uniform walk reads it, and that walk serves plans of one graph.  UGS_NO_FIRST_PICK_TABLE=1: neither built nor used.
+    const bool want_ord1 = plan->G == 1 && !plan->g_level.empty() && plan->g_level[0] >= 0 && plan->nverts < ((int64_t)1 << 26) &&
+                           !env_is_one("UGS_NO_FIRST_PICK_TABLE");
+    const size_t bytes = row_bytes + (want_ord1 ? (size_t)plan->nverts * UGS_ORD1_BYTES : 0);
     if (bytes <= ((size_t)64 << 20)) {
         const std::string keep = t_err;
         if (pool_get(bytes, plan->device, plan->prow) != UGS_OK) { t_err = keep; plan->prow_failed = true; return UGS_OK; }
@@ -1013,7 +1022,6 @@ int ensure_prow(ugs_plan *plan, hipStream_t s) {
         plan->prow.p = p; plan->prow.bytes = bytes; plan->prow.dev = plan->device;
     }
     HIP_TRY(ugs_launch_build_prow(plan->dev, plan->nverts, static_cast<int2 *>(plan->prow.p), shift, plan->cus, s));
-    HIP_TRY(hipStreamSynchronize(s));          // once per plan: later calls may come on other streams
     plan->dev.prow = static_cast<const int2 *>(plan->prow.p);
     plan->dev.prow_shift = shift;
     // entries fetched together with the header: whole 128-byte lines (16 entries) covering the typical visited row; a row that
@@ -1021,7 +1029,15 @@ int ensure_prow(ugs_plan *plan, hipStream_t s) {
     int first = (int)std::ceil((sb + 0.5 * std::sqrt(sb) + 1.0) / 16.0) * 16;
     if (const char *e = std::getenv("UGS_PROW_FIRST")) { const int f = std::atoi(e); if (f >= 1) first = f; }
     plan->dev.prow_first = std::max(1, std::min(first, 1 << shift));
+    if (want_ord1) {                            // behind the rows' build on the same stream: its kernel reads them
+        uint8_t *o = static_cast<uint8_t *>(plan->prow.p) + row_bytes;
+        HIP_TRY(hipMemsetAsync(o, 0, (size_t)plan->nverts * UGS_ORD1_BYTES, s));
+        HIP_TRY(ugs_launch_build_ord1(plan->dev, plan->nverts, o, nullptr, plan->cus, s));
+        plan->ord1 = o;
+    }
+    HIP_TRY(hipStreamSynchronize(s));          // once per plan: later calls may come on other streams
     plan->prow_bytes.store(plan->prow.bytes);
+    plan->prow_asked = bytes;
     if (plan->cached) plan_cache_trim();        // the cache admitted the plan without these bytes: apply its byte cap again
     return UGS_OK;
 }
@@ -1863,8 +1879,34 @@ int ugs_plan_info(const ugs_plan *plan, int k, int64_t *num_graphs, int64_t *num
     if (num_graphs) *num_graphs = plan->G;
     if (num_vertices) *num_vertices = plan->nverts;
     if (nnz) *nnz = plan->nnz;
-    if (device_bytes) *device_bytes = (int64_t)(plan->blob_bytes + plan->prow.bytes);
+    if (device_bytes) *device_bytes = (int64_t)(plan->blob_bytes + plan->prow_asked);
     if (tier) *tier = choose_tier(const_cast<ugs_plan *>(plan), k).first;
+    return UGS_OK;
+}
+
+int ugs_plan_first_pick_table(ugs_plan *plan, int64_t capacity, int64_t *num_vertices, int32_t *c1, uint8_t *ord1) {
+    if (!plan || !num_vertices) return fail(UGS_E_BAD_ARG, "null argument");
+    HIP_TRY(hipSetDevice(plan->device));
+    std::lock_guard<std::mutex> lk(plan->mu);
+    *num_vertices = plan->ord1 ? plan->nverts : 0;
+    if (!plan->ord1 || (!c1 && !ord1)) return UGS_OK;
+    if (capacity < plan->nverts) return fail(UGS_E_BAD_ARG, "capacity below the plan's vertices");
+    const size_t nv = (size_t)plan->nverts;
+    DeviceCtx dc;
+    if (int rc = device_ctx(dc)) return rc;
+    if (ord1) HIP_TRY(hipMemcpy(ord1, plan->ord1, nv * UGS_ORD1_BYTES, hipMemcpyDeviceToHost));       // the table the walks read
+    if (c1) {                                   // the candidate counts are not kept: the build kernel once more, into scratch
+        void *tmp = nullptr;
+        HIP_TRY(hipMalloc(&tmp, nv * (UGS_ORD1_BYTES + sizeof(int32_t))));
+        uint8_t *o = static_cast<uint8_t *>(tmp);
+        int32_t *c = reinterpret_cast<int32_t *>(o + nv * UGS_ORD1_BYTES);
+        hipError_t e = hipMemsetAsync(tmp, 0, nv * (UGS_ORD1_BYTES + sizeof(int32_t)), dc.stream);
+        if (e == hipSuccess) e = ugs_launch_build_ord1(plan->dev, plan->nverts, o, c, plan->cus, dc.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(dc.stream);
+        if (e == hipSuccess) e = hipMemcpy(c1, c, nv * sizeof(int32_t), hipMemcpyDeviceToHost);
+        (void)hipFree(tmp);
+        if (e != hipSuccess) return fail_hip(e, "first-pick table read-back");
+    }
     return UGS_OK;
 }
 
@@ -1956,6 +1998,7 @@ static int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_grap
     a.seed64 = (uint64_t)(int64_t)seed;
     a.seed_ptr = d_seed_ptr;
     a.seeds = d_seeds;
+    a.ord1 = env_is_one("UGS_NO_FIRST_PICK_TABLE") ? nullptr : plan->ord1;     // (read per call: tests and A/Bs toggle it)
     a.row_begin = row_begin; a.row_count = row_count;
     a.nodes = d_nodes;
     a.counts = static_cast<uint32_t *>(plan->counts.p);
@@ -2173,6 +2216,7 @@ int ugs_plan_graph_create(ugs_plan *plan, int m_per_graph, int k, int mode, int6
     {
         std::lock_guard<std::mutex> lk(plan->mu);
         sh->dev = plan->dev;         // device arrays shared, not owned (blob stays null)
+        sh->ord1 = plan->ord1;
     }
     sh->prow_failed = true;          // never a private copy of the padded rows: the owner's, or the row-pointer path
     sh->g_n = plan->g_n; sh->g_maxdeg = plan->g_maxdeg; sh->g_sbdeg = plan->g_sbdeg; sh->g_level = plan->g_level;
@@ -2241,6 +2285,7 @@ int ugs_plan_twin(ugs_plan *plan, int k, ugs_plan **twin_out) {
             if (e != hipSuccess) { delete sh; return fail(UGS_E_HIP, hipGetErrorString(e)); }
         }
         sh->dev = plan->dev;
+        sh->ord1 = plan->ord1;
         sh->walk_share = plan->walk_share;
     }
     sh->g_n = plan->g_n; sh->g_maxdeg = plan->g_maxdeg; sh->g_sbdeg = plan->g_sbdeg; sh->g_level = plan->g_level;

@@ -1660,6 +1660,7 @@ __device__ __forceinline__ void flush_parked(const Grp<64> &g_, const FlushOut &
 struct UniLaunch {
     UgsPlanDev plan;
     UgsGraphDesc gd;
+    const uint8_t *ord1;     // first-pick table (UgsWalkArgs::ord1), or null
     __device__ __forceinline__ void init(const UgsWalkArgs &a) {
         plan = a.plan;
         static_assert(sizeof(UgsGraphDesc) == 48 && offsetof(UgsGraphDesc, n) == 32 && offsetof(UgsGraphDesc, n_viable) == 40, "read word by word below");
@@ -1669,6 +1670,7 @@ struct UniLaunch {
         gd.n = (int32_t)(uint32_t)nl; gd.level = (int32_t)(uint32_t)(nl >> 32); gd.n_viable = (int32_t)(uint32_t)q[5]; gd.pad = 0;
         // (the padded rows of a plan span less than 4 GB, prow_entry: the 32-bit entry index of vbase + v splits without a carry)
         plan.prow += (uint32_t)gd.vbase << plan.prow_shift;
+        ord1 = a.ord1 ? a.ord1 + ((uint32_t)gd.vbase << 6) : nullptr;
         plan.roots += gd.vbase;
         plan.viable += gd.viable_base;
         gd.vbase = 0;
@@ -1763,6 +1765,14 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     uint32_t v = root_v;                                                      // the vertex whose row is scanned next (local index size-1)
     if constexpr (PAD) e0 = load_prow(P, gd.vbase + v, g.lane);
     else { r0 = g.uni((uint32_t)P.rowptr[gd.rbase + v]); r1 = g.uni((uint32_t)P.rowptr[gd.rbase + v + 1]); }
+    // First-pick table (UNI): the candidates the root's row leaves, D1, and the order the selection gives them depend on the plan
+    // and the root alone, so the first pick is a function of (root, rsel) -- lane r asks for byte r of the root's 64, the position
+    // in D1 of the candidate at iteration position r, together with the root's row: no round trip of its own.  Used below when
+    // the row leaves at most 64 candidates; the byte of any other root is never looked at.
+    [[maybe_unused]] uint32_t ord_byte = 0u;
+    if constexpr (UNI) {
+        if (ul->ord1) ord_byte = *reinterpret_cast<const uint8_t *>(reinterpret_cast<const char *>(ul->ord1) + ((v << 6) + (uint32_t)g.lane));
+    }
     SP::sync();
     if (g.lane == 0) { ws.HK[hash_slot(root_v, ws.hmask)] = root_v | kInS; SV[0] = root_v; }
     SP::sync();
@@ -1779,6 +1789,8 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
     // c = 0 and nvalid = 0 and rebuilds D and the order stages from there.  A walk that stops early (c == 0) or is handed on (an
     // ADD scan's overflow) leaves the loop before this and is what it was.  The other tiers keep the loop as it was.
     const bool root_only = STG && k == 1;                                     // the root's row is the last row: no growth step
+    [[maybe_unused]] uint32_t fp_lim = 0u;                                    // UNI: candidates up to which the next pick comes from the first-pick table
+    if constexpr (UNI) fp_lim = ul->ord1 ? (uint32_t)UGS_ORD1_BYTES : 0u;
     bool last_row = root_only;                                                // set by the last pick, nowhere else
     for (int step = 0; !root_only; ++step) {
         Grp<GS> g = g_;                                                       // see select_lds: keeps lane-derived constants out of long-lived registers
@@ -1834,7 +1846,16 @@ __device__ __forceinline__ bool do_walk(const Work<SP> &ws, const Grp<GS> &g_, c
         if constexpr (DRAWS) xsel = draw64(cd, dcur++); else xsel = rng.next();
         const uint32_t rsel = g.uni(mod64_by<sizeof(typename SP::TW) == 4, sizeof(typename SP::TW) == 4 && GS == 64>(xsel, c));
         STAMP_END(4);
-        const Pick pick = select_any<GS, MAXPER>(ws, g, c, rsel, nvalid);
+        Pick pick;
+        // (UNI) the pick behind the root's row comes from the table when the row left at most 64 candidates.  One scalar compare per
+        // growth step: `fp_lim` is 64 for that pick of a launch with a table and 0 otherwise (c >= 1 here); an opaque scalar, or the
+        // three conditions it stands for are combined as 64-bit lane masks, eleven scalar instructions per step.
+        [[maybe_unused]] uint32_t lim = 0u;
+        if constexpr (UNI) { lim = fp_lim; fp_lim = 0u; asm volatile("" : "+s"(lim)); }
+        if (UNI && __builtin_expect(c <= lim, 0)) {                           // no stage is computed, `nvalid` stays 0
+            pick.q = g.bcast(ord_byte, (int)rsel);
+            pick.w = g.uni(ws.D[pick.q]);
+        } else pick = select_any<GS, MAXPER>(ws, g, c, rsel, nvalid);
         const uint32_t w = pick.w;
         if constexpr (PAD) {
             e0 = load_prow(P, gd.vbase + w, g.lane);                  // the row itself: issued now, consumed after the candidate list has been updated
@@ -2182,6 +2203,67 @@ __global__ __launch_bounds__(256) void ugs_build_prow(UgsPlanDev P, int64_t num_
     if (l == 0) e = make_int2((int)deg, (int)start);
     else if (l - 1 < deg) e = P.adj[start + l - 1];
     prow[idx] = e;
+}
+
+// First-pick table (UgsWalkArgs::ord1) of a plan of one graph, once per plan: one wave per root -- every order position of a graph
+// whose roots are drawn by weight, every entry of the viable list of a relaxed one -- with the walk's own workspace and routines.
+// The root is entered as the walk enters it, its padded row scanned by the walk's scan_prow with the root's own rank as the suffix
+// bound, and the walk's select_lds asked for every iteration position r < c in turn (`nvalid` carried: the stages are
+// materialised once); the position it names goes to byte r.  Vertices that are no root of the plan keep the zeros of the caller.
+__global__ __launch_bounds__(64) void ugs_build_ord1(UgsPlanDev P, uint8_t *ord1, int32_t *c1) {
+    constexpr int CAP = 448;
+    using Cfg = TierCfg<CAP>;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[Cfg::WORDS];
+    Grp<64> g;
+    g.init();
+    g.chain = chain_lane_const<Cfg::NSTAGE>(g.lane);
+    Work<LdsSpace> ws;
+    ws.D = lds;
+    ws.ORD = reinterpret_cast<uint16_t *>(ws.D + CAP);
+    ws.AUX = nullptr;
+    ws.TBL = ws.D + CAP + Cfg::ORDW;
+    ws.HK = ws.TBL + Cfg::BCAP_A;
+    uint32_t *SV = ws.HK + Cfg::HS;
+    ws.cap = CAP;
+    ws.hmask = Cfg::HS - 1;
+    ws.hlimit = Cfg::HLIMIT;
+#ifdef UGS_STAMPS
+    __shared__ unsigned long long stamps[32];      // the builder's phases are not reported
+    ws.ST = stamps;
+#endif
+    const UgsGraphDesc gd = P.graphs[0];
+    if (gd.level < 0) return;
+    const int64_t items = gd.level == 0 ? (int64_t)gd.n : (int64_t)gd.n_viable;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        uint32_t vi, v;
+        if (gd.level == 0) { vi = (uint32_t)it; v = (uint32_t)P.roots[gd.vbase + it].v_self; }
+        else { const int2 vr = P.viable[gd.viable_base + it]; vi = (uint32_t)vr.x; v = (uint32_t)vr.y; }
+        vi = g.uni(vi); v = g.uni(v);
+        const int64_t vrow = gd.vbase + v;
+        int2 e0 = load_prow(P, vrow, g.lane);
+        {
+            uint4 *H4 = reinterpret_cast<uint4 *>(ws.HK);
+            const uint32_t n4 = (ws.hmask + 1u) >> 2;
+            for (uint32_t s = g.lane; s < n4; s += 64) H4[s] = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
+        }
+        LdsSpace::sync();
+        if (g.lane == 0) { ws.HK[hash_slot(v, ws.hmask)] = v | kInS; SV[0] = v; }
+        LdsSpace::sync();
+        StageCtx sc;
+        sc.EL = reinterpret_cast<uint4 *>(SV + UGS_KMAX); sc.ne = 0u; sc.on = false; sc.onm = 0ull;      // nothing is staged
+        uint32_t size = 1, c = 0, hcount = 1, ecount = 0;
+        const bool ok = scan_prow<LdsSpace, true, true>(ws, g, P, v, vi, size, c, hcount, ecount, e0, vrow, sc);
+        if (c1 && g.lane == 0) c1[vrow] = ok ? (int32_t)c : -1;
+        if (!ok || c == 0u || c > (uint32_t)UGS_ORD1_BYTES) continue;
+        int nvalid = 0;
+        uint32_t mine = 0u;
+        for (uint32_t r = 0; r < c; ++r) {
+            const Pick pk = select_lds<64, (CAP + 63) / 64>(ws, g, c, r, nvalid);
+            mine = (uint32_t)g.lane == r ? pk.q : mine;
+        }
+        if ((uint32_t)g.lane < c) ord1[(vrow << 6) + g.lane] = (uint8_t)mine;
+        LdsSpace::sync();
+    }
 }
 
 // last tier: workspace in global memory, one wave per walk, any candidate-set size up to gcap
@@ -2699,6 +2781,15 @@ hipError_t ugs_launch_build_prow(const UgsPlanDev &plan, int64_t num_vertices, i
     const int64_t total = num_vertices << shift;
     if (total <= 0) return hipSuccess;
     hipLaunchKernelGGL(ugs_build_prow, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, plan, num_vertices, prow, shift);
+    return hipGetLastError();
+}
+
+hipError_t ugs_launch_build_ord1(const UgsPlanDev &plan, int64_t num_vertices, uint8_t *ord1, int32_t *c1, int cus, hipStream_t s) {
+    if (num_vertices <= 0 || plan.num_graphs != 1 || !plan.prow) return hipErrorInvalidValue;
+    if (cus <= 0) cus = 256;
+    const int64_t cap = (int64_t)cus * UGS_BLOCKS_M;                                         // the walk's residency: the same workspace per wave
+    const int64_t grid = num_vertices < cap ? num_vertices : cap;
+    hipLaunchKernelGGL(ugs_build_ord1, dim3((unsigned)grid), dim3(64), 0, s, plan, ord1, c1);
     return hipGetLastError();
 }
 

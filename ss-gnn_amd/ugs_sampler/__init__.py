@@ -473,6 +473,19 @@ class Plan:
         check(lib.ugs_plan_info(self._h, self.k, C.byref(g), C.byref(nv), C.byref(nnz), C.byref(nb), C.byref(tier)))
         return {"num_graphs": g.value, "num_vertices": nv.value, "nnz": nnz.value, "device_bytes": nb.value, "tier": tier.value}
 
+    def first_pick_table(self):
+        """The plan's first-pick table copied back from HBM (testing aid): {"c1": int32 [num_vertices], candidates the root's row
+        leaves (-1: more than the 448-candidate tier holds), "ord1": uint8 [num_vertices, 64]}, or None when the plan has no table
+        (no walk of a one-walk-per-wave tier yet, several graphs, UGS_NO_FIRST_PICK_TABLE=1)."""
+        import numpy as np
+        nv = C.c_int64()
+        check(lib.ugs_plan_first_pick_table(self._h, 0, C.byref(nv), None, None))
+        if nv.value == 0:
+            return None
+        c1, ord1 = np.zeros(nv.value, np.int32), np.zeros((nv.value, 64), np.uint8)
+        check(lib.ugs_plan_first_pick_table(self._h, nv.value, C.byref(nv), c1.ctypes.data, ord1.ctypes.data))
+        return {"c1": c1, "ord1": ord1}
+
     def last_launch(self):
         name = C.create_string_buffer(128)
         grid, block, lds, ovf = C.c_int(), C.c_int(), C.c_int(), C.c_int64()

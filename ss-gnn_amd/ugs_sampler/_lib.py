@@ -95,6 +95,7 @@ def _load():
         "ugs_plan_graph_csr": [vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), i64p] + [vp] * 5,
         "ugs_plan_twin": [vp, C.c_int, C.POINTER(vp)],
         "ugs_plan_info": [vp, C.c_int, i64p, i64p, i64p, i64p, C.POINTER(C.c_int)],
+        "ugs_plan_first_pick_table": [vp, C.c_int64, i64p, vp, vp],
         "ugs_plan_walk": [vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, i64p],
         "ugs_plan_fill": [vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, vp],
         "ugs_plan_step": [vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, vp],
