@@ -447,6 +447,60 @@ int ugs_uniform_population_sample_begin(ugs_uniform_population *pop, const int64
                                         ugs_job **job_out, int64_t *total_edges_out);
 int ugs_uniform_population_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                                          int64_t *edge_src, int dst_is_device);
+/* ---- WL class indices of a population: the vocabulary ids of the sampled subgraphs from the cache, no hashing per step.
+ *      A row of the uniform sampler is one member of the fixed population S_g, and its WL digest (ugs_wl_hash below) is a function of
+ *      that member and of the graph alone.  A population made by create_wl hashes every member once, when its graph is added, and
+ *      keeps an int32 class index beside every key; a sample call then gathers.
+ *      The law.  For a batch that passes the call's checks, population_sample_wl_begin / population_distinct_wl_begin give the
+ *      tensors, graph_status and valid_out of population_sample_begin / population_distinct_begin, and d_wl_ids_out [G m] int64 equals
+ *      ugs_wl_hash (populations whose adds gave no labels) or ugs_wl_hash_labeled (d_labels = L), with the population's iterations,
+ *      followed by ugs_wl_lookup with the given table, over the nodes, edge_index and edge_ptr that the SAME call gives in mode 0
+ *      ("sample"), where L[ptr[g] + v] is the label given for vertex v of the graph added under slots[g].  Bit for bit, for every
+ *      batch composition, and whatever the call's own mode.  So a row of -1 (a failed slot with seeds, a graph with fewer than k
+ *      vertices, the rows behind valid_out[g] of a distinct call) gets unknown_id, and so does a member with a start label outside
+ *      [0, 2^32) (status 3).  Labels are fixed when the graph is added; nothing of the batch but its columns is read per step.
+ *      Loops.  A digest depends on loop columns (item 2 of the law of ugs_wl_hash; in the labelled form a loop only makes the vertex
+ *      its own neighbour), the adjacency fingerprint of a slot does not.  A WL population therefore keeps, per slot, a fingerprint of
+ *      the set of vertices that have a loop column, and a _wl_begin with check != 0 compares it as well: a mismatch is UGS_E_BAD_ARG
+ *      naming the first graph whose adjacency or loop set differs.  With check == 0 the ids are those of the added graph.  Calls
+ *      without wl behave on a WL population exactly as on a plain one.
+ *      create_wl(k, block_keys, iterations): as create; 0 <= iterations <= 8 and 1 <= k <= 32 (ugs_wl_hash's range), otherwise
+ *      UGS_E_UNSUPPORTED.  No device work.
+ *      add_wl: as add (which, on a WL population, is add_wl without labels), then the WL stage under the same exclusive lock: the
+ *      stored members are written out as mode-0 rows with their edges by the enumeration's row and fill kernels, in chunks of at
+ *      most 2^16 rows and 2^23 edge entries (under 256 MiB of scratch), each chunk is hashed by ugs_wl_hash / ugs_wl_hash_labeled,
+ *      unchanged -- a stored digest is the digest of the sampler's own row, loops and duplicate columns included --, and the digests
+ *      are numbered: one class per distinct digest, -1 for a member without one.  Class numbers are internal.  d_labels: DEVICE
+ *      int64 [num_labels], the start label of every vertex of the call (num_labels = ptr[num_graphs], ptr[0] = 0), or NULL for the
+ *      degree form; every add of one population uses the same form (UGS_E_BAD_ARG otherwise, before any device work).
+ *      wl_stats: distinct digests held, rows hashed so far (add time only: a sample call hashes nothing).  wl_digests: *count_out =
+ *      the number of distinct digests; if capacity >= it, digest_out [count, 2] holds them in ugs_wl_hash's format, ascending as
+ *      128-bit numbers.  info's bytes include the class indices and the class table.
+ *      _wl_begin: d_vocab_keys / d_vocab_ids / vocab_size / unknown_id as ugs_wl_lookup takes them (device arrays that outlive the
+ *      call); vocab_token names the table: the population keeps, per token, the device array id_of_class (ugs_wl_lookup over its
+ *      class table) and makes it again when the class table has grown, so equal tokens must mean equal tables.  d_wl_ids_out is a
+ *      DEVICE array of G m int64, written on the job's stream before begin returns.  One more launch behind the draws
+ *      (uni_pop_wl_ids: the row's draw index as the row kernels read it, cls[draw], id_of_class[cls]) and, with check, one for the
+ *      loops; the outcome of that check travels in the status words read with the edge total.  UGS_E_BAD_ARG for a population made
+ *      without iterations.  Finished by population_sample_finish. */
+int ugs_uniform_population_create_wl(int k, int64_t block_keys, int iterations, ugs_uniform_population **pop_out);
+int ugs_uniform_population_add_wl(ugs_uniform_population *pop, const int64_t *edge_index, int64_t row_stride, int64_t num_cols,
+                                  const int64_t *ptr, int64_t num_graphs, int64_t max_rows, const int64_t *d_labels, int64_t num_labels,
+                                  int64_t *slots_out, int32_t *graph_status);
+int ugs_uniform_population_wl_stats(ugs_uniform_population *pop, int64_t *classes_out, int64_t *rows_hashed_out);
+int ugs_uniform_population_wl_digests(ugs_uniform_population *pop, int64_t capacity, uint64_t *digest_out, int64_t *count_out);
+int ugs_uniform_population_sample_wl_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index,
+                                           int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph,
+                                           int mode, uint64_t seed, const uint64_t *seeds, int check, int32_t *graph_status,
+                                           const uint64_t *d_vocab_keys, const int64_t *d_vocab_ids, int64_t vocab_size,
+                                           int64_t unknown_id, uint64_t vocab_token, int64_t *d_wl_ids_out, ugs_job **job_out,
+                                           int64_t *total_edges_out);
+int ugs_uniform_population_distinct_wl_begin(ugs_uniform_population *pop, const int64_t *slots, const int64_t *edge_index,
+                                             int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                                             int m_per_graph, int mode, const uint64_t *seeds, int check, int32_t *graph_status,
+                                             int64_t *valid_out, const uint64_t *d_vocab_keys, const int64_t *d_vocab_ids,
+                                             int64_t vocab_size, int64_t unknown_id, uint64_t vocab_token, int64_t *d_wl_ids_out,
+                                             ugs_job **job_out, int64_t *total_edges_out);
 /* Vertices per graph up to which ugs_uniform_* enumerates.  Default 64: every call behaves as it did before the wide form existed.
  * A caller whose graphs are larger (PROTEINS, IMDB-BINARY) raises it, to 1024 at most, once at start-up; nothing raises it
  * implicitly.  Results for graphs of at most 64 vertices never depend on it, and a call without wide graphs allocates and launches

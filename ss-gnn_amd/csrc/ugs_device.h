@@ -325,6 +325,21 @@ struct UgsPopCall {
 };
 hipError_t ugs_uniform_pop_begin(UgsPopCall &p, hipStream_t s);
 hipError_t ugs_uniform_pop_fill(const UgsPopCall &p, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+// WL class indices (ugs_uniform_population_*_wl_*): every stored key has an int32 class index beside it (the class of its WL digest,
+// -1: no digest), a slot also a fingerprint of its loop vertices -- the bitmap of the vertices with a loop column, reduced like an
+// adjacency bitmap.  ugs_uniform_pop_loops, behind the column buckets of either kind of call: out[g] = graph g's loop fingerprint
+// (add), or status[3] = G - (first enumerable graph whose fingerprint is not want[g]), 0: none (check).  ugs_uniform_pop_wl, behind
+// ugs_uniform_pop_begin and before the status words are read: that check (p.check), then ids_out[row] = id_of_class[cls[g][draw]],
+// unknown_id for a row of -1 or a class of -1.
+struct UgsPopWl {
+    const int32_t *const *cls;               // [G] the class indices of graph g's keys (nullptr: no keys)
+    const uint64_t *lfp;                     // [G] loop fingerprint stored at add time
+    const int64_t *id_of_class;              // [classes] vocabulary id of every class (ugs_wl_lookup over the class table)
+    int64_t unknown_id;
+    int64_t *ids_out;                        // [rows]
+};
+hipError_t ugs_uniform_pop_loops(const UgsUniCall &c, const uint64_t *want, uint64_t *out, hipStream_t s);
+hipError_t ugs_uniform_pop_wl(const UgsPopCall &p, const UgsPopWl &q, hipStream_t s);
 
 // ---- rwr_sampler (ugs_rwr.hip): random walk with restart, one SplitMix64 stream per graph, counter-based speculation ----
 #define UGS_RWR_KMAX 64

@@ -994,6 +994,49 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_wpop_fill(UgsPopCall p, int64_t
     }
 }
 
+// ---- WL class indices of a population (ugs_uniform_population_*_wl_begin): a stored key has one int32 class index beside it, the
+//      class of its WL digest, hashed once at add time; a step turns a row's draw into a vocabulary id with two loads. ----
+// ids_out[row] = id_of_class[cls of the row's drawn key]; unknown_id for a row of -1 (pop_key says so) or a key without a digest
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_wl_ids(UgsPopCall p, UgsPopWl q) {
+    const int64_t row = (int64_t)blockIdx.x * UNI_BLOCK + threadIdx.x;
+    if (row >= p.c.rows) return;
+    const int64_t g = row / p.c.m;
+    int64_t id = q.unknown_id;
+    if (p.c.gsize[g] > 0) {                                         // the draw index, as pop_key reads it
+        const int64_t d = p.c.seeds ? row : (int64_t)p.c.nepos[g] * p.c.m + (row - g * p.c.m);
+        const int32_t draw = p.c.draws[d];
+        if (draw >= 0) {
+            const int32_t cls = q.cls[g][draw];
+            if (cls >= 0) id = q.id_of_class[cls];
+        }
+    }
+    q.ids_out[row] = id;
+}
+
+// The loop vertices of graph g (a loop changes a WL digest, never S_g): one workgroup per graph marks them in a bitmap of
+// UGS_UNI_WIDE_MAX_N bits in LDS from the graph's column bucket and reduces it like an adjacency bitmap (fp_mix over the non-zero
+// words).  out: the fingerprint is stored (add); want: it is compared with the stored one, status[3] = G - (first graph that differs).
+__global__ __launch_bounds__(UNI_BLOCK) void uni_pop_loops(UgsUniCall c, const uint64_t *want, uint64_t *out) {
+    constexpr int WORDS = UGS_UNI_WIDE_MAX_N / 64;
+    __shared__ unsigned long long s_bits[WORDS];
+    const int64_t g = blockIdx.x;
+    const UgsUniGraph gd = c.graphs[g];
+    if (threadIdx.x < WORDS) s_bits[threadIdx.x] = 0ull;
+    __syncthreads();
+    if (gd.enumerable)                                              // (n <= UGS_UNI_WIDE_MAX_N; uni_colgraph kept both endpoints inside [0, n))
+        for (int64_t q = c.cstart[g] + threadIdx.x; q < c.cstart[g + 1]; q += UNI_BLOCK) {
+            const int64_t col = c.cval2[q];
+            const int64_t u = c.src[col] - gd.lo;
+            if (u == c.dst[col] - gd.lo && u >= 0 && u < UGS_UNI_WIDE_MAX_N) atomicOr(&s_bits[u >> 6], 1ull << (u & 63));
+        }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint64_t fp = 0;
+    for (int i = 0; i < WORDS; ++i) if (s_bits[i]) fp += fp_mix(s_bits[i], (uint64_t)i);
+    if (out) out[g] = fp;
+    if (want && gd.enumerable && fp != want[g]) atomicMax((unsigned long long *)&c.status[3], (unsigned long long)(c.G - g));
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // uni_draw_distinct over every graph of the call; the sort's width, and with it the LDS, follows m, not the limit
@@ -1163,5 +1206,18 @@ hipError_t ugs_uniform_pop_fill(const UgsPopCall &p, int64_t *edge_index, int64_
     if (p.c.rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(uni_pop_fill, dim3(blocks(p.c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p, edge_index, edge_src, ld);
     if (p.any_wide) hipLaunchKernelGGL(uni_wpop_fill, dim3(blocks(p.c.rows, POP_GROUPS)), dim3(UNI_BLOCK), 0, s, p, edge_index, edge_src, ld);
+    return hipGetLastError();
+}
+
+// ---- WL class indices of a population ----
+hipError_t ugs_uniform_pop_loops(const UgsUniCall &c, const uint64_t *want, uint64_t *out, hipStream_t s) {
+    if (c.G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(uni_pop_loops, dim3((unsigned)c.G), dim3(UNI_BLOCK), 0, s, c, want, out);
+    return hipGetLastError();
+}
+
+hipError_t ugs_uniform_pop_wl(const UgsPopCall &p, const UgsPopWl &q, hipStream_t s) {
+    if (p.check && p.c.G > 0) hipLaunchKernelGGL(uni_pop_loops, dim3((unsigned)p.c.G), dim3(UNI_BLOCK), 0, s, p.c, q.lfp, (uint64_t *)nullptr);
+    if (p.c.rows > 0) hipLaunchKernelGGL(uni_pop_wl_ids, dim3(blocks(p.c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, p, q);
     return hipGetLastError();
 }

@@ -71,6 +71,14 @@ def _load():
                                        C.POINTER(vp), i64p],
         "ugs_uniform_population_distinct_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, vp,
                                                   C.POINTER(vp), i64p],
+        "ugs_uniform_population_create_wl": [C.c_int, C.c_int64, C.c_int, C.POINTER(vp)],
+        "ugs_uniform_population_add_wl": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp],
+        "ugs_uniform_population_wl_stats": [vp, i64p, i64p],
+        "ugs_uniform_population_wl_digests": [vp, C.c_int64, vp, i64p],
+        "ugs_uniform_population_sample_wl_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp,
+                                                   vp, vp, C.c_int64, C.c_int64, C.c_uint64, vp, C.POINTER(vp), i64p],
+        "ugs_uniform_population_distinct_wl_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, vp,
+                                                     vp, vp, C.c_int64, C.c_int64, C.c_uint64, vp, C.POINTER(vp), i64p],
         "ugs_rwr_sample_graphs_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp,
                                         C.POINTER(vp), i64p],
         "ugs_rwr_sample_rows_begin": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_double, vp,
