@@ -1,4 +1,4 @@
-// ugs_device.h -- structures shared by the host library (ugs_host.cpp) and the gfx950 kernels (ugs_kernels.hip).
+// ugs_device.h -- structures shared by the host library (ugs_host.cpp, ugs_jobs.cpp, ugs_side_*.cpp) and the gfx950 kernels (ugs_kernels.hip).
 //
 // HBM layout of a *plan* (one PyG batch, or one graph of the handle API), all arrays resident in device memory:
 //
@@ -415,6 +415,7 @@ void ugs_devpre_trim(UgsDevPre *d);
 size_t ugs_devpre_resident_bytes(const UgsDevPre *d);
 hipError_t ugs_devpre_assemble(UgsDevPre *d, const int64_t *h_colmap, int64_t cols, int2 *adj, int2 *adjf, hipStream_t s);
 
-// ---- what the other translation units take from ugs_host.cpp (internal, not part of the C ABI) ----
+// ---- what the .hip translation units and ugs_apx.cpp take from ugs_host.cpp (internal, not part of the C ABI; the host files
+//      of the job path and the side samplers share more with it, through ugs_host_internal.h) ----
 int ugs_internal_fail(int code, const char *msg);            // sets the calling thread's message, the one ugs_last_error() returns; returns code
 int ugs_internal_ctx(int *device, hipStream_t *stream);      // the calling thread's device and stream (ugs_set_device / ugs_set_stream)

@@ -55,7 +55,7 @@ def _check_cpu_i64(t, name):
 
 def _carve(opts, shapes):
     """int64 tensors of the given shapes as views of ONE allocation, in order: one allocator call instead of len(shapes), and
-    the library moves adjacent outputs with one copy (ugs_host.cpp finish_common).  Each view is contiguous."""
+    the library moves adjacent outputs with one copy (ugs_jobs.cpp finish_common).  Each view is contiguous."""
     sizes = [int(torch.Size(s).numel()) for s in shapes]
     buf = torch.empty((sum(sizes),), **opts)
     out, off = [], 0

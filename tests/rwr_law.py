@@ -34,12 +34,12 @@ SPEC_CAP = 64          # ugs_rwr.hip `constexpr uint64_t SPEC_CAP`: rwr_walk's `
 RWR_LDS_INTS = 8192    # ugs_rwr.hip `constexpr int RWR_LDS_INTS`: rwr_resolve's `n + 1 + D + (n + 3) / 4 <= RWR_LDS_INTS`
 DOOM_LANE = 32         # ugs_rwr.hip rwr_doomed_len: `for (int j = 0; j < 32; ...)`, positions classified per lane
 DOOM_ROUND = DOOM_LANE * RWR_BLOCK   # ugs_rwr.hip rwr_doomed_len: `pos += 32ull * RWR_BLOCK`, positions per round
-SPEC_MAX = 4           # ugs_rwr.hip `RWR_WMAX = 4 * RWR_BLOCK` and ugs_host.cpp rwr_begin `c.spec = min(4, ...)`
+SPEC_MAX = 4           # ugs_rwr.hip `RWR_WMAX = 4 * RWR_BLOCK` and ugs_side_rwr.cpp rwr_begin `c.spec = min(4, ...)`
 KM_WIDTHS = (8, 16, 32, 64)   # ugs_rwr.hip ugs_rwr_begin / ugs_rwr_fill: launch_walks<8|16|32|64> by `c.k <= KM`
 
 
 def spec_window(m):
-    """(spec, W) of a call with m rows per graph: ugs_host.cpp rwr_begin `c.spec = min(4, max(1, (m * 16 + 255) / 256))`,
+    """(spec, W) of a call with m rows per graph: ugs_side_rwr.cpp rwr_begin `c.spec = min(4, max(1, (m * 16 + 255) / 256))`,
     ugs_rwr.hip rwr_resolve `W = c.spec * RWR_BLOCK`."""
     spec = min(SPEC_MAX, max(1, (16 * m + 255) // 256))
     return spec, RWR_BLOCK * spec

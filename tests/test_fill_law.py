@@ -70,6 +70,8 @@ def test_census_constants_are_the_kernels():
         dev = f.read()
     with open(os.path.join(CSRC, "ugs_host.cpp")) as f:
         host = f.read()
+    with open(os.path.join(CSRC, "ugs_jobs.cpp")) as f:                     # begin_common and the packed step
+        jobs = f.read()
     assert hip.count("for (uint32_t cb = 0; cb < T; cb += %d * GS) {" % L.SUB_CHUNKS) == 2
     assert hip.count("for (int u = 0; u < %d; ++u) {" % L.SUB_CHUNKS) >= 4 and hip.count("if (cb + u * GS >= T) break;") == 2
     assert "if (k <= %d) {" % L.LOOKUP_REGS in hip and "j += (ps[t] <= e) ? 1 : 0;" in hip and "j += (PS[t] <= e) ? 1 : 0;" in hip
@@ -83,10 +85,10 @@ def test_census_constants_are_the_kernels():
     assert "write = 3 * (int64_t)tot <= a.packed_cap;" in hip and "if (l >= 0 && pos < a.ld) {" in hip
     assert "#define UGS_STAGE_ITEMS %d " % L.STAGE_ITEMS in dev
     assert "!dyn && row_count <= %d && !capturing(s)" % L.FUSED_MAX_ROWS in host
-    assert "j->rows <= %d && tc0.first == UGS_TIER_S" % L.FUSED_MAX_ROWS in host
-    assert "const int64_t cap3_want = 3 * j->rows * 2 * (int64_t)k * (int64_t)(k - 1);" in host
-    assert "cap3_want * (int64_t)sizeof(int64_t) <= ((int64_t)192 << 20)" in host and L.PACKED_STAGING_BYTES == 192 << 20
-    assert "j->packed_ok = 3 * j->total <= cap3;" in host
+    assert "j->rows <= %d && tc0.first == UGS_TIER_S" % L.FUSED_MAX_ROWS in jobs
+    assert "const int64_t cap3_want = 3 * j->rows * 2 * (int64_t)k * (int64_t)(k - 1);" in jobs
+    assert "cap3_want * (int64_t)sizeof(int64_t) <= ((int64_t)192 << 20)" in jobs and L.PACKED_STAGING_BYTES == 192 << 20
+    assert "j->packed_ok = 3 * j->total <= cap3;" in jobs
 
 
 @pytest.mark.parametrize("name", P.CASE_NAMES)

@@ -115,7 +115,7 @@ def test_census_constants_are_the_kernels():
     # the census restates these; if the kernel's move, this fails and the inputs have to be chosen again
     with open(os.path.join(CSRC, "ugs_rwr.hip")) as f:
         hip = f.read()
-    with open(os.path.join(CSRC, "ugs_host.cpp")) as f:
+    with open(os.path.join(CSRC, "ugs_side_rwr.cpp")) as f:
         host = f.read()
     const = lambda name: int(re.search(r"constexpr \w+ %s = (\d+);" % name, hip).group(1))
     assert const("RWR_BLOCK") == R.RWR_BLOCK and const("SPEC_CAP") == R.SPEC_CAP and const("RWR_LDS_INTS") == R.RWR_LDS_INTS
