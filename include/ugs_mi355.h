@@ -650,6 +650,64 @@ int ugs_rwr_cache_sample_begin(ugs_rwr_cache *cache, const int64_t *slots, const
                                const uint64_t *seeds, double p_restart, int row_streams, int check, int32_t *graph_status,
                                ugs_job **job_out, int64_t *total_edges_out);
 
+/* ---- ugs_sampler.GraphCache (ugs_graph_cache_*): every graph of a dataset preprocessed once, at one k, and kept on one device as
+ *      one "plan of all added graphs" -- row pointer, (neighbour, rank) and (neighbour, column) entries, root records, viable lists --
+ *      so that a sample call over any batch of added graphs runs only the walks, the scan and the fill.
+ *      create(k, reserve_vertices, reserve_columns): no device work; k as ugs_sample_batch_begin checks it (k > 32: UGS_E_UNSUPPORTED
+ *      "k > 32 is not supported by the HIP sampler").  The storage is allocated at the first add, on the calling thread's device, with
+ *      room for at least the reservation, and grows by reallocation and a device-to-device copy to at least twice its size.  Each
+ *      allocation is a generation: a job holds the one it walks on until it is finished or cancelled, so an add never invalidates a
+ *      job in flight, and destroy may be called with jobs in flight.
+ *      add(edge_index, ptr, G): a batch of graphs, vertices [ptr[g], ptr[g+1]).  Every column must lie inside one graph and the
+ *      columns must come graph by graph, in the order of the graphs (UGS_E_BAD_ARG otherwise): each graph's columns are stored as
+ *      given, in their order, as pairs of local ids.  Each graph is preprocessed on its own content at the cache's k by the stages
+ *      an LRU miss of ugs_sample_batch_begin runs -- without reading or changing the LRU, the handle registry, the plan cache or the
+ *      batch index: ugs_cache_stats is the same before and after.  A graph with n <= 0 or n < k keeps a slot and its columns and
+ *      nothing else (m rows of -1, as in a batch).  slots_out[g] is the graph's slot (never reused; adding a graph again gives a
+ *      new one, the old bytes stay until destroy).  Limits, UGS_E_UNSUPPORTED with the cache left as it was: the CSR entries of all
+ *      adds < 2^31 - 1, the columns of all adds < 2^31 - 1.  Synchronous.  Adds are exclusive among themselves; any number of threads
+ *      may sample meanwhile.
+ *      info: slots, root records (vertices of the non-degenerate graphs), CSR entries, bytes of the current generation, generations
+ *      so far (any may be NULL).
+ *      sample_begin.  THE CONTRACT.  Let B be the batch whose columns are, for g = 0 ... G-1 in order, the columns stored for
+ *      slots[g], each shifted by ptr[g] -- what collating the added graphs in that order produces.  The call, finished with
+ *      ugs_sample_batch_finish, gives bit for bit what, after ugs_cache_clear, ugs_sample_batch_begin (seeds == NULL) or
+ *      ugs_sample_graphs_begin (seeds != NULL: num_graphs C ints) gives on (B, ptr) with the cache's k, mode and seed, in all five
+ *      tensors.  The walk, scan and fill kernels are the uncached call's own, code and argument layout: they reach a graph only
+ *      through its descriptor {node_lo, rbase, vbase, viable_base, n, level, n_viable}, and a row's generator is keyed by the seed
+ *      and the row's index inside its graph, so a descriptor whose bases point into the store serves them.  The store keeps a
+ *      graph's columns numbered from 0; one small kernel behind the fill adds coff[g], the number of columns of the graphs ahead of
+ *      g in the batch, to the edge_src entries of g's rows.
+ *      THE DEVIATION.  The call never reads or changes the LRU, so it does not reproduce the reference's reuse of ANOTHER graph's
+ *      preprocessing: a graph the LRU holds under a different k (the key ignores k), and two different graphs of more than 1000
+ *      columns that share a strided key (include/cache.hpp:100-107).  Every graph gets the preprocessing of its own content at the
+ *      cache's k, whatever the LRU holds -- which is what the uncached call gives on an empty LRU, except for the second case inside
+ *      one batch.
+ *      Before any device work: every slot exists, ptr[g+1] - ptr[g] is the slot's vertex count (UGS_E_BAD_ARG naming the graph and
+ *      both counts), and, when edge_index is given or check != 0, num_cols equals the slots' column counts together
+ *      (UGS_E_BAD_ARG "the batch has E columns, the added graphs have S").
+ *      check != 0: the batch's edge_index goes up with the descriptors and one kernel compares every column e, of the graph g with
+ *      coff[g] <= e < coff[g+1], with the stored column, exactly; the smallest g with a column that differs reaches the host ahead
+ *      of the edge total, without a wait of its own, and the call fails with UGS_E_BAD_ARG "graph g of the batch differs from the
+ *      graph added in its place".  It can never accept a batch that is not B; it also refuses a batch that merely permutes a
+ *      graph's columns (edge_src would differ).  check == 0: edge_index is not read and may be NULL (num_cols is then ignored); for
+ *      a batch that is not B the result is that of B (never a fault: nothing of the batch but ptr is read).
+ *      Host work is O(G).  Padded rows and the first-pick table are not built for the store: a call whose tier has 64 lanes per walk
+ *      reads rows through the row pointer.  Same job protocol, stream rules and ugs_job_cancel as the other jobs.
+ *      last_launch: the names of the first-tier walk kernel and of the fill kernel of the calling thread's last sample call on this
+ *      cache ("" if there was none, or no fill ran) -- a read-only aid like ugs_plan_last_launch / ugs_plan_last_fill. */
+typedef struct ugs_graph_cache ugs_graph_cache;
+int ugs_graph_cache_create(int k, int64_t reserve_vertices, int64_t reserve_columns, ugs_graph_cache **cache_out);
+int ugs_graph_cache_destroy(ugs_graph_cache *cache);
+int ugs_graph_cache_add(ugs_graph_cache *cache, const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                        int64_t num_graphs, int64_t *slots_out);
+int ugs_graph_cache_info(ugs_graph_cache *cache, int64_t *graphs_out, int64_t *vertices_out, int64_t *entries_out, int64_t *bytes_out,
+                         int64_t *generations_out);
+int ugs_graph_cache_sample_begin(ugs_graph_cache *cache, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                                 int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int mode, int seed,
+                                 const int32_t *seeds, int check, ugs_job **job_out, int64_t *total_edges_out);
+int ugs_graph_cache_last_launch(ugs_graph_cache *cache, char *walk_buf, int walk_buf_len, char *fill_buf, int fill_buf_len);
+
 /* ---- uniform_sampler.sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode) / PopulationCache.sample_distinct: sampling
  *      WITHOUT replacement from the finite population S_g -- m distinct connected k-subsets per graph, every ordered selection
  *      equally likely, and the whole population, in its order, when it has at most m sets (the "full bag": no sampling variance

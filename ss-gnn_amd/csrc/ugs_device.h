@@ -395,6 +395,31 @@ struct UgsRwrCheck {
 hipError_t ugs_rwr_store_check(const UgsRwrCheck &k, hipStream_t s);
 hipError_t ugs_rwr_fill(const UgsRwrCall &c, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
 
+// ---- ugs_sampler.GraphCache (ugs_store.hip): the store is one "plan of all added graphs".  An add lays its
+//      chunk out as a plan of its own (columns local to each graph) and ugs_store_append moves that plan behind everything the store
+//      holds: rowptr + adj_base, adj, adjf, root records, viable entries, and the chunk's columns narrowed to int2 pairs of local ids.
+struct UgsStoreAppend {
+    const int64_t *rowptr; const int2 *adj, *adjf; const UgsRootRec *roots; const int2 *viable;      // the chunk's plan
+    const int64_t *col_u, *col_v;                                                                    // the chunk's columns, local ids
+    int64_t n_rowptr, nnz, n_roots, n_viable, n_cols;                                                // entries of each of them
+    int64_t *s_rowptr; int2 *s_adj, *s_adjf; UgsRootRec *s_roots; int2 *s_viable, *s_cols;           // the storage generation being written
+    int64_t row_base, adj_base, root_base, via_base, col_base;                                       // where this add goes
+};
+hipError_t ugs_store_append(const UgsStoreAppend &a, hipStream_t s);
+// The check of a cached call: column e of the batch, of the graph g with coff[g] <= e < coff[g+1], against stored column
+// col0[g] + e - coff[g] after taking lo[g] = ptr[g] off both endpoints; first_bad = the smallest g with a column that differs.
+struct UgsStoreCheck {
+    int64_t E, G;
+    const int64_t *src, *dst;                            // the batch's columns
+    const int64_t *lo, *coff, *col0;                     // [G] ptr[g]; [G + 1] prefix sums of the slots' column counts; [G] first stored column
+    const int2 *cols;                                    // the store's columns
+    int32_t *first_bad;
+};
+hipError_t ugs_store_check(const UgsStoreCheck &c, hipStream_t s);
+// edge_src of a cached call, behind its fill: the store's adjf holds columns local to their graph, so the entries
+// [edge_ptr[r], edge_ptr[r+1]) of row r get coff[r / m] added -- the column's place in the batch.
+hipError_t ugs_store_rebase_src(const int64_t *edge_ptr, int64_t *edge_src, const int64_t *coff, int64_t rows, int32_t m, hipStream_t s);
+
 // ---- epsilon_uniform_sampler (ugs_eps.hip): one launcher for the walk (fill = 0: nodes and per-row counts) and the fill ----
 struct UgsEpsLaunch {
     const UgsGraphDesc *graphs; const int64_t *rowptr; const int32_t *nbr; const int32_t *ecs; int64_t num_graphs;

@@ -643,7 +643,10 @@ void ev_clear(ugs_plan *p) {
 
 void destroy_plan(ugs_plan *p) {
     if (!p) return;
-    if (p->device >= 0 && hipSetDevice(p->device) == hipSuccess) (void)hipDeviceSynchronize();   // kernels may still read the plan
+    if (p->device >= 0 && hipSetDevice(p->device) == hipSuccess) {                               // kernels may still read the plan
+        if (!p->view) (void)hipDeviceSynchronize();
+        else if (p->last_valid) (void)hipEventSynchronize(p->last_ev);
+    }
     ev_clear(p);
     if (p->last_ev) (void)hipEventDestroy(p->last_ev);
     if (p->blob_buf.p) pool_put(p->blob_buf); else if (p->blob) (void)hipFree(p->blob);
@@ -658,6 +661,14 @@ void destroy_plan(ugs_plan *p) {
 }
 }  // namespace
 namespace ugs_host __attribute__((visibility("hidden"))) { void plan_unref(ugs_plan *p) { if (p && p->refs.fetch_sub(1) == 1) destroy_plan(p); } }
+namespace ugs_host __attribute__((visibility("hidden"))) {
+int graph_outside_lru(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int k, std::shared_ptr<Graph> &out) { return make_graph(src, dst, E, n, k, out); }
+int plan_of_graphs(const std::vector<std::shared_ptr<Graph>> &graphs, const DeviceCtx &dc, ugs_plan *plan) {
+    std::vector<PlanPiece> pieces(graphs.size());
+    for (size_t g = 0; g < graphs.size(); ++g) pieces[g].g = graphs[g];          // lo = 0, colmap = nullptr: adjf keeps the graph's own column numbers
+    return assemble_plan(pieces, dc, plan);
+}
+}  // namespace ugs_host
 namespace {
 
 // plan cache of batches (small LRU; a hit skips assembly + upload)

@@ -1,6 +1,6 @@
 // ugs_host_internal.h -- what the host translation units of libugs_mi355.so share: ugs_host.cpp (preprocessing, registry, LRU, plans,
-// batch index, device batch pass), ugs_jobs.cpp (the two-phase job path and the streamed call) and one ugs_side_<name>.cpp per side
-// sampler.  Not part of the C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
+// batch index, device batch pass), ugs_jobs.cpp (the two-phase job path and the streamed call), one ugs_side_<name>.cpp per side
+// sampler and ugs_graph_cache.cpp (ugs_sampler.GraphCache).  Not part of the C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
 //
 // Declarations only: every global and every thread_local is defined in exactly one .cpp -- ugs_host.cpp, except the job-path section
 // at the end, which ugs_jobs.cpp owns.  Everything sits in namespace ugs_host with hidden visibility, so nothing here is exported
@@ -162,12 +162,19 @@ struct ugs_plan {
     bool timing = false;
     struct EvPair { hipEvent_t a, b; int kind; };     // kind 0 = first-tier walk kernel, 1 = overflow tiers + scan, 2 = fill kernel
     std::vector<EvPair> events;
+    // a view plan (ugs_graph_cache.cpp): one cached call's descriptors over the store's arrays, which `keep` holds.  It is never shared
+    // and dies with its job, so destroying it waits for its own last kernel (last_ev) instead of the whole device.
+    bool view = false;
 };
 
 namespace ugs_host __attribute__((visibility("hidden"))) {
 
 // ---- what the job path needs of a plan (all defined in ugs_host.cpp) ----
 TierChoice choose_tier(ugs_plan *p, int k);
+// ugs_graph_cache.cpp: a graph preprocessed at k that no registry, LRU or batch index learns of, and a chunk of such graphs
+// (nullptr: degenerate, n <= 0 or n < k) laid out as one plan -- node_lo 0 and columns local to each graph -- that no cache holds
+int graph_outside_lru(const int64_t *src, const int64_t *dst, int64_t E, int64_t n, int k, std::shared_ptr<Graph> &out);
+int plan_of_graphs(const std::vector<std::shared_ptr<Graph>> &graphs, const DeviceCtx &dc, ugs_plan *plan);
 int plan_enter(ugs_plan *plan, hipStream_t s);
 int plan_leave(ugs_plan *plan, hipStream_t s);
 hipError_t ev_begin(ugs_plan *p, int kind, hipStream_t s);
@@ -216,6 +223,9 @@ struct ugs_job {
     // that finish runs from them.  The hook holds the sampler's call struct by value; empty: the job fills through its plan.
     PoolBuf blob;
     JobFill fill;
+    // a job on a view plan (ugs_graph_cache.cpp): runs behind the plan's own fill at finish, on the job's stream -- edge_src from
+    // columns local to each graph to batch columns (a packed step had it at begin)
+    std::function<hipError_t(int64_t *edge_src, hipStream_t s)> after_fill;
     // a job whose begin reports its own row count (ugs_uniform_enumerate_begin): its sample_ptr [G + 1], rows = sample_ptr[G];
     // empty: rows = G m and sample_ptr = g m
     std::vector<int64_t> sample_ptr;

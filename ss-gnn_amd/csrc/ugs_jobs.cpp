@@ -158,6 +158,7 @@ int finish_common(ugs_job *j, int64_t *nodes, int64_t *edge_index, int64_t *edge
             if (j->fill) HIP_TRY(j->fill(d_ei, d_es, tot, s));
             else if (int r = ugs_plan_fill(j->plan, j->m, j->k, j->mode, j->extra, 0, rows, s, static_cast<const int64_t *>(j->nodes.p),
                                            j->d_eptr, d_ei, tot, d_es)) return r;
+            if (j->after_fill) HIP_TRY(j->after_fill(d_es, s));
         }
         const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         // adjacent outputs (the Python shim carves its tensors out of one allocation) travel in one copy each -- or all in one

@@ -11,6 +11,8 @@ Additions that the reference does not have (all optional, keyword-only or separa
   * sample_graphs(): sample_batch with one seed per graph -- the trainer's presample loop (one one-graph call per dataset graph)
     as one call (law: include/ugs_mi355.h at ugs_sample_graphs_begin);
   * clear_cache() / cache_stats(): the process-global preprocessing LRU (reference: UGS_CACHE_SIZE, default 1000);
+  * GraphCache: every dataset graph preprocessed once at one k and kept on the device -- a step over any batch of added graphs runs
+    only the walks, the scan and the fill, and equals sample_batch / sample_graphs on an empty LRU (ugs_sampler/graph_cache.py);
   * Plan: a batch preprocessed once and kept resident in HBM, sampled repeatedly / over row sub-ranges
     (multi-GPU sharding, see ugs_sampler.distributed).
 """
@@ -21,10 +23,11 @@ import torch
 
 from ._graphs import _edge_index_view, _out_opts, _select_device
 from ._lib import UGS_E_CAPACITY, check, lib, vp
+from .graph_cache import GraphCache
 
 __version__ = (lib.ugs_version() or b"").decode()
 __all__ = ["sample", "create_preproc", "destroy_preproc", "has_graphlets", "get_preproc_info", "sample_batch", "sample_graphs",
-           "clear_cache", "cache_stats", "preproc_dump", "Plan", "device_count"]
+           "clear_cache", "cache_stats", "preproc_dump", "Plan", "device_count", "GraphCache"]
 
 _EDGE_MODES = {"local": 0, "flat": 1, "global": 2}
 _BATCH_MODES = {"sample": 0, "graph": 1, "global": 2}
