@@ -708,6 +708,65 @@ int ugs_graph_cache_sample_begin(ugs_graph_cache *cache, const int64_t *slots, c
                                  const int32_t *seeds, int check, ugs_job **job_out, int64_t *total_edges_out);
 int ugs_graph_cache_last_launch(ugs_graph_cache *cache, char *walk_buf, int walk_buf_len, char *fill_buf, int fill_buf_len);
 
+/* ---- epsilon_uniform_sampler.GraphCache (ugs_eps_cache_*): the adjacency lists of every graph of a dataset -- what
+ *      ugs_eps_sample_batch_begin builds on the host for every batch -- built once, by a kernel, and kept on one device, so that a
+ *      sample call over any batch of added graphs runs only the walks, the scan and the fill.  The lists depend on neither k nor
+ *      epsilon: one cache serves every value of both, and they are arguments of the call.
+ *      create(reserve_vertices, reserve_columns): no device work.  The storage is allocated at the first add, on the calling
+ *      thread's device, with room for at least the reservation (vertices: the graphs' vertices plus one entry per graph), and
+ *      grows by reallocation and a device-to-device copy to at least twice its size.  Each allocation is a generation: a job holds
+ *      the one it walked on until it is finished or cancelled, so an add never invalidates a job in flight, and destroy may be
+ *      called with jobs in flight.
+ *      add(edge_index, ptr, G): a batch of graphs, vertices [ptr[g], ptr[g+1]).  Every column must lie inside one graph and the
+ *      columns must come graph by graph, in the order of the graphs (UGS_E_BAD_ARG otherwise): each graph's columns are stored as
+ *      given, in their order, as pairs of local ids.  The columns go up and one kernel writes, behind everything the store holds,
+ *      per graph n + 1 row offsets and per column two entries (neighbour, 2 * column inside the graph + side): THE ROW ORDER -- inside a
+ *      vertex's row the half-edges stand in (column, side) order, the source side (side 0) before the destination side, and a loop
+ *      column puts both its half-edges into the same row, source side first -- is that of the lists the uncached call builds.
+ *      slots_out[g] is the graph's slot (never reused; adding a graph again gives a new one, the old bytes stay until destroy).
+ *      Limits, UGS_E_UNSUPPORTED with the cache left as it was: the half-edges of all adds < 2^31, vertices plus graphs of all adds
+ *      < 2^31, 2^30 columns per add.  Synchronous.  Adds are exclusive among themselves; any number of threads may sample meanwhile.
+ *      info: slots, row-offset entries (vertices plus one per graph), half-edges held, bytes of the current generation, generations
+ *      so far (any may be NULL).
+ *      graph_csr: one slot's rows copied back from HBM (read-only, diagnostic: the counterpart of ugs_plan_graph_csr).  rowptr:
+ *      num_nodes + 1 values relative to the graph's first entry; per entry the neighbour (local id) and 2 * (column inside the
+ *      graph) + side.  rowptr holds node_capacity + 1 values, the entry arrays entry_capacity (UGS_E_CAPACITY if too small, with
+ *      both counts reported); any pointer may be NULL.  Synchronises with the device.
+ *      sample_begin.  THE CONTRACT.  Let B be the batch whose columns are, for g = 0 ... G-1 in order, the columns stored for
+ *      slots[g], each shifted by ptr[g] -- what collating the added graphs in that order produces.  The call, finished with
+ *      ugs_eps_sample_batch_finish, gives bit for bit what ugs_eps_sample_batch_begin (seeds == NULL: `seed` keys every row) or
+ *      ugs_eps_sample_graphs_begin (seeds != NULL: num_graphs values; graph_status, if given, is written all zero) gives on
+ *      (B, ptr) with the same m_per_graph, k, mode and epsilon, in all five tensors.  The walk kernel is the uncached call's own:
+ *      it reaches a graph only through its descriptor {node_lo, rbase, n}, the row offsets and the two entry arrays, and a row's
+ *      generator is keyed by the seed and the row's index, so a descriptor whose rbase points into the store serves it.  A stored
+ *      row names columns inside its graph; the fill adds coff[g], the number of columns of the graphs ahead of g in the batch,
+ *      when it writes edge_src (the uncached fill is the same kernel compiled without that addition).
+ *      Same checks and texts as ugs_eps_sample_batch_begin for epsilon, m_per_graph and k, before any device work; also before any:
+ *      every slot exists, ptr[g+1] - ptr[g] is the slot's vertex count (UGS_E_BAD_ARG naming the graph and both counts), and, when
+ *      edge_index is given or check != 0, num_cols equals the slots' column counts together (UGS_E_BAD_ARG "the batch has E columns,
+ *      the added graphs have S").
+ *      check != 0: the batch's edge_index goes up with the descriptors and one kernel compares every column e, of the graph g with
+ *      coff[g] <= e < coff[g+1], with the stored column, exactly; the smallest g with a column that differs comes back in the
+ *      read-back of the edge total, and the call fails with UGS_E_BAD_ARG "graph g of the batch differs from the graph added in its
+ *      place".  It can never accept a batch that is not B; it also refuses a batch that merely permutes a graph's columns (edge_src
+ *      would differ).  check == 0: edge_index is not read and may be NULL (num_cols is then ignored); for a batch that is not B the
+ *      result is that of B (never a fault: nothing of the batch but ptr is read).
+ *      Host work is O(G); the blob holds descriptors, coff, seeds, the check's columns and the walks' scratch -- no adjacency.  Same
+ *      job protocol, stream rules and ugs_job_cancel as the other jobs. */
+typedef struct ugs_eps_cache ugs_eps_cache;
+int ugs_eps_cache_create(int64_t reserve_vertices, int64_t reserve_columns, ugs_eps_cache **cache_out);
+int ugs_eps_cache_destroy(ugs_eps_cache *cache);
+int ugs_eps_cache_add(ugs_eps_cache *cache, const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr,
+                      int64_t num_graphs, int64_t *slots_out);
+int ugs_eps_cache_info(ugs_eps_cache *cache, int64_t *graphs_out, int64_t *vertices_out, int64_t *half_edges_out, int64_t *bytes_out,
+                       int64_t *generations_out);
+int ugs_eps_cache_graph_csr(ugs_eps_cache *cache, int64_t slot, int64_t node_capacity, int64_t entry_capacity, int64_t *num_nodes,
+                            int64_t *num_entries, int64_t *rowptr, int32_t *nbr, int32_t *ecs);
+int ugs_eps_cache_sample_begin(ugs_eps_cache *cache, const int64_t *slots, const int64_t *edge_index, int64_t row_stride,
+                               int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int m_per_graph, int k, int mode, uint64_t seed,
+                               const uint64_t *seeds, double epsilon, int check, int32_t *graph_status, ugs_job **job_out,
+                               int64_t *total_edges_out);
+
 /* ---- uniform_sampler.sample_distinct(edge_index, ptr, m_per_graph, k, seeds, mode) / PopulationCache.sample_distinct: sampling
  *      WITHOUT replacement from the finite population S_g -- m distinct connected k-subsets per graph, every ordered selection
  *      equally likely, and the whole population, in its order, when it has at most m sets (the "full bag": no sampling variance

@@ -426,8 +426,23 @@ struct UgsEpsLaunch {
     int32_t m, k, mode, max_attempts; uint64_t seed; double epsilon; int64_t rows;
     int64_t *nodes; uint32_t *counts; const int64_t *edge_ptr; int64_t *edge_index; int64_t *edge_src; int64_t ld;
     const uint64_t *seeds;        // device array [num_graphs]: one seed per graph (sample_graphs); null: `seed` for every row
+    const int64_t *col_base;      // device array [num_graphs], fill only: added to the column an ecs entry names (a cached call, whose
+                                  // rows hold columns local to their graph); null: ecs holds batch columns already
 };
 hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s);
+// epsilon_uniform_sampler.GraphCache (ugs_eps_cache.cpp): the adjacency of an add, built on the device behind
+// everything the store holds.  Graph g of the add has vertices vptr[g] ... vptr[g+1] and the columns cptr[g] ... cptr[g+1] of
+// cols[col_base ...] (pairs of local ids, already in the store); it gets the n + 1 rowptr entries from row_base + vptr[g] + g
+// (absolute offsets into nbr / ecs) and the 2 (cptr[g+1] - cptr[g]) entries of nbr / ecs from adj_base + 2 cptr[g].  Within a vertex's
+// row the half-edges stand in (column, side) order, source side first: the push_back order of eps_begin.
+struct UgsEpsBuild {
+    int64_t G;
+    const int64_t *vptr, *cptr;                          // [G + 1] each, device
+    int32_t *cursor;                                     // scratch [vptr[G]]: per-vertex write position, relative to the graph's entries
+    int64_t *rowptr; int32_t *nbr, *ecs; const int2 *cols;      // the storage generation being written
+    int64_t row_base, adj_base, col_base;                // where this add goes
+};
+hipError_t ugs_eps_build(const UgsEpsBuild &b, hipStream_t s);
 
 // ---- device-side preprocessing stages (ugs_preproc.hip) ----
 struct UgsDevPre;

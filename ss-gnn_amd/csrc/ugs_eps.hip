@@ -11,6 +11,8 @@
 // (seeds[graph], row inside the graph, attempt) instead: graph g's rows draw what a one-graph call with seed seeds[g] draws.
 // Edge extraction is a count pass (fused into the walk), a scan, and a fill pass that writes each sample's edges and
 // orders them by column inside the sample's own segment.
+// The adjacency rows are built on the host per call (ugs_side_eps.cpp) or, for epsilon_uniform_sampler.GraphCache, once per dataset
+// graph by ugs_eps_build_k at the end of this file (ugs_eps_cache.cpp); the walk and the fill read either through the same arguments.
 #include "ugs_device.h"
 
 namespace {
@@ -65,6 +67,7 @@ struct EpsArgs {
     const int64_t *edge_ptr;      // fill pass
     int64_t *edge_index, *edge_src;
     int64_t ld;
+    const int64_t *col_base;      // fill pass of a cached call: [num_graphs], added to the column of an ecs entry
 };
 
 // GRAPH_SEEDS = false: one seed per call, generator key (seed, batch row, attempt) -- sample_batch.
@@ -156,6 +159,10 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_walk(EpsArgs a) {
     }
 }
 
+// COL_BASE = false: ecs holds batch columns (the uncached call).  COL_BASE = true: ecs holds columns local to the row's graph and
+// col_base[gi] -- the columns of the graphs ahead of it in the batch -- makes them the batch's (a cached call); the offset is the
+// same for a whole row, so the order inside the row's segment is the same.
+template <bool COL_BASE>
 __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_fill(EpsArgs a) {
     const int k = a.k;
     for (int64_t row = (int64_t)blockIdx.x * EPS_BLOCK + threadIdx.x; row < a.rows; row += (int64_t)gridDim.x * EPS_BLOCK) {
@@ -164,6 +171,7 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_fill(EpsArgs a) {
         const int64_t gi = row / a.m;
         const UgsGraphDesc gd = a.graphs[gi];
         const int64_t *nrow = a.nodes + row * k;
+        const int64_t cbase = COL_BASE ? a.col_base[gi] : 0;
         int64_t w = e0;
         for (int j = 0; j < k; ++j) {
             const int64_t ug = nrow[j];
@@ -178,7 +186,7 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_fill(EpsArgs a) {
                 if (l < 0) continue;
                 a.edge_index[w] = a.mode == 0 ? (int64_t)j : ug;
                 a.edge_index[a.ld + w] = a.mode == 0 ? (int64_t)l : vg;
-                a.edge_src[w] = (int64_t)(cs >> 1);
+                a.edge_src[w] = (int64_t)(cs >> 1) + cbase;
                 ++w;
             }
         }
@@ -195,18 +203,100 @@ __global__ __launch_bounds__(EPS_BLOCK) void ugs_eps_fill(EpsArgs a) {
     }
 }
 
+// ---- the adjacency of a GraphCache add (UgsEpsBuild in ugs_device.h) ----
+// One wave per graph, one column per lane, 64 columns at a time.  A column (u, v) has two half-edges, (u, source side) and
+// (v, destination side); the row order wanted is (column, side) inside every vertex's row.  Inside a chunk a half-edge's place in
+// its vertex's row is the number of earlier half-edges of the chunk on the same vertex -- counted with cross-lane reads, one lane's
+// endpoints broadcast per step, so the order never depends on arrival -- on top of the vertex's cursor in memory, which the LAST
+// lane of the chunk that touches the vertex moves past the chunk's half-edges.  The same pass with the cursors at zero and nothing
+// written counts the rows; a wave scan turns the counts into row starts.  No atomics anywhere.
+constexpr int EPS_BUILD_BLOCK = 64;
+
+template <bool WRITE>
+__device__ __forceinline__ void eps_build_pass(const int2 *__restrict__ cols, int64_t cn, int32_t n, int32_t *cur, int32_t *nbr, int32_t *ecs,
+                                               int lane) {
+    for (int64_t t0 = 0; t0 < cn; t0 += EPS_BUILD_BLOCK) {
+        const int live = (int)(cn - t0 < EPS_BUILD_BLOCK ? cn - t0 : EPS_BUILD_BLOCK);       // uniform
+        int u = -1, v = -2;                                 // a lane without a column matches no vertex
+        bool ok = false;
+        if (lane < live) {
+            const int2 c = cols[t0 + lane];
+            ok = (uint32_t)c.x < (uint32_t)n && (uint32_t)c.y < (uint32_t)n;                  // (the host refuses any other column)
+            if (ok) { u = c.x; v = c.y; }
+        }
+        int ru = 0, rv = 0;                                 // half-edges of earlier lanes on u, on v
+        bool later_u = false, later_v = false;              // a later lane touches u, v
+        for (int j = 0; j < live; ++j) {
+            const int uj = __builtin_amdgcn_readlane(u, j), vj = __builtin_amdgcn_readlane(v, j);       // (j is uniform)
+            const int hu = (uj == u ? 1 : 0) + (vj == u ? 1 : 0), hv = (uj == v ? 1 : 0) + (vj == v ? 1 : 0);
+            if (j < lane) { ru += hu; rv += hv; }
+            else if (j > lane) { later_u = later_u || hu != 0; later_v = later_v || hv != 0; }
+        }
+        const bool loop = u == v;                           // both half-edges in one row, source side first
+        int32_t cu = 0, cv = 0;
+        if (ok) { cu = cur[u]; cv = cur[v]; }
+        if (WRITE && ok) {
+            const int32_t col = (int32_t)(t0 + lane);
+            const int64_t a = (int64_t)cu + ru, b = (int64_t)cv + rv + (loop ? 1 : 0);
+            if (a < 2 * cn) { nbr[a] = v; ecs[a] = 2 * col; }
+            if (b < 2 * cn) { nbr[b] = u; ecs[b] = 2 * col + 1; }
+        }
+        __syncthreads();                                    // every lane has its cursors: now they move
+        if (ok) {
+            if (!later_u) cur[u] = cu + ru + 1 + (loop ? 1 : 0);
+            if (!loop && !later_v) cur[v] = cv + rv + 1;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(EPS_BUILD_BLOCK) void ugs_eps_build_k(const UgsEpsBuild b) {
+    const int lane = (int)threadIdx.x;
+    for (int64_t g = blockIdx.x; g < b.G; g += gridDim.x) {
+        const int64_t v0 = b.vptr[g], c0 = b.cptr[g], cn = b.cptr[g + 1] - c0;
+        const int32_t n = (int32_t)(b.vptr[g + 1] - v0);
+        const int64_t ab = b.adj_base + 2 * c0;
+        const int2 *cols = b.cols + b.col_base + c0;
+        int32_t *cur = b.cursor + v0, *nbr = b.nbr + ab, *ecs = b.ecs + ab;
+        int64_t *rp = b.rowptr + b.row_base + v0 + g;
+        for (int64_t i = lane; i < n; i += EPS_BUILD_BLOCK) cur[i] = 0;
+        __syncthreads();
+        eps_build_pass<false>(cols, cn, n, cur, nbr, ecs, lane);
+        int32_t carry = 0;                                  // row starts: exclusive scan of the counts, 64 vertices at a time
+        for (int64_t base = 0; base < n; base += EPS_BUILD_BLOCK) {
+            const int64_t i = base + lane;
+            const int32_t c = i < n ? cur[i] : 0;
+            int32_t inc = c;
+            for (int d = 1; d < EPS_BUILD_BLOCK; d <<= 1) { const int32_t y = __shfl_up(inc, d); if (lane >= d) inc += y; }
+            if (i < n) { cur[i] = carry + inc - c; rp[i] = ab + carry + inc - c; }
+            carry += __shfl(inc, EPS_BUILD_BLOCK - 1);
+        }
+        if (lane == 0) rp[n] = ab + carry;
+        __syncthreads();
+        eps_build_pass<true>(cols, cn, n, cur, nbr, ecs, lane);
+    }
+}
+
 }  // namespace
+
+hipError_t ugs_eps_build(const UgsEpsBuild &b, hipStream_t s) {
+    if (b.G <= 0) return hipSuccess;
+    const int64_t grid = b.G < ((int64_t)1 << 16) ? b.G : ((int64_t)1 << 16);
+    hipLaunchKernelGGL(ugs_eps_build_k, dim3((unsigned)grid), dim3(EPS_BUILD_BLOCK), 0, s, b);
+    return hipGetLastError();
+}
 
 hipError_t ugs_eps_launch(const UgsEpsLaunch &l, int fill, int cus, hipStream_t s) {
     if (l.rows <= 0) return hipSuccess;
     EpsArgs a;
     a.graphs = l.graphs; a.rowptr = l.rowptr; a.nbr = l.nbr; a.ecs = l.ecs; a.num_graphs = l.num_graphs;
     a.m = l.m; a.k = l.k; a.mode = l.mode; a.max_attempts = l.max_attempts; a.seed = l.seed; a.seeds = l.seeds; a.epsilon = l.epsilon; a.rows = l.rows;
-    a.nodes = l.nodes; a.counts = l.counts; a.edge_ptr = l.edge_ptr; a.edge_index = l.edge_index; a.edge_src = l.edge_src; a.ld = l.ld;
+    a.nodes = l.nodes; a.counts = l.counts; a.edge_ptr = l.edge_ptr; a.edge_index = l.edge_index; a.edge_src = l.edge_src; a.ld = l.ld; a.col_base = l.col_base;
     int64_t grid = (l.rows + EPS_BLOCK - 1) / EPS_BLOCK;
     const int64_t cap = (int64_t)(cus > 0 ? cus : 256) * 8;
     if (grid > cap) grid = cap;
-    if (fill) hipLaunchKernelGGL(ugs_eps_fill, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
+    if (fill && l.col_base) hipLaunchKernelGGL(ugs_eps_fill<true>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
+    else if (fill) hipLaunchKernelGGL(ugs_eps_fill<false>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
     else if (l.seeds) hipLaunchKernelGGL(ugs_eps_walk<true>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
     else hipLaunchKernelGGL(ugs_eps_walk<false>, dim3((unsigned)grid), dim3(EPS_BLOCK), 0, s, a);
     return hipGetLastError();

@@ -1,6 +1,6 @@
 // ugs_host_internal.h -- what the host translation units of libugs_mi355.so share: ugs_host.cpp (preprocessing, registry, LRU, plans,
 // batch index, device batch pass), ugs_jobs.cpp (the two-phase job path and the streamed call), one ugs_side_<name>.cpp per side
-// sampler and ugs_graph_cache.cpp (ugs_sampler.GraphCache).  Not part of the C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
+// sampler, ugs_graph_cache.cpp (ugs_sampler.GraphCache) and ugs_eps_cache.cpp (epsilon_uniform_sampler.GraphCache).  Not part of the C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
 //
 // Declarations only: every global and every thread_local is defined in exactly one .cpp -- ugs_host.cpp, except the job-path section
 // at the end, which ugs_jobs.cpp owns.  Everything sits in namespace ugs_host with hidden visibility, so nothing here is exported

@@ -11,13 +11,19 @@ same growth law, same acceptance law min(1, eps/(w+eps)), same attempt budget ma
 sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", epsilon=0.1) -> the 5-tuple + failed[G] (bool, all False):
 graph g's rows keyed by (seeds[g], row inside the graph) instead of (seed, batch row) -- the presample loop batched; law at
 ugs_eps_sample_graphs_begin.
+
+GraphCache(device) builds the adjacency lists of every dataset graph once, on the device (add / add_many), and keeps them there:
+cache.sample_batch / cache.sample_graphs over any batch of added graphs equal the module's calls bit for bit, for every k and
+epsilon, while running only the walks, the scan and the fill.  Contract at ugs_eps_cache_sample_begin.
 """
 import ctypes as C
 
 from ugs_sampler import _graphs
 from ugs_sampler._lib import lib
 
-__all__ = ["sample_batch", "sample_graphs", "_sample_graphs"]
+from .graph_cache import GraphCache
+
+__all__ = ["sample_batch", "sample_graphs", "_sample_graphs", "GraphCache"]
 
 
 def sample_batch(edge_index, ptr, m_per_graph, k, mode="sample", seed=42, epsilon=0.1):

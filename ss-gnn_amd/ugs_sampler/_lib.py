@@ -96,6 +96,13 @@ def _load():
         "ugs_graph_cache_sample_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                          C.POINTER(vp), i64p],
         "ugs_graph_cache_last_launch": [vp, C.c_char_p, C.c_int, C.c_char_p, C.c_int],
+        "ugs_eps_cache_create": [C.c_int64, C.c_int64, C.POINTER(vp)],
+        "ugs_eps_cache_destroy": [vp],
+        "ugs_eps_cache_add": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp],
+        "ugs_eps_cache_info": [vp, i64p, i64p, i64p, i64p, i64p],
+        "ugs_eps_cache_graph_csr": [vp, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp],
+        "ugs_eps_cache_sample_begin": [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_double,
+                                       C.c_int, vp, C.POINTER(vp), i64p],
         "ugs_cache_clear": [],
         "ugs_cache_stats": [i64p, i64p, i64p],
         "ugs_batch_pass_stats": [i64p, i64p],
