@@ -2045,6 +2045,12 @@ template <int CAP> struct TierCfg {
 // DRAWS: the launch-uniform walk with its chunks' random numbers drawn across the lanes (chunk_draws; launch_lds picks it).  A
 // parameter of the one kernel template, so that every instantiation keeps the code it had: a body shared by two kernels through
 // an inlined function compiled the other tiers to different register allocations (the 32-candidate tier 95 -> 97 VGPRs).
+// Dynamic work loop: rows a wave works on together (a DPP row per walk: chunk_draws, Parked), and rows it takes per counter trip.
+#define UGS_WORK_CHUNK 4
+#ifndef UGS_WORK_GRAB
+#define UGS_WORK_GRAB 32
+#endif
+static_assert(UGS_WORK_GRAB % UGS_WORK_CHUNK == 0 && UGS_WORK_GRAB >= UGS_WORK_CHUNK, "a grab is whole sub-chunks");
 template <int GS, int CAP, int BLOCK, bool PAD, bool SEEDS = false, bool UNI = false, bool DRAWS = false>
 __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 5 : (CAP == 704 ? 3 : (CAP <= 64 || CAP == 1024 || CAP == 1408 ? 2 : 1)))) void ugs_walk_lds(UgsWalkArgs a) {
     using Cfg = TierCfg<CAP>;
@@ -2077,20 +2083,40 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
     if constexpr (UNI) ul.init(a);
     const int64_t total = (!UNI && a.in_list) ? (int64_t)*a.in_count : a.row_count;
     const int64_t ngroups = (int64_t)gridDim.x * GROUPS;
-    // Work distribution.  Dynamic (a.work_next, launches with many more walks than resident groups): chunks of UGS_WORK_CHUNK
-    // consecutive items, the first chunk by group index, every further one from a device counter (one round trip per chunk: a
-    // single hot address answers in several microseconds); a walk's cost varies, so a static split ends with the unluckiest wave.
+    // Work distribution.  Dynamic (a.work_next, launches with many more walks than resident groups): a wave works on chunks of
+    // UGS_WORK_CHUNK consecutive items and takes them from a device counter in GRABS of up to UGS_WORK_GRAB items, the first grab
+    // by group index; a walk's cost varies, so a static split ends with the unluckiest wave.
     // Two loops, two inlined copies of the walk: one shared loop measured 0.8 % slower on C5 (register allocation).
     if (a.work_next) {
-        // The counter counts ITEMS: a group takes its first chunk by index, every further one by atomicAdd(counter, chunk) with a
-        // chunk that shrinks as the launch drains -- 4 while more than 8 items per group are left (2 / 4 / 8 / 16 rows per counter
-        // round trip measured 8.85 / 8.83 / 8.91 / 9.04 ms per 1M walks; 1 throughout is 50 % slower: the counter's round trip
-        // under contention), then 2, and 1 for the last two items per group, so that the launch ends within one walk of even
-        // (guided self-scheduling; matters most for launches that give a group only a few dozen walks, e.g. a rank's shard).
-        // (against fixed chunks of 4, or 2 for small launches: 6.80 -> 6.77 ms per 1M walks, 0.951 -> 0.929 ms per 125k)
-        auto chunk_for = [&](int64_t left) -> int64_t { return left > 8 * ngroups ? 4 : (left > 2 * ngroups ? 2 : 1); };
+        // The counter counts ITEMS and is ONE word for the whole device.  A same-address atomicAdd-with-return is served in 12 ns,
+        // one at a time, whoever asks (tools/counter_probe.hip: 5120 waves on one word 12.0 ns per trip, 83 M trips/s; one wave
+        // alone gets its answer in 0.32 us) -- the microseconds a trip was seen to take inside a launch are the QUEUE of a
+        // saturated server, not a latency, and the trips of a launch are a floor under its time whatever its walks cost: four rows
+        // per trip are 250 000 trips, 3.0 ms, per 1M rows, where every light shape of this tier sat (ER degree 40 at k = 4: 3.12 ms
+        // with the counter, 1.94 ms with the static split's slower code; profiles/work_grabs_probe.txt).  (One row per trip "50 %
+        // slower" than 8.83 ms and "2 / 4 / 8 / 16 rows per trip 8.85 / 8.83 / 8.91 / 9.04 ms" in earlier notes here are the same
+        // server seen by a kernel of 8.8 ms: 1M trips are 12 ms, 250 000 are 3 ms and hide behind the walks.)
+        // So a GRAB of UGS_WORK_GRAB rows per trip while more than 2 * UGS_WORK_GRAB items per group are left; the wave works it off
+        // as sub-chunks of four -- the chunk is bound to the wave, a DPP row per walk (chunk_draws, Parked) -- each with its own
+        // chunk_draws and its own flush_parked, and goes back to the counter only when the grab is used up.  Then, as the launch
+        // drains, 4 while more than 8 items per group are left, then 2, and 1 for the last two items per group, so that the launch
+        // ends within one walk of even (guided self-scheduling; matters most for launches that give a group only a few dozen walks,
+        // e.g. a rank's shard, which never reach a grab above four).  A wave sizes its grab by its own position, which is at or
+        // behind the counter: the estimate only picks the size.
+        // Measured (profiles/work_grabs_ab.txt, work_grabs_sweep_er_shapes.txt), grabs of 8 / 16 / 32 against chunks of four: C5
+        // step 4.187 -> 4.153 / 4.150 / 4.140 ms; degree 40 at k = 4 3.28 -> 1.94 / 1.88 / 1.95 ms.  32 is kept: best on C5, the
+        // only one there that clears twice the wider spread.  A halving ladder (32, 16, 8, 4, 2, 1) makes fewer trips still and wins
+        // at k = 4 (1.81 ms) but lost on C5 (4.156 ms) and at k = 10 (+3 %); from 64 down it lost everywhere above k = 4.
+        // Grabs are taken by the one-walk-per-wave tiers only: the 8- and 16-lane tiers keep the four-row trips and the code they
+        // had (with the grab in their loop the 8-lane, 32-candidate instantiation went 95 -> 97 VGPRs and from five waves per SIMD
+        // to four, and C4's walk 0.061 -> 0.067 ms although its launches take the static split).
+        constexpr bool GRABS = GS == 64 && UGS_WORK_GRAB > UGS_WORK_CHUNK;
+        auto chunk_for = [&](int64_t left) -> int64_t {
+            if constexpr (GRABS) { if (left > 2 * (int64_t)UGS_WORK_GRAB * ngroups) return (int64_t)UGS_WORK_GRAB; }
+            return left > 8 * ngroups ? 4 : (left > 2 * ngroups ? 2 : 1);
+        };
         const int64_t first = chunk_for(total);
-        int64_t it = ((int64_t)blockIdx.x * GROUPS + gib) * first, end = it + first;
+        int64_t it = ((int64_t)blockIdx.x * GROUPS + gib) * first, gend = it + first;
         // Rows of a chunk park their epilogue (see Parked): one walk per wave, k <= 8, staging on -- the same answer for every wave
         // of the launch.  Every chunk ends with the epilogue of its parked rows, the drain's chunks of two and one and a chunk cut
         // short by `total` included: nothing is parked when the next chunk starts or the kernel returns.
@@ -2102,7 +2128,9 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
         static_assert(!DRAWS || (BT && UNI), "lane-parallel draws: the launch-uniform walk");
         ChunkDraws cd{0u, 0u};
         while (it < total) {
-            if (end > total) end = total;
+            if (gend > total) gend = total;
+            int64_t end = gend;
+            if constexpr (GRABS) end = gend - it > UGS_WORK_CHUNK ? it + UGS_WORK_CHUNK : gend;   // this sub-chunk of the grab
             uint32_t dcur = 0u;
             if constexpr (DRAWS) chunk_draws(cd, a.seed_ptr ? *a.seed_ptr : a.seed64, a.row_begin + it, a.k + 1, &ul.gd);
             for (; it < end; ++it) {
@@ -2119,7 +2147,6 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
                     if (ne) park_row(pk, g, (uint32_t)end - 1u - (uint32_t)it, SV, EL, ne, g.uni(res.py), row_rel, off);
                 }
             }
-            const int64_t chunk = chunk_for(total - it);                 // `it` is close to the counter: the estimate only picks the chunk size
             unsigned long long nxt = 0ull;
             if constexpr (BT) {
                 if (park) {
@@ -2139,10 +2166,12 @@ __global__ __launch_bounds__(BLOCK, CAP <= 32 ? 4 : ((CAP > 64 && CAP <= 512) ? 
             }
             // (the counter asked for behind the parked hits' gather instead of here, its round trip beside the gather's, measured
             // 0.3 % SLOWER on C5 -- 227.1..227.6 against 227.8..228.3 M rows/s, five alternations: the epilogue then waits for both)
+            if constexpr (GRABS) { if (it < gend) continue; }            // the grab's next sub-chunk: no counter trip
+            const int64_t chunk = chunk_for(total - it);                 // `it` is close to the counter: the estimate only picks the grab size
             if (g.lane == 0) nxt = atomicAdd(a.work_next, (unsigned long long)chunk);
             const uint32_t lo = g.bcast((uint32_t)nxt, 0), hi = g.bcast((uint32_t)(nxt >> 32), 0);
             it = ngroups * first + (int64_t)(((unsigned long long)hi << 32) | lo);
-            end = it + chunk;
+            gend = it + chunk;
         }
         return;
     }
