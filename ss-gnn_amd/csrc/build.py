@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "libugs_mi355.so")
 SRCS = [os.path.join(HERE, "ugs_kernels.hip"), os.path.join(HERE, "ugs_eps.hip"), os.path.join(HERE, "ugs_uniform.hip"), os.path.join(HERE, "ugs_rwr.hip"), os.path.join(HERE, "ugs_preproc.hip"), os.path.join(HERE, "ugs_collate.hip"), os.path.join(HERE, "ugs_batch.hip"), os.path.join(HERE, "ugs_host.cpp"),
-        os.path.join(HERE, "ugs_jobs.cpp"), os.path.join(HERE, "ugs_side_eps.cpp"), os.path.join(HERE, "ugs_side_uniform.cpp"), os.path.join(HERE, "ugs_side_rwr.cpp"),
+        os.path.join(HERE, "ugs_jobs.cpp"), os.path.join(HERE, "ugs_side_eps.cpp"), os.path.join(HERE, "ugs_side_uniform.cpp"), os.path.join(HERE, "ugs_side_rwr.cpp"), os.path.join(HERE, "ugs_cache_common.cpp"), os.path.join(HERE, "ugs_rwr_cache.cpp"),
         os.path.join(HERE, "ugs_graph_cache.cpp"), os.path.join(HERE, "ugs_store.hip"), os.path.join(HERE, "ugs_eps_cache.cpp"),
         os.path.join(HERE, "ugs_apx.cpp"), os.path.join(HERE, "ugs_apx_gpu.hip"), os.path.join(HERE, "ugs_wl.hip")]
 HDRS = [os.path.join(HERE, "ugs_device.h"), os.path.join(HERE, "ugs_host_internal.h"), os.path.join(HERE, "ugs_apx_common.h"), os.path.join(HERE, "..", "..", "include", "ugs_mi355.h")]

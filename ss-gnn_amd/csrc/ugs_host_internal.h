@@ -1,9 +1,12 @@
 // ugs_host_internal.h -- what the host translation units of libugs_mi355.so share: ugs_host.cpp (preprocessing, registry, LRU, plans,
 // batch index, device batch pass), ugs_jobs.cpp (the two-phase job path and the streamed call), one ugs_side_<name>.cpp per side
-// sampler, ugs_graph_cache.cpp (ugs_sampler.GraphCache) and ugs_eps_cache.cpp (epsilon_uniform_sampler.GraphCache).  Not part of the C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
+// sampler, one file per dataset cache -- ugs_rwr_cache.cpp (rwr_sampler.GraphCache), ugs_graph_cache.cpp (ugs_sampler.GraphCache),
+// ugs_eps_cache.cpp (epsilon_uniform_sampler.GraphCache) -- and ugs_cache_common.cpp (what those three share).  Not part of the
+// C ABI (that is include/ugs_mi355.h) and not for the .hip files (they share ugs_device.h).
 //
-// Declarations only: every global and every thread_local is defined in exactly one .cpp -- ugs_host.cpp, except the job-path section
-// at the end, which ugs_jobs.cpp owns.  Everything sits in namespace ugs_host with hidden visibility, so nothing here is exported
+// Declarations and templates only: every global and every thread_local is defined in exactly one .cpp -- ugs_host.cpp, except the
+// job-path section, which ugs_jobs.cpp owns, and the caches' section at the end, which ugs_cache_common.cpp owns.
+// Everything sits in namespace ugs_host with hidden visibility, so nothing here is exported
 // (the block a .cpp defines these in repeats the attribute: a definition does not take it over from its declaration);
 // the two opaque types of the C ABI, ugs_plan and ugs_job, stay at global scope.
 #pragma once
@@ -18,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -285,5 +289,144 @@ int scan_ptr(const int64_t *ptr, int64_t G, bool per_graph, std::vector<int32_t>
     }
     return UGS_OK;
 }
+
+// ---- what the dataset caches share (rwr_sampler, ugs_sampler and epsilon_uniform_sampler GraphCache: ugs_rwr_cache.cpp,
+//      ugs_graph_cache.cpp, ugs_eps_cache.cpp; defined in ugs_cache_common.cpp) ----
+// A cache's device storage is a short fixed list of arrays, stated as data.  Arrays of one capacity group hold the same number of
+// entries and grow together (rwr: rs and doomed; ugs: adj and adjf; eps: nbr and ecs).
+constexpr int STORE_MAX = 6;
+struct StoreArray { size_t elem; int group; };
+struct StoreShape { int arrays, groups; StoreArray a[STORE_MAX]; };
+
+// One generation of the storage.  Growth makes a new one and copies; a job holds the one it walks on for as long as it lives.
+struct StoreGen {
+    const StoreShape &shape;
+    void *p[STORE_MAX] = {};
+    int64_t cap[STORE_MAX] = {};              // entries per group, each at least 1
+    explicit StoreGen(const StoreShape &s) : shape(s) {}
+    StoreGen(const StoreGen &) = delete;
+    ~StoreGen();
+    int64_t bytes() const;
+    template <class T> T *at(int array) const { return static_cast<T *>(p[array]); }
+};
+
+// The state every cache has; a cache derives its own from it and adds its slots (a deque whose entries have n, cols and col0).
+// The locking, the same for all three: adds run one at a time under add_mu, from the build to the publication, and only they write
+// used, gen and dev, so an add reads them under add_mu alone.  An add publishes under the exclusive `mu`, only after its stream has
+// synchronised, and a failed add publishes nothing: the cache is as it was.  A begin copies `gen` and reads the slots under the
+// shared `mu`, and its job keeps the generation alive (plan->keep for ugs, the fill hook's capture for rwr and eps).
+struct CacheState {
+    const StoreShape &shape;
+    const char *name, *sampler;               // "rwr cache" in the add's refusals and the device check, "rwr_sampler" in the begin's
+    int info_vertices, info_entries;          // the groups whose fill info reports as vertices and as half-edges / CSR entries
+    int dev = -1;
+    int64_t reserve[STORE_MAX] = {};          // per group: the least a first allocation takes
+    std::mutex add_mu;
+    std::shared_mutex mu;
+    std::shared_ptr<StoreGen> gen;
+    int64_t used[STORE_MAX] = {}, graphs = 0, generations = 0;
+    CacheState(const StoreShape &s, const char *name_, const char *sampler_, int info_v, int info_e)
+        : shape(s), name(name_), sampler(sampler_), info_vertices(info_v), info_entries(info_e) {}
+};
+int cache_reserve_check(int64_t reserve_vertices, int64_t reserve_columns);
+int cache_info(CacheState *st, int64_t *graphs_out, int64_t *vertices_out, int64_t *entries_out, int64_t *bytes_out, int64_t *generations_out);
+
+// An add between its front half and its publication.
+struct CacheAdd {
+    DeviceCtx dc;
+    std::shared_ptr<StoreGen> gen;            // where the build writes, behind `used`: the current generation or (grow) a new one
+    bool grow = false;
+    int64_t need[STORE_MAX] = {};             // per group: the entries used once the add is published
+};
+// The add's front half.  cache_add_args: the argument checks (`outs`: the outputs the cache fills for G > 0 are there); G == 0 adds
+// nothing and is no error unless it brings columns.  The ptr scan is scan_ptr.  cache_walk_columns hands column x to
+// each(x, g, u - ptr[g], v - ptr[g]) and leaves the prefix sums of the columns per graph in cptr [G + 1]: columns must come graph by
+// graph, in the order of the graphs, both endpoints inside the graph -- that order is what a batch is compared with, and a column
+// that left its graph could fall into a neighbour's range once the graph stands in a batch.  cache_add_device (under add_mu, behind
+// the cache's own 2^31 guards): the calling thread's device, which must be the cache's.
+int cache_add_args(const char *name, bool have_cache, const int64_t *edge_index, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                   bool outs, const char *outs_text, int64_t cols_limit, const char *cols_limit_text);
+template <class Each>
+int cache_walk_columns(const char *name, const int64_t *edge_index, int64_t row_stride, int64_t E, const int64_t *ptr, int64_t G,
+                       std::vector<int64_t> &cptr, Each each) {
+    cptr.assign((size_t)G + 1, 0);
+    int64_t g = 0;
+    for (int64_t x = 0; x < E; ++x) {
+        const int64_t u = edge_index[x], v = edge_index[row_stride + x];
+        while (g < G && !(ptr[g] <= u && u < ptr[g + 1])) ++g;
+        if (g >= G || !(ptr[g] <= v && v < ptr[g + 1]))
+            return fail(UGS_E_BAD_ARG, std::string(name) + " add: column " + std::to_string(x) + " is not inside one graph, or the columns are not in the order of the graphs");
+        ++cptr[(size_t)g + 1];
+        each(x, g, u - ptr[g], v - ptr[g]);
+    }
+    for (int64_t h = 0; h < G; ++h) cptr[(size_t)h + 1] += cptr[(size_t)h];
+    return UGS_OK;
+}
+int cache_add_device(const CacheState &st, CacheAdd &a);
+// Room for a.need: the current generation, or a new one -- per group max(need, twice what there was, the reserve) entries, at least
+// 1 -- with the copies of everything held so far (used * elem bytes of every array) queued on the add's stream.
+int cache_room(const CacheState &st, CacheAdd &a);
+// The publication, behind the stream's synchronisation: push() appends the cache's slots, placed from st.used as it still is.
+template <class Push>
+void cache_publish(CacheState &st, const CacheAdd &a, int64_t G, Push push) {
+    std::unique_lock<std::shared_mutex> lk(st.mu);
+    push();
+    st.dev = a.dc.id;
+    if (a.grow) { st.gen = a.gen; ++st.generations; }
+    std::copy(a.need, a.need + st.shape.groups, st.used);
+    st.graphs += G;
+}
+
+// What a begin takes from the cache under the shared lock: the generation, and per graph of the batch the prefix sums of the column
+// counts and the first stored column (E = coff[G]).
+struct CacheBatch {
+    std::shared_ptr<StoreGen> gen;
+    int dev = -1;
+    std::vector<int64_t> coff, col0;
+    int64_t E = 0;
+};
+// The begin's front half.  cache_begin_args: the argument checks all three share; the cache's own follow it.  cache_scan_slots:
+// every slot known, ptr non-decreasing, every graph of the batch as large as the graph added in its place; each(g, slot, n) writes
+// the cache's descriptor and may refuse the graph (its return, UGS_OK to go on).  cache_begin_device: the column total, if the
+// batch's columns are at hand (`compare`), and the calling thread's device, which must be the cache's.
+int cache_begin_args(const char *name, bool have_args, const int64_t *slots, const int64_t *edge_index, int64_t num_cols, int64_t num_graphs, int check);
+template <class Slots, class Each>
+int cache_scan_slots(CacheState &st, const Slots &all, const int64_t *slots, const int64_t *ptr, int64_t G, CacheBatch &cb, Each each) {
+    if (G >= (int64_t)0x7f7f7f7f) return fail(UGS_E_UNSUPPORTED, "batch too large: graphs must be < 0x7f7f7f7f");   // (first_bad starts there)
+    cb.coff.assign((size_t)G + 1, 0); cb.col0.assign((size_t)G, 0);
+    std::shared_lock<std::shared_mutex> lk(st.mu);
+    cb.gen = st.gen;
+    cb.dev = st.dev;
+    for (int64_t g = 0; g < G; ++g) {
+        if (slots[g] < 0 || slots[g] >= (int64_t)all.size()) return fail(UGS_E_BAD_ARG, std::string("unknown ") + st.name + " slot " + std::to_string(slots[g]));
+        const auto &s = all[(size_t)slots[g]];
+        const int64_t n = ptr[g + 1] - ptr[g];
+        if (n < 0) return fail(UGS_E_BAD_ARG, "ptr must be non-decreasing (graph " + std::to_string(g) + ")");
+        if (n != s.n)
+            return fail(UGS_E_BAD_ARG, std::string(st.sampler) + " cache: graph " + std::to_string(g) + " of the batch has " + std::to_string(n) +
+                                           " vertices, the graph added in its place has " + std::to_string(s.n));
+        if (int rc = each(g, s, n)) return rc;
+        cb.coff[(size_t)g + 1] = cb.coff[(size_t)g] + s.cols;
+        cb.col0[(size_t)g] = s.col0;
+    }
+    cb.E = cb.coff[(size_t)G];
+    return UGS_OK;
+}
+int cache_begin_device(const CacheState &st, const CacheBatch &cb, bool compare, int64_t num_cols, DeviceCtx &dc);
+
+// The inputs of the check of a cached call (ugs_store_check, ugs_rwr_store_check), as pieces of the call's blob: coff [G + 1],
+// lo [G] (the batch's ptr), col0 [G] and both rows of the batch's Ec columns.  A piece goes up only where its flag says so; each
+// cache fills its own kernel struct from the offsets.  cache_check_verdict turns the word the check leaves (first_bad, 0x7f7f7f7f
+// where the host set it: above every g) into the refusal.
+struct CheckInputs {
+    size_t coff, lo, col0, src, dst;
+    bool coff_up, lo_up, col0_up;
+    int64_t Ec;
+    CheckInputs(BlobLayout &L, int64_t G, int64_t Ec_, bool coff_up_, bool lo_up_, bool col0_up_)
+        : coff(L.take(coff_up_ ? (size_t)(G + 1) * 8 : 0)), lo(L.take(lo_up_ ? (size_t)G * 8 : 0)), col0(L.take(col0_up_ ? (size_t)G * 8 : 0)),
+          src(L.take((size_t)Ec_ * 8)), dst(L.take((size_t)Ec_ * 8)), coff_up(coff_up_), lo_up(lo_up_), col0_up(col0_up_), Ec(Ec_) {}
+    void stage(char *host, const CacheBatch &cb, const int64_t *ptr, int64_t G, const int64_t *edge_index, int64_t row_stride) const;
+};
+int cache_check_verdict(const CacheState &st, int64_t word, int64_t G);
 
 }  // namespace ugs_host

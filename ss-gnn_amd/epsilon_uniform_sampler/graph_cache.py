@@ -1,13 +1,14 @@
 """epsilon_uniform_sampler.GraphCache: the adjacency lists of every graph of a dataset built once, by a kernel, and kept on the
 device; a training step over any batch of added graphs then runs only the walks, the scan and the fill (C ABI and contract:
-include/ugs_mi355.h at ugs_eps_cache_sample_begin; layout, the build kernel and generations: DESIGN.md section 16).  Modelled on
-rwr_sampler.GraphCache and ugs_sampler.GraphCache."""
+include/ugs_mi355.h at ugs_eps_cache_sample_begin; layout, the build kernel and generations: DESIGN.md section 16; what it shares
+with the other samplers' caches: ugs_sampler/_dataset_cache.py)."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from ugs_sampler import _graphs
+from ugs_sampler._dataset_cache import DatasetCache
 from ugs_sampler._lib import check as _check
 from ugs_sampler._lib import lib
 
@@ -15,7 +16,7 @@ from ugs_sampler._lib import lib
 CHUNK_COLUMNS = 1 << 24
 
 
-class GraphCache:
+class GraphCache(DatasetCache):
     """The adjacency lists of a dataset's graphs, built once and kept on `device`, for every k and epsilon.
 
         cache = GraphCache("cuda:0")
@@ -36,123 +37,23 @@ class GraphCache:
     begun before an add finishes on the buffers it started with.  Adds are exclusive among themselves; any number of threads may
     sample meanwhile."""
 
+    SAMPLER, ENTRIES, CHUNK = "epsilon_uniform_sampler", "half_edges", CHUNK_COLUMNS
+    _destroy, _info = staticmethod(lib.ugs_eps_cache_destroy), staticmethod(lib.ugs_eps_cache_info)
+
     def __init__(self, device, *, reserve=(0, 0)):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise ValueError("device must be a GPU device")
-        rv, rc = (int(x) for x in reserve)
-        if rv < 0 or rc < 0:
-            raise ValueError(f"reserve must be two counts >= 0, got {reserve}")
-        self._slot = {}                 # graph index -> (slot, vertices, columns)
-        self._cache = C.c_void_p()
-        _check(lib.ugs_eps_cache_create(rv, rc, C.byref(self._cache)))
+        super().__init__(device, reserve, lib.ugs_eps_cache_create)
 
-    def close(self):
-        """Frees the storage (once the jobs still sampling from it have finished); the object cannot be used afterwards."""
-        if getattr(self, "_cache", None):
-            lib.ugs_eps_cache_destroy(self._cache)
-            self._cache = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # noqa: BLE001  (interpreter shutdown: the library may be gone already)
-            pass
-
-    def _handle(self):
-        if not self._cache:
-            raise RuntimeError("the cache is closed")
-        return self._cache
-
-    def add(self, index, edge_index, num_nodes):
-        """One graph; same effect as add_many of one."""
-        self.add_many([index], [(edge_index, num_nodes)])
-
-    def add_many(self, indices, graphs):
-        """`graphs` holds (edge_index, num_nodes) per index, local vertex ids as a dataset stores them.  A column with an endpoint
-        outside [0, num_nodes) raises ValueError naming the index, and nothing of the call is added: in a batch such a column
-        could fall into a neighbouring graph, where the uncached call would keep it.  A few batched device calls."""
-        indices = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
-        graphs = list(graphs)
-        if len(indices) != len(graphs):
-            raise ValueError("indices and graphs must have the same length")
-        cols = []
-        for i, (ei, n) in zip(indices, graphs):
-            if not torch.is_tensor(ei):
-                raise RuntimeError("edge_index must be a tensor")
-            _graphs.check_int64(ei, torch.empty(0, dtype=torch.int64))
-            if ei.dim() != 2 or ei.size(0) != 2:
-                raise RuntimeError("edge_index must have shape [2, E]")
-            if int(n) < 0:
-                raise ValueError("num_nodes must be >= 0")
-            a = ei.detach().cpu().numpy()
-            if a.size and (a.min() < 0 or a.max() >= int(n)):
-                raise ValueError(f"graph {i} has a column with an endpoint outside [0, {int(n)})")
-            cols.append(a)
-        self._handle()
-        run, ne, nv = [], 0, 0
-        for i, a, (_, n) in zip(indices, cols, graphs):
-            if run and (ne + a.shape[1] > CHUNK_COLUMNS or nv + int(n) > CHUNK_COLUMNS):
-                self._batched(run)
-                run, ne, nv = [], 0, 0
-            run.append((i, a, int(n)))
-            ne, nv = ne + a.shape[1], nv + int(n)
-        self._batched(run)
-
-    def _batched(self, run):
-        if not run:
-            return
-        G = len(run)
-        ptr = np.zeros(G + 1, np.int64)
-        np.cumsum([g[2] for g in run], out=ptr[1:])
-        ei = np.ascontiguousarray(np.concatenate([a + ptr[g] for g, (_, a, _) in enumerate(run)], axis=1))
-        slots = np.zeros(G, np.int64)
-        _graphs._select_device(self.dev)
-        _check(lib.ugs_eps_cache_add(self._handle(), ei.ctypes.data, ei.shape[1], ei.shape[1], ptr.ctypes.data, G, slots.ctypes.data))
-        for (i, a, n), s in zip(run, slots.tolist()):
-            self._slot[i] = (s, n, a.shape[1])
-
-    def _out_device(self, device):
-        """`device`, if given, must be the cache's: the outputs are always there."""
-        if device is not None:
-            dev = torch.device(device)
-            if dev.type != "cuda":
-                raise ValueError("device= must be a GPU device")
-            if dev.index is not None and self.dev.index is not None and dev.index != self.dev.index:
-                raise ValueError(f"the cache lives on {self.dev}, not on {dev}")
-        return self.dev
+    def _add(self, run, ei, ptr, slots):
+        _check(lib.ugs_eps_cache_add(self._handle(), ei.ctypes.data, ei.shape[1], ei.shape[1], ptr.ctypes.data, len(run), slots.ctypes.data))
 
     def _job(self, graph_idx, ptr, edge_index, m_per_graph, k, mode, seed, seeds, epsilon, check, device):
-        if not torch.is_tensor(ptr):
-            raise TypeError("ptr must be a torch.Tensor")
-        if edge_index is None:
-            if check:
-                raise ValueError("edge_index=None needs check=False: the check compares the batch's columns")
-        else:
-            _graphs.check_int64(edge_index, ptr)
-            _graphs._edge_index_view(edge_index)
-        if ptr.dtype != torch.int64:
-            raise RuntimeError("ptr must be int64")
+        self._check_batch(ptr, edge_index, check)
         if not (epsilon > 0.0 and epsilon <= 1.0):                     # (the uncached call's check and text)
             raise RuntimeError("epsilon must be in (0, 1]")
-        dev = self._out_device(device)
-        gi = graph_idx.cpu().flatten().tolist() if torch.is_tensor(graph_idx) else [int(i) for i in graph_idx]
+        dev = self._own_device(device)
+        gi, G = self._graphs_of(graph_idx, ptr)
         pt = ptr.detach().cpu().contiguous()
-        G = pt.numel() - 1
-        if len(gi) != G:
-            raise ValueError(f"graph_idx names {len(gi)} graphs, ptr holds {G}")
-        slots = np.zeros(max(G, 1), np.int64)
-        have, total = pt.tolist(), 0
-        for g, i in enumerate(gi):
-            if i not in self._slot:
-                raise KeyError(i)
-            slots[g], n, ncol = self._slot[i]
-            if have[g + 1] - have[g] != n:
-                raise RuntimeError(f"epsilon_uniform_sampler cache: graph {g} of the batch has {have[g + 1] - have[g]} vertices, "
-                                   f"the graph added in its place has {n}")
-            total += ncol
-        if edge_index is not None and edge_index.size(1) != total:
-            raise RuntimeError(f"epsilon_uniform_sampler cache: the batch has {edge_index.size(1)} columns, the added graphs have {total}")
+        slots = self._slots_of(gi, pt.tolist(), edge_index)
         cache = self._handle()
         md, eps = 0 if mode == "sample" else 1, C.c_double(float(epsilon))
         sd = _graphs.seed_array(seeds, max(G, 0)) if seeds is not None else None
@@ -198,6 +99,4 @@ class GraphCache:
     def info(self):
         """graphs (indices held), vertices (entries of the row-offset array: vertices plus one per graph added), half_edges, bytes
         of the device storage and generations (allocations so far); what replaced graphs held stays counted until close"""
-        v = [C.c_int64() for _ in range(5)]
-        _check(lib.ugs_eps_cache_info(self._handle(), *[C.byref(x) for x in v]))
-        return {"graphs": len(self._slot), "vertices": v[1].value, "half_edges": v[2].value, "bytes": v[3].value, "generations": v[4].value}
+        return super().info()

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ugs_sampler import _graphs
+from ugs_sampler._dataset_cache import DatasetCache
 from ugs_sampler._lib import check as _check
 from ugs_sampler._lib import lib
 
@@ -70,7 +71,7 @@ def _sample_graphs(edge_index, ptr, m_per_graph, k, seeds, mode="sample", p_rest
 CHUNK_COLUMNS = 1 << 24
 
 
-class GraphCache:
+class GraphCache(DatasetCache):
     """The CSRs of a dataset's graphs, built once and kept on `device`, for one k.
 
         cache = GraphCache(k, "cuda:0")
@@ -90,133 +91,36 @@ class GraphCache:
     grows by doubling, and a call begun before an add finishes on the buffers it started with.  Adds are exclusive; any number of
     threads may sample at once."""
 
+    SAMPLER, ENTRIES, CHUNK = "rwr_sampler", "half_edges", CHUNK_COLUMNS
+    _destroy, _info = staticmethod(lib.ugs_rwr_cache_destroy), staticmethod(lib.ugs_rwr_cache_info)
+
     def __init__(self, k, device, *, reserve=(0, 0)):
         self.k = int(k)
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise ValueError("device must be a GPU device")
-        rv, rc = (int(x) for x in reserve)
-        if rv < 0 or rc < 0:
-            raise ValueError(f"reserve must be two counts >= 0, got {reserve}")
         self.failed = set()
-        self._slot = {}                 # graph index -> (slot, vertices, columns)
-        self._cache = C.c_void_p()
-        _check(lib.ugs_rwr_cache_create(self.k, rv, rc, C.byref(self._cache)))
-
-    def close(self):
-        """Frees the storage (once the jobs still sampling from it have finished); the object cannot be used afterwards."""
-        if getattr(self, "_cache", None):
-            lib.ugs_rwr_cache_destroy(self._cache)
-            self._cache = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # noqa: BLE001  (interpreter shutdown: the library may be gone already)
-            pass
-
-    def _handle(self):
-        if not self._cache:
-            raise RuntimeError("the cache is closed")
-        return self._cache
+        super().__init__(device, reserve, lib.ugs_rwr_cache_create, self.k)
 
     def add(self, index, edge_index, num_nodes):
         """One graph; same effect as add_many of one.  Returns False if the graph failed."""
         self.add_many([index], [(edge_index, num_nodes)])
         return int(index) not in self.failed
 
-    def add_many(self, indices, graphs):
-        """`graphs` holds (edge_index, num_nodes) per index, local vertex ids as a dataset stores them.  A column with an endpoint
-        outside [0, num_nodes) raises ValueError naming the index, and nothing of the call is added: in a batch such a column
-        could fall into a neighbouring graph, where the uncached call would keep it.  A few batched device calls."""
-        indices = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
-        graphs = list(graphs)
-        if len(indices) != len(graphs):
-            raise ValueError("indices and graphs must have the same length")
-        cols = []
-        for i, (ei, n) in zip(indices, graphs):
-            if not torch.is_tensor(ei):
-                raise RuntimeError("edge_index must be a tensor")
-            _graphs.check_int64(ei, torch.empty(0, dtype=torch.int64))
-            if ei.dim() != 2 or ei.size(0) != 2:
-                raise RuntimeError("edge_index must have shape [2, E]")
-            if int(n) < 0:
-                raise ValueError("num_nodes must be >= 0")
-            a = ei.detach().cpu().numpy()
-            if a.size and (a.min() < 0 or a.max() >= int(n)):
-                raise ValueError(f"graph {i} has a column with an endpoint outside [0, {int(n)})")
-            cols.append(a)
-        self._handle()
-        run, ne, nv = [], 0, 0
-        for i, a, (_, n) in zip(indices, cols, graphs):
-            if run and (ne + a.shape[1] > CHUNK_COLUMNS or nv + int(n) > CHUNK_COLUMNS):
-                self._batched(run)
-                run, ne, nv = [], 0, 0
-            run.append((i, a, int(n)))
-            ne, nv = ne + a.shape[1], nv + int(n)
-        self._batched(run)
-
-    def _batched(self, run):
-        if not run:
-            return
-        G = len(run)
-        ptr = np.zeros(G + 1, np.int64)
-        np.cumsum([g[2] for g in run], out=ptr[1:])
-        ei = np.ascontiguousarray(np.concatenate([a + ptr[g] for g, (_, a, _) in enumerate(run)], axis=1))
-        slots, status = np.zeros(G, np.int64), np.zeros(G, np.int32)
-        _graphs._select_device(self.dev)
-        _check(lib.ugs_rwr_cache_add(self._handle(), ei.ctypes.data, ei.shape[1], ei.shape[1], ptr.ctypes.data, G, slots.ctypes.data,
+    def _add(self, run, ei, ptr, slots):
+        status = np.zeros(len(run), np.int32)
+        _check(lib.ugs_rwr_cache_add(self._handle(), ei.ctypes.data, ei.shape[1], ei.shape[1], ptr.ctypes.data, len(run), slots.ctypes.data,
                                      status.ctypes.data))
-        for (i, a, n), s, st in zip(run, slots.tolist(), status.tolist()):
-            self._slot[i] = (s, n, a.shape[1])
+        for (i, _, _), st in zip(run, status.tolist()):
             if st:
                 self.failed.add(i)
             else:
                 self.failed.discard(i)
 
-    def _out_device(self, device, ptr, edge_index):
-        """Where the outputs go: `device`, else the device of a GPU ptr (or edge_index), else None (pinned host tensors)."""
-        if device is None:
-            for t in (ptr, edge_index):
-                if t is not None and t.device.type == "cuda":
-                    device = t.device
-                    break
-            else:
-                return None
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("device= must be a GPU device (or None for pinned host tensors)")
-        if dev.index is not None and self.dev.index is not None and dev.index != self.dev.index:
-            raise ValueError(f"the cache lives on {self.dev}, not on {dev}")
-        return self.dev
-
     def _job(self, graph_idx, ptr, edge_index, m_per_graph, mode, seed, seeds, p_restart, streams, check, device):
         rows = _row_streams(streams)
-        if edge_index is None:
-            if check:
-                raise ValueError("edge_index=None needs check=False: the check compares the batch's columns")
-        else:
-            _graphs.check_int64(edge_index, ptr)
-            _graphs._edge_index_view(edge_index)
-        if ptr.dtype != torch.int64:
-            raise RuntimeError("ptr must be int64")
+        self._check_batch(ptr, edge_index, check)
         dev = self._out_device(device, ptr, edge_index)
-        gi = graph_idx.cpu().flatten().tolist() if torch.is_tensor(graph_idx) else [int(i) for i in graph_idx]
-        G = ptr.numel() - 1
-        if len(gi) != G:
-            raise ValueError(f"graph_idx names {len(gi)} graphs, ptr holds {G}")
-        slots = np.zeros(max(G, 1), np.int64)
-        have, total = ptr.cpu().tolist(), 0
-        for g, i in enumerate(gi):
-            if i not in self._slot:
-                raise KeyError(i)
-            slots[g], n, ncol = self._slot[i]
-            if have[g + 1] - have[g] != n:
-                raise RuntimeError(f"rwr_sampler cache: graph {g} of the batch has {have[g + 1] - have[g]} vertices, "
-                                   f"the graph added in its place has {n}")
-            total += ncol
-        if edge_index is not None and edge_index.size(1) != total:
-            raise RuntimeError(f"rwr_sampler cache: the batch has {edge_index.size(1)} columns, the added graphs have {total}")
+        gi, G = self._graphs_of(graph_idx, ptr)
+        have = ptr.cpu().tolist()
+        slots = self._slots_of(gi, have, edge_index)
         if seeds is None:
             for g, i in enumerate(gi):
                 if i in self.failed:
@@ -246,7 +150,8 @@ class GraphCache:
         device, on torch's current stream.  Before any device work: KeyError for an index never added, ValueError if graph_idx and
         ptr disagree in length, if the device is not the cache's, if streams is neither value and for edge_index=None without
         check=False, RuntimeError for a wrong vertex count or column count and for a failed graph.  With check, after the device
-        work: RuntimeError "graph g of the batch differs from the graph added in its place", g the smallest such."""
+        work: RuntimeError "graph g of the batch differs from the graph added in its
+        place", g the smallest such."""
         return self._job(graph_idx, ptr, edge_index, m_per_graph, mode, seed, None, p_restart, streams, check, device)[0]
 
     def sample_graphs(self, graph_idx, ptr, edge_index, m_per_graph, seeds, mode="sample", p_restart=0.2, *, streams="graph", check=True,
@@ -259,6 +164,4 @@ class GraphCache:
     def info(self):
         """graphs (indices held), vertices (entries of the row-start array: vertices plus one per add), half_edges, bytes of the
         device storage and generations (allocations so far); what replaced graphs held stays counted until close"""
-        v = [C.c_int64() for _ in range(5)]
-        _check(lib.ugs_rwr_cache_info(self._handle(), *[C.byref(x) for x in v]))
-        return {"graphs": len(self._slot), "vertices": v[1].value, "half_edges": v[2].value, "bytes": v[3].value, "generations": v[4].value}
+        return super().info()

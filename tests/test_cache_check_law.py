@@ -51,7 +51,7 @@ def test_model_constants_and_lines_are_the_kernels():
     # the batch's columns of a cached call go up for the check alone
     with open(os.path.join(CSRC, "ugs_graph_cache.cpp")) as f:
         assert "const int64_t Ec = run_check ? E : 0;" in f.read()
-    with open(os.path.join(CSRC, "ugs_side_rwr.cpp")) as f:
+    with open(os.path.join(CSRC, "ugs_rwr_cache.cpp")) as f:
         assert "const int64_t Ec = checked ? E : 0;" in f.read()
 
 

@@ -115,8 +115,10 @@ def test_census_constants_are_the_kernels():
     # the census restates these; if the kernel's move, this fails and the inputs have to be chosen again
     with open(os.path.join(CSRC, "ugs_rwr.hip")) as f:
         hip = f.read()
-    with open(os.path.join(CSRC, "ugs_side_rwr.cpp")) as f:
-        host = f.read()
+    hosts = []
+    for name in ("ugs_side_rwr.cpp", "ugs_rwr_cache.cpp"):          # rwr_begin and the cached begin
+        with open(os.path.join(CSRC, name)) as f:
+            hosts.append(f.read())
     const = lambda name: int(re.search(r"constexpr \w+ %s = (\d+);" % name, hip).group(1))
     assert const("RWR_BLOCK") == R.RWR_BLOCK and const("SPEC_CAP") == R.SPEC_CAP and const("RWR_LDS_INTS") == R.RWR_LDS_INTS
     assert "constexpr int RWR_WMAX = %d * RWR_BLOCK;" % R.SPEC_MAX in hip
@@ -126,7 +128,8 @@ def test_census_constants_are_the_kernels():
     assert "while (s < c.m && cc < base + (uint64_t)W)" in hip and "if (left <= n) {" in hip
     assert [int(x) for x in re.findall(r"launch_walks<(\d+)>\(c, s\);", hip)] == list(R.KM_WIDTHS)
     assert [int(x) for x in re.findall(r"hipLaunchKernelGGL\(\(rwr_fill<(\d+)>\)", hip)] == list(R.KM_WIDTHS)
-    assert "c.spec = (int32_t)std::min<int64_t>(%d, std::max<int64_t>(1, ((int64_t)m_per_graph * 16 + 255) / 256));" % R.SPEC_MAX in host
+    for host in hosts:
+        assert "c.spec = (int32_t)std::min<int64_t>(%d, std::max<int64_t>(1, ((int64_t)m_per_graph * 16 + 255) / 256));" % R.SPEC_MAX in host
     assert [R.spec_window(m) for m in (0, 1, 16, 17, 32, 33, 48, 49, 2100)] == \
         [(1, 256), (1, 256), (1, 256), (2, 512), (2, 512), (3, 768), (3, 768), (4, 1024), (4, 1024)]
 

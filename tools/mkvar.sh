@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 HERE=$ROOT/ss-gnn_amd/csrc
 W=/tmp/vb/$NAME; mkdir -p $W $ROOT/ab; rm -f $W/*.o
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -x hip"
-HOST="ugs_host ugs_jobs ugs_side_eps ugs_side_uniform ugs_side_rwr ugs_graph_cache ugs_eps_cache"     # the host translation units (ugs_host_internal.h)
+HOST="ugs_host ugs_jobs ugs_side_eps ugs_side_uniform ugs_side_rwr ugs_cache_common ugs_rwr_cache ugs_graph_cache ugs_eps_cache"     # the host translation units (ugs_host_internal.h)
 /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-sched-strategy=${SCHED:-max-ilp} "$@" -I$HERE -c ${KSRC:-$HERE/ugs_kernels.hip} -o $W/ugs_kernels.o &
 for f in $HOST; do /opt/rocm/bin/hipcc $FL "$@" -c $HERE/$f.cpp -o $W/$f.o & done
 wait
