@@ -875,6 +875,41 @@ int ugs_wl_hash_labeled(const int64_t *d_nodes, const int64_t *d_edge_index, int
 int ugs_wl_lookup(const uint64_t *d_digest, const int32_t *d_status, int64_t rows, const uint64_t *d_keys, const int64_t *d_ids,
                   int64_t vocab_size, int64_t unknown_id, int64_t *d_ids_out);
 
+/* ---- ugs_sampler.rows.unique_rows: the repeated subgraphs of a sampler's output merged per graph, on the device -----------------
+ * The inputs are the five tensors of any sampler here (or of PresampleCache.load): nodes [R, k], edge_index [2, Es] with rows
+ * `in_stride` apart, edge_ptr [R + 1], sample_ptr [G + 1], edge_src [Es] (or NULL: then edge_src_u is not written), and the batch's
+ * ptr [G + 1].  All pointers are DEVICE pointers.  THE LAW:
+ *   1. Rows sample_ptr[g] .. sample_ptr[g+1]-1 belong to graph g.  The KEY of a row is its k entries in order (by = 0, "sequence")
+ *      or sorted ascending (by = 1, "set").  An entry -1 is a value like any other: the all -1 placeholder rows of one graph merge.
+ *   2. Row r is KEPT iff no row r' < r of the same graph has the same key.  Rows of different graphs never merge.
+ *   3. The kept rows keep their relative order and are copied unchanged: their nodes row as it stands (not sorted), their span
+ *      edge_ptr[r] .. edge_ptr[r+1]-1 of both rows of edge_index and of edge_src (the values untouched: every sampling mode works).
+ *      edge_ptr_u [U + 1] and sample_ptr_u [G + 1] are the new prefix sums; a graph without rows keeps an empty span.
+ *   4. count[u] is the number of original rows whose key equals kept row u's; inverse[r] is the position in the result of the kept
+ *      row with r's key.  Hence inverse of a kept row is its own new position, count sums to R, and nodes_u[inverse] has the keys
+ *      of nodes.
+ *   5. The result does not depend on the launch shape, and repeated calls are bit-identical.
+ * Keys are exact, not hashes: an entry v of graph g is coded as v - ptr[g] + 1 (0 for -1) in b = min(31, floor(128 / k)) bits of
+ * one 128-bit word.  Limits: 1 <= k <= 32; ptr[g+1] - ptr[g] + 1 <= 2^b for every graph with rows; at most 4096 rows per graph;
+ * R < 2^31, G < 2^31.
+ * begin checks on the device, before anything is indexed by them: sample_ptr and edge_ptr start at 0, do not decrease and end at R
+ * and at num_edges (Es); ptr does not decrease; every graph with rows is within the limits; every entry is -1 or inside
+ * [ptr[g], ptr[g+1]).  A call that fails one of these returns UGS_E_BAD_ARG (UGS_E_UNSUPPORTED for a limit) with a message that
+ * names the first offending index, graph or row, makes no job and leaves the library as it was.  Otherwise begin reports U and Eu
+ * (one read-back) and the caller allocates nodes_u [U, k], edge_index_u [2, ld >= Eu], edge_ptr_u [U + 1], sample_ptr_u [G + 1],
+ * edge_src_u [Eu], count [U], inverse [R]; finish writes them on the job's stream, waits for it as every finish does (the scratch
+ * goes back to the pool) and frees the job.  The inputs must stay alive and unchanged from begin to finish;
+ * ugs_job_cancel(job) gives the job up instead.  The scratch comes from the library's pool.
+ * ugs_rows_last_launch: the dedup kernel forms of the calling thread's last begin -- "wave" (graphs of at most 64 rows, one wave
+ * each), "workgroup" (65..4096 rows, one workgroup each, sorted in LDS), "wave+workgroup", or "none". */
+int ugs_rows_unique_begin(const int64_t *d_nodes, int k, int64_t num_rows, const int64_t *d_edge_ptr, int64_t num_edges,
+                          const int64_t *d_sample_ptr, int64_t num_graphs, const int64_t *d_ptr, int by, ugs_job **job_out,
+                          int64_t *unique_rows_out, int64_t *unique_edges_out);
+int ugs_rows_unique_finish(ugs_job *job, int64_t *d_nodes_u, const int64_t *d_edge_index_in, int64_t in_stride, const int64_t *d_edge_src_in,
+                           int64_t *d_edge_index_u, int64_t ld, int64_t *d_edge_ptr_u, int64_t *d_sample_ptr_u, int64_t *d_edge_src_u,
+                           int64_t *d_count, int64_t *d_inverse);
+int ugs_rows_last_launch(char *buf, int buf_len);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

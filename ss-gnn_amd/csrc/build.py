@@ -10,7 +10,8 @@ OUT = os.path.join(HERE, "libugs_mi355.so")
 SRCS = [os.path.join(HERE, "ugs_kernels.hip"), os.path.join(HERE, "ugs_eps.hip"), os.path.join(HERE, "ugs_uniform.hip"), os.path.join(HERE, "ugs_rwr.hip"), os.path.join(HERE, "ugs_preproc.hip"), os.path.join(HERE, "ugs_collate.hip"), os.path.join(HERE, "ugs_batch.hip"), os.path.join(HERE, "ugs_host.cpp"),
         os.path.join(HERE, "ugs_jobs.cpp"), os.path.join(HERE, "ugs_side_eps.cpp"), os.path.join(HERE, "ugs_side_uniform.cpp"), os.path.join(HERE, "ugs_side_rwr.cpp"), os.path.join(HERE, "ugs_cache_common.cpp"), os.path.join(HERE, "ugs_rwr_cache.cpp"),
         os.path.join(HERE, "ugs_graph_cache.cpp"), os.path.join(HERE, "ugs_store.hip"), os.path.join(HERE, "ugs_eps_cache.cpp"),
-        os.path.join(HERE, "ugs_apx.cpp"), os.path.join(HERE, "ugs_apx_gpu.hip"), os.path.join(HERE, "ugs_wl.hip")]
+        os.path.join(HERE, "ugs_apx.cpp"), os.path.join(HERE, "ugs_apx_gpu.hip"), os.path.join(HERE, "ugs_wl.hip"),
+        os.path.join(HERE, "ugs_rows.hip"), os.path.join(HERE, "ugs_rows.cpp")]
 HDRS = [os.path.join(HERE, "ugs_device.h"), os.path.join(HERE, "ugs_host_internal.h"), os.path.join(HERE, "ugs_apx_common.h"), os.path.join(HERE, "..", "..", "include", "ugs_mi355.h")]
 DEPS = SRCS + HDRS
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -22,7 +23,9 @@ def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
 
     def compile_one(src):
-        obj = os.path.splitext(src)[0] + ".o"
+        stem = os.path.splitext(src)[0]
+        twins = sum(os.path.splitext(s)[0] == stem for s in SRCS) > 1       # ugs_rows.hip beside ugs_rows.cpp: one object each
+        obj = (src if twins else stem) + ".o"
         if not force and os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in [src, __file__] + HDRS):
             return obj                                       # object is newer than its source, the headers and this recipe
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",

@@ -444,6 +444,36 @@ struct UgsEpsBuild {
 };
 hipError_t ugs_eps_build(const UgsEpsBuild &b, hipStream_t s);
 
+// ---- ugs_sampler.rows.unique_rows (ugs_rows.hip; host: ugs_rows.cpp; law: include/ugs_mi355.h at ugs_rows_unique_begin) ----
+// One call's arrays.  The inputs are the caller's; everything else is a piece of the job's blob.  A status word holds the lowest
+// offending index of its kind, UGS_ROWS_NONE where there is none; a kernel behind the check runs only while words 0 and 1 say so,
+// so nothing is ever indexed by a pointer-array value that the check has not passed.
+#define UGS_ROWS_NONE 0x7f7f7f7f7f7f7f7fll
+#define UGS_ROWS_MAX_PER_GRAPH 4096
+enum { UGS_ROWS_ST_PTR = 0 /* index into sample_ptr (code 0), edge_ptr (1) or ptr (2): 4 index + code */, UGS_ROWS_ST_GRAPH = 1 /* graph over a limit */,
+       UGS_ROWS_ST_ENTRY = 2 /* row with an entry outside its graph */, UGS_ROWS_ST_WORDS = 4 };
+struct UgsRowsBack { int64_t U, Eu, st[UGS_ROWS_ST_WORDS - 1], big, small; };   // what begin reads back: totals, status, graphs in the workgroup and the wave form
+struct UgsRowsCall {
+    const int64_t *nodes, *edge_ptr, *sample_ptr, *ptr;      // inputs: [R, k], [R + 1], [G + 1], [G + 1]
+    int64_t R, G, Es;
+    int32_t k, by /* 0 sequence, 1 set */, bits;
+    int64_t *status;                                         // [UGS_ROWS_ST_WORDS]
+    uint4 *keys;                                             // [R]
+    int32_t *rowg, *rep, *lrank, *cnt;                       // [R]: graph of the row; representative (a row); rank among its graph's kept rows and
+                                                             //      run length (kept rows only)
+    int64_t *eoff;                                           // [R]: edge entries of the kept rows before it in its graph (kept rows only)
+    int64_t *ug, *eg;                                        // [G]: kept rows and their edge entries per graph
+    int64_t *ubase, *ebase;                                  // [G + 1]: their exclusive scans
+    int32_t *big, *nbig;                                     // [3][G] graphs of 65..256, ..1024, ..4096 rows, in any order; their numbers [3] and the number of graphs of 1..64 rows
+    UgsRowsBack *back;
+};
+struct UgsRowsOut {
+    const int64_t *edge_index_in; int64_t in_stride; const int64_t *edge_src_in;
+    int64_t *nodes_u, *edge_index_u, *edge_ptr_u, *sample_ptr_u, *edge_src_u, *count, *inverse; int64_t ld;
+};
+hipError_t ugs_rows_dedup(const UgsRowsCall &c, hipStream_t s);                          // check, keys, both dedup forms, scan, `back`
+hipError_t ugs_rows_compact(const UgsRowsCall &c, const UgsRowsOut &o, int64_t U, int64_t Eu, hipStream_t s);
+
 // ---- device-side preprocessing stages (ugs_preproc.hip) ----
 struct UgsDevPre;
 size_t ugs_devpre_bytes(int64_t n, int64_t E);

@@ -205,7 +205,7 @@ int plan_walk_locked(ugs_plan *plan, const TierChoice &tc, int m_per_graph, int 
 // ---------------------------------------------------------------------------------------------------------------
 // What fills a side sampler's edge outputs at finish: edge_index [2, ld] and edge_src [ld] on the device, on the job's stream.
 using JobFill = std::function<hipError_t(int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s)>;
-enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR, UGS_JOB_UNIFORM_ENUM, UGS_JOB_UNIFORM_POP };
+enum { UGS_JOB_UGS = 0, UGS_JOB_EPS, UGS_JOB_UNIFORM, UGS_JOB_RWR, UGS_JOB_UNIFORM_ENUM, UGS_JOB_UNIFORM_POP, UGS_JOB_ROWS };
 
 }  // namespace ugs_host
 
@@ -233,6 +233,10 @@ struct ugs_job {
     // a job whose begin reports its own row count (ugs_uniform_enumerate_begin): its sample_ptr [G + 1], rows = sample_ptr[G];
     // empty: rows = G m and sample_ptr = g m
     std::vector<int64_t> sample_ptr;
+    // ugs_rows_unique_begin (ugs_rows.cpp): no sampler's job -- the call's arrays (UgsRowsCall over `blob` and the caller's inputs) and
+    // the number of kept rows; `rows` is R and `total` is Eu
+    std::shared_ptr<void> rows_call;
+    int64_t rows_kept = 0;
 };
 
 namespace ugs_host __attribute__((visibility("hidden"))) {

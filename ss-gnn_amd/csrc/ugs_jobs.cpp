@@ -246,6 +246,7 @@ int ugs_sample_begin(int64_t handle, int m_per_graph, int k, int edge_mode, int6
 
 int ugs_sample_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *edge_src, int dst_is_device) {
     if (!job) return fail(UGS_E_BAD_ARG, "job is null");
+    if (job->kind == UGS_JOB_ROWS) return fail(UGS_E_BAD_ARG, "a unique_rows job is no sampler's: ugs_rows_unique_finish completes it");
     return finish_common(job, nodes, edge_index, edge_ptr, nullptr, edge_src, dst_is_device);
 }
 
@@ -312,6 +313,7 @@ int ugs_sample_graphs_begin(const int64_t *edge_index, int64_t row_stride, int64
 int ugs_sample_batch_finish(ugs_job *job, int64_t *nodes, int64_t *edge_index, int64_t *edge_ptr, int64_t *sample_ptr,
                             int64_t *edge_src_global, int dst_is_device) {
     if (!job) return fail(UGS_E_BAD_ARG, "job is null");
+    if (job->kind == UGS_JOB_ROWS) return fail(UGS_E_BAD_ARG, "a unique_rows job is no sampler's: ugs_rows_unique_finish completes it");
     return finish_common(job, nodes, edge_index, edge_ptr, sample_ptr, edge_src_global, dst_is_device);
 }
 

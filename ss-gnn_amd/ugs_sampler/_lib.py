@@ -135,6 +135,9 @@ def _load():
         "ugs_wl_hash_labeled": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp],
         "ugs_wl_feature_labels": [vp, C.c_int64, C.c_int64, C.c_int64, vp],
         "ugs_wl_lookup": [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp],
+        "ugs_rows_unique_begin": [vp, C.c_int, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int, C.POINTER(vp), i64p, i64p],
+        "ugs_rows_unique_finish": [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp],
+        "ugs_rows_last_launch": [C.c_char_p, C.c_int],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)          # AttributeError here = the library does not export what the header declares
