@@ -910,6 +910,42 @@ int ugs_rows_unique_finish(ugs_job *job, int64_t *d_nodes_u, const int64_t *d_ed
                            int64_t *d_count, int64_t *d_inverse);
 int ugs_rows_last_launch(char *buf, int buf_len);
 
+/* ---- ugs_sampler.graphlets: the exact isomorphism class of every sampled subgraph (ugs_graphlet.hip, ugs_graphlet.cpp) -----------
+ *      What the WL digest above stands in for, computed itself: a graph on n <= 8 vertices is 28 adjacency bits, and there are
+ *      1, 2, 4, 11, 34, 156, 1044, 12346 graphs on 1 .. 8 vertices, so the complete vocabulary is a fixed table.
+ *      The law, for row i of nodes [rows, k] (any values) with the entries [edge_ptr[i], edge_ptr[i+1]) of edge_index:
+ *        1. items 1, 3 and 4 of ugs_wl_hash's law: n = number of entries >= 0 in the row, the graph has the vertices 0 .. n-1;
+ *           n = 0: status 1; an endpoint outside [0, n), or an edge_ptr range that is no range of [0, num_cols]: status 2 (nothing
+ *           of such a range is read).  Other rows are not disturbed;
+ *        2. the graph is SIMPLE: every entry contributes the undirected pair {u, v}, duplicates and reversed copies collapse, and a
+ *           loop (u, u) is dropped -- the one difference from WL's reading of the same row;
+ *        3. pair (i, j), i < j, has bit position b(i, j) = j (j - 1) / 2 + i: the adjacency among the first n - 1 vertices is the
+ *           low bits, the last vertex's neighbours are the top n - 1;
+ *        4. for a permutation p of the n vertices, code(p) = sum of A[p(i), p(j)] << b(i, j);
+ *        5. the CANONICAL CODE is the minimum of code(p) over all n! permutations;
+ *        6. the row's KEY is (n << 28) | canonical code, as int64; -1 where status != 0;
+ *        7. the CLASS ID is the rank of the key in the ascending list of all keys with 1 <= n' <= 8.  It does not depend on k: the
+ *           ids of graphs on at most k vertices fill [0, C_k), C_k = 1, 3, 7, 18, 52, 208, 1252, 13598 for k = 1 .. 8.  A row with
+ *           status != 0 gets the id C_k (the len(vocab) convention of the WL vocabulary).
+ *      1 <= k <= 8, otherwise UGS_E_UNSUPPORTED.
+ * ugs_graphlet_canon: all pointers are DEVICE pointers.  key_out [rows] int64, status_out [rows] int32.  d_table and d_class_out may
+ *      both be NULL; otherwise d_table [table_len] is the ascending key table for n <= k (ugs_graphlet_table for n = 1 .. k, one
+ *      after the other) and class_out [rows] receives the ids, table_len for a row with status != 0, in the same launch.  One launch
+ *      on the calling thread's stream (ugs_set_stream), no allocation, no synchronisation with the host; rows = 0 is a no-op.
+ * ugs_graphlet_table: HOST function, no device work.  *count_out = the number of graphs on exactly n vertices; if capacity >= it,
+ *      keys_out holds their keys, ascending.  Built once per process and per n, under a mutex, by extending every (n-1)-class with
+ *      a last vertex over all 2^(n-1) neighbour sets and canonicalising; item 3's layout makes that complete.
+ * ugs_graphlet_canon_code: HOST function, the canonicaliser the table is built with and the same search the kernel runs:
+ *      *out = the canonical code of the graph whose adjacency bits are `code` (bits above n (n - 1) / 2: UGS_E_BAD_ARG).
+ * ugs_graphlet_search_stats: HOST function, the cost of that search for `code`: the complete codes it compares (1 for a graph
+ *      without symmetry, 48 for the cube) and the search nodes it evaluates (n - 1 at the least). */
+int ugs_graphlet_canon(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                       const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, int64_t table_len,
+                       int64_t *d_key_out, int32_t *d_status_out, int64_t *d_class_out);
+int ugs_graphlet_table(int n, int64_t *keys_out, int64_t capacity, int64_t *count_out);
+int ugs_graphlet_canon_code(uint32_t code, int n, uint32_t *out);
+int ugs_graphlet_search_stats(uint32_t code, int n, uint32_t *leaves_out, uint32_t *nodes_out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

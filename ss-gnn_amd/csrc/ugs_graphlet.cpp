@@ -1,0 +1,81 @@
+// ugs_graphlet.cpp -- host side of ugs_sampler.graphlets (C ABI: ugs_graphlet_canon_code / ugs_graphlet_table in
+// include/ugs_mi355.h, which states the law; kernel: ugs_graphlet.hip; the search both share: ugs_graphlet_common.h).
+// No device work here: the table of all graphs on n vertices is built on the host, once per process and per n.
+#include "ugs_host_internal.h"
+#include "ugs_graphlet_common.h"
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+using namespace ugs_host;
+
+namespace {
+
+struct HostStack {
+    uint64_t w[UGS_GL_KMAX];
+    void put(int level, uint64_t v) { w[level] = v; }
+    uint64_t get(int level) const { return w[level]; }
+};
+
+uint32_t canon_code(uint32_t code, int n, uint32_t *stats = nullptr) {
+    HostStack st;
+    return ugs_gl::canon(ugs_gl::adj_of_code(code, n), n, st, stats);
+}
+
+std::mutex g_table_mu;
+std::vector<uint32_t> g_codes[UGS_GL_KMAX + 1];       // [n]: canonical codes of all graphs on n vertices, ascending; empty = not built
+
+// Every graph on n vertices is a graph on n - 1 vertices plus a last vertex, and the last vertex's column is the top n - 1 bits: all
+// (n-1)-classes times all 2^(n-1) neighbour sets reach every n-class.  Called with the mutex held.
+const std::vector<uint32_t> &codes_of(int n) {
+    std::vector<uint32_t> &out = g_codes[n];
+    if (!out.empty()) return out;
+    if (n == 1) { out.push_back(0); return out; }
+    const std::vector<uint32_t> &below = codes_of(n - 1);
+    const int lo = ugs_gl::tri(n - 1);
+    std::vector<uint32_t> all;
+    all.reserve(below.size() << (n - 1));
+    for (uint32_t c : below)
+        for (uint32_t s = 0; s < (1u << (n - 1)); ++s) all.push_back(canon_code(c | (s << lo), n));
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    out.swap(all);
+    return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ugs_graphlet_canon_code(uint32_t code, int n, uint32_t *out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_canon_code: 1 <= n <= 8");
+    if (!out) return fail(UGS_E_BAD_ARG, "graphlet_canon_code: null output pointer");
+    if ((uint64_t)code >> ugs_gl::tri(n)) return fail(UGS_E_BAD_ARG, "graphlet_canon_code: the code has bits above n(n-1)/2");
+    *out = canon_code(code, n);
+    return UGS_OK;
+}
+
+int ugs_graphlet_search_stats(uint32_t code, int n, uint32_t *leaves_out, uint32_t *nodes_out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_search_stats: 1 <= n <= 8");
+    if (!leaves_out || !nodes_out) return fail(UGS_E_BAD_ARG, "graphlet_search_stats: null output pointer");
+    if ((uint64_t)code >> ugs_gl::tri(n)) return fail(UGS_E_BAD_ARG, "graphlet_search_stats: the code has bits above n(n-1)/2");
+    uint32_t stats[2] = {0, 0};
+    canon_code(code, n, stats);
+    *leaves_out = stats[0];
+    *nodes_out = stats[1];
+    return UGS_OK;
+}
+
+int ugs_graphlet_table(int n, int64_t *keys_out, int64_t capacity, int64_t *count_out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_table: 1 <= n <= 8");
+    if (!count_out || capacity < 0 || (capacity > 0 && !keys_out)) return fail(UGS_E_BAD_ARG, "graphlet_table: count_out, and keys_out for capacity > 0, are needed");
+    std::lock_guard<std::mutex> lock(g_table_mu);
+    const std::vector<uint32_t> &codes = codes_of(n);
+    *count_out = (int64_t)codes.size();
+    if (capacity >= (int64_t)codes.size())
+        for (size_t i = 0; i < codes.size(); ++i) keys_out[i] = ((int64_t)n << 28) | (int64_t)codes[i];
+    return UGS_OK;
+}
+
+}  // extern "C"

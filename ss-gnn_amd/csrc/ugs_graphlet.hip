@@ -1,0 +1,136 @@
+// ugs_graphlet.hip -- exact graphlet keys and class ids of sampled rows, on the device.  The law is stated at
+// ugs_graphlet_canon in include/ugs_mi355.h; the search is ugs_graphlet_common.h, the same code the host table is built with.
+//
+// ugs_graphlet_canon_kernel: eight lanes per row (one per vertex), eight rows per wave64; groups never span a wave.
+//   row     lane u reads entry u of the row (k = 8: a wave reads 512 consecutive bytes); n is the popcount of the group's ballot.  The
+//           lanes stride over the row's edge entries and OR them into 64-bit words (byte v = neighbour mask of v) that three
+//           xor-shuffles fold: range check, deduplication, reversed copies and dropped loops at once;
+//   search  every lane evaluates the root of ugs_gl's search (eight candidates, one cell).  Lane u then owns the subtree below the
+//           first pick u, if u is one of the tied candidates the twin rule keeps, and runs ugs_gl::search there: refinement by
+//           adjacency to the vertices already placed, twins in fixed order, ties permuted, bounded by the bits already fixed.  Three
+//           xor-shuffles take the minimum over the group.  The subtrees of one row run side by side and do not share their bounds: a
+//           lane may follow a branch that a sequential search would have cut, but never longer than its own subtree.  The per-level
+//           cell words live in LDS, [level][thread]: registers cannot be indexed by the level and the layout puts a wave's accesses
+//           on consecutive addresses (0 bytes of scratch);
+//   id      lane 0 of the group: binary search of the key in the ascending table (at most 13 598 entries: 14 probes, the table
+//           stays in L2).
+// There is one path.  What the split over first picks buys, and what the most symmetric rows cost: DESIGN.md section 19.
+#include "ugs_device.h"
+#include "ugs_graphlet_common.h"
+#include "../../include/ugs_mi355.h"
+
+#define UGS_GL_BLOCK 256
+#define UGS_GL_LANES 8             // lanes per row: one per vertex, UGS_GL_KMAX
+
+namespace {
+
+struct GlArgs {
+    const int64_t *nodes;        // [rows, k]
+    const int64_t *edge_index;   // [2, num_cols], row stride `stride`
+    int64_t stride, num_cols;
+    const int64_t *edge_ptr;     // [rows + 1]
+    int64_t rows;
+    int k;
+    const int64_t *table;        // ascending keys of all graphs on at most k vertices, or NULL
+    int64_t table_len;
+    int64_t *key;                // [rows]
+    int32_t *status;             // [rows]
+    int64_t *cls;                // [rows], or NULL
+};
+
+struct LdsStack {
+    uint64_t *base;              // this thread's column of [UGS_GL_KMAX][UGS_GL_BLOCK]
+    __device__ __forceinline__ void put(int level, uint64_t v) { base[level * UGS_GL_BLOCK] = v; }
+    __device__ __forceinline__ uint64_t get(int level) const { return base[level * UGS_GL_BLOCK]; }
+};
+
+__global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_canon_kernel(GlArgs a) {
+    __shared__ uint64_t cells_sh[UGS_GL_KMAX * UGS_GL_BLOCK];
+    const int tid = (int)threadIdx.x;
+    const int u = tid & (UGS_GL_LANES - 1);                      // vertex, and first pick, of this lane
+    const int64_t row = (int64_t)blockIdx.x * (UGS_GL_BLOCK / UGS_GL_LANES) + (tid >> 3);
+    if (row >= a.rows) return;                                   // whole groups leave; no barrier below: a lane's LDS column is its own
+
+    const int64_t id = u < a.k ? a.nodes[row * a.k + u] : -1;
+    const int gshift = (tid & 63) & ~(UGS_GL_LANES - 1);         // the group's first lane inside the wave
+    const int n = __popc((unsigned)(__ballot(id >= 0) >> gshift) & 0xffu);
+    int bad = 0;
+    uint64_t adj = 0;
+    if (n > 0) {
+        const int64_t lo = a.edge_ptr[row], hi = a.edge_ptr[row + 1];
+        if (lo < 0 || hi < lo || hi > a.num_cols) {
+            bad = 1;                                             // not a range of edge_index: nothing is read
+        } else {
+            for (int64_t e = lo + u; e < hi; e += UGS_GL_LANES) {
+                const int64_t x = a.edge_index[e], y = a.edge_index[a.stride + e];
+                if (x < 0 || x >= n || y < 0 || y >= n) bad = 1;
+                else if (x != y) adj |= (1ull << (8 * (int)x + (int)y)) | (1ull << (8 * (int)y + (int)x));
+            }
+        }
+    }
+    for (int d = 1; d < UGS_GL_LANES; d <<= 1) {                 // the group's lanes are all here: n and the row are theirs alike
+        adj |= __shfl_xor(adj, d);
+        bad |= __shfl_xor(bad, d);
+    }
+    const int status = n == 0 ? 1 : bad ? 2 : 0;
+    uint32_t code = 1u << 28;                                    // above every code
+    if (status == 0) {
+        if (n == 1) {
+            code = 0;
+        } else {
+            const uint64_t root = (1ull << n) - 1ull;            // one cell: nothing placed
+            uint32_t tied, col;
+            ugs_gl::eval_node(adj, root, tied, col);
+            if (n == 2) {
+                code = col;                                      // the root is the last level with a column
+            } else if ((tied >> u) & 1u) {
+                LdsStack st{cells_sh + tid};
+                code = ugs_gl::search(adj, ugs_gl::split_cells(adj, root, u), n - 2, col << ugs_gl::tri(n - 1), st);
+            }
+        }
+        for (int d = 1; d < UGS_GL_LANES; d <<= 1) code = min(code, (uint32_t)__shfl_xor((int)code, d));
+    }
+    if (u != 0) return;
+    const int64_t key = status == 0 ? ((int64_t)n << 28) | (int64_t)code : -1;
+    a.key[row] = key;
+    a.status[row] = status;
+    if (a.cls) {
+        int64_t cid = a.table_len;                               // the id of a refused row: len(vocab)
+        if (status == 0) {
+            int64_t lo_i = 0, hi_i = a.table_len;                // first table key >= key
+            while (lo_i < hi_i) {
+                const int64_t mid = lo_i + ((hi_i - lo_i) >> 1);
+                if (a.table[mid] < key) lo_i = mid + 1; else hi_i = mid;
+            }
+            if (lo_i < a.table_len && a.table[lo_i] == key) cid = lo_i;
+        }
+        a.cls[row] = cid;
+    }
+}
+
+}  // namespace
+
+extern "C" int ugs_graphlet_canon(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                                  const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, int64_t table_len,
+                                  int64_t *d_key_out, int32_t *d_status_out, int64_t *d_class_out) {
+    if (k < 1 || k > UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_canon: 1 <= k <= 8");
+    if (rows < 0 || num_cols < 0 || (num_cols > 0 && row_stride < num_cols))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_canon: rows >= 0, num_cols >= 0, row_stride >= num_cols");
+    if (table_len < 0 || (d_class_out && !d_table && table_len > 0)) return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_canon: a class output needs the key table");
+    if (rows == 0) return UGS_OK;
+    if (!d_nodes || !d_edge_ptr || !d_key_out || !d_status_out || (num_cols > 0 && !d_edge_index))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_canon: null pointer");
+    const int64_t per_block = UGS_GL_BLOCK / UGS_GL_LANES;
+    const int64_t blocks = (rows + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffll) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_canon: too many rows for one launch");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    GlArgs a{};
+    a.nodes = d_nodes; a.edge_index = d_edge_index; a.stride = row_stride; a.num_cols = num_cols; a.edge_ptr = d_edge_ptr;
+    a.rows = rows; a.k = k; a.table = d_table; a.table_len = d_table ? table_len : 0;
+    a.key = d_key_out; a.status = d_status_out; a.cls = d_class_out;
+    hipLaunchKernelGGL(ugs_graphlet_canon_kernel, dim3((unsigned)blocks), dim3(UGS_GL_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}

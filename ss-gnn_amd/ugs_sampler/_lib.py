@@ -138,6 +138,10 @@ def _load():
         "ugs_rows_unique_begin": [vp, C.c_int, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int, C.POINTER(vp), i64p, i64p],
         "ugs_rows_unique_finish": [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp],
         "ugs_rows_last_launch": [C.c_char_p, C.c_int],
+        "ugs_graphlet_canon": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, vp],
+        "ugs_graphlet_table": [C.c_int, vp, C.c_int64, i64p],
+        "ugs_graphlet_canon_code": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)],
+        "ugs_graphlet_search_stats": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)          # AttributeError here = the library does not export what the header declares

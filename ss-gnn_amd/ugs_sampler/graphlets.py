@@ -1,0 +1,190 @@
+"""Exact graphlet class ids of sampled subgraphs, computed on the GPU.
+
+`ugs_sampler.wl` reproduces the digest the reference's SS-GNN-WL model uses as a stand-in for a sample's isomorphism class.  For
+k <= 8 the class itself is small: a graph on n <= 8 vertices is 28 adjacency bits, and there are 1, 2, 4, 11, 34, 156, 1044 and
+12 346 graphs on 1 .. 8 vertices.  So the complete vocabulary is a fixed table -- no build pass over a dataset, no unknown id, the
+same ids for every dataset and every run -- and WL's merged classes (3 of the 112 connected graphs on 6 vertices, 17 of 853 on 7)
+stay apart:
+
+    vocab_size = graphlets.num_classes(k)                                        # the frozen embedding's size, 208 for k = 6
+    wl_ids = graphlets.class_ids(nodes, edge_index, edge_ptr)                    # every forward pass, one launch
+
+The law is stated at ugs_graphlet_canon in include/ugs_mi355.h.  A row's key is (n << 28) | canonical code, the canonical code being
+the smallest adjacency code over all n! orders of the row's vertices; its class id is the key's rank among all keys with n <= 8, so
+the id of a graph does not depend on k and the ids of a k-sampler fill [0, num_classes(k)).  Row status: 0 = classified; 1 = the row
+has no entry >= 0; 2 = an edge endpoint outside the row's vertices or an edge_ptr range outside the columns.  A row of status 1 or 2
+has key -1 and the id num_classes(k), the len(vocab) convention of `wl.WLVocab.ids`.  The graph is simple: loops are dropped, which
+is the one difference from WL's reading of the same row.  Limits: 1 <= k <= 8.
+
+With `uniform_sampler.enumerate_graphs` the ids give a graph's exact graphlet histogram:
+
+    nodes, edge_index, edge_ptr, sample_ptr, _, _ = uniform_sampler.enumerate_graphs(batch.edge_index, batch.ptr, k, device=dev)
+    hist = graphlets.histogram(graphlets.class_ids(nodes, edge_index, edge_ptr), sample_ptr, k)     # int64 [G, num_classes(k)]
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _select_device
+from ._lib import check, lib
+from .wl import _check_inputs, _placed
+
+__all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats"]
+
+KMAX = 8
+_NUM_CLASSES = (1, 3, 7, 18, 52, 208, 1252, 13598)     # graphs on at most k vertices, k = 1 .. 8
+_host_tables = {}                                       # n -> numpy int64 keys of the graphs on exactly n vertices
+_dev_tables = {}                                        # (device index, k) -> the table for n <= k on that GPU
+
+
+def _check_k(k):
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError("k must be an int")
+    if not 1 <= k <= KMAX:                              # the library states the limit
+        check(lib.ugs_graphlet_canon(None, None, 0, 0, None, 0, k, None, 0, None, None, None))
+
+
+def num_classes(k):
+    """The number of graphs on at most k vertices, 1 <= k <= 8: 1, 3, 7, 18, 52, 208, 1252, 13598.  The ids of `class_ids` on
+    [S, k] rows are below it, and it is the id of a row without a class."""
+    _check_k(k)
+    return _NUM_CLASSES[k - 1]
+
+
+def _table_n(n):
+    if n not in _host_tables:
+        count = C.c_int64(0)
+        check(lib.ugs_graphlet_table(n, None, 0, C.byref(count)))
+        keys = np.empty((count.value,), dtype=np.int64)
+        check(lib.ugs_graphlet_table(n, keys.ctypes.data, keys.size, C.byref(count)))
+        _host_tables[n] = keys
+    return _host_tables[n]
+
+
+def table(k):
+    """The keys of all graphs on at most k vertices, ascending: int64 [num_classes(k)] on the host; table(k)[id] is the key of
+    class `id`.  Built by the library on first use (all of k = 8 takes a fraction of a second) and kept."""
+    _check_k(k)
+    return torch.from_numpy(np.concatenate([_table_n(n) for n in range(1, k + 1)]))
+
+
+def _device_table(dev, k):
+    key = (dev.index, k)
+    if key not in _dev_tables:
+        _dev_tables[key] = table(k).to(dev)
+    return _dev_tables[key]
+
+
+def _canon_on_device(nodes, edge_index, edge_ptr, with_ids):
+    """(key int64 [S], status int32 [S], ids int64 [S] or None) on the tensors' GPU; the library's device and stream are selected."""
+    dev = nodes.device
+    S, k = nodes.shape
+    tab = _device_table(dev, k) if with_ids and 1 <= k <= KMAX else None
+    key = torch.empty((S,), dtype=torch.int64, device=dev)
+    status = torch.empty((S,), dtype=torch.int32, device=dev)
+    ids = torch.empty((S,), dtype=torch.int64, device=dev) if with_ids else None
+    nodes, edge_ptr = nodes.contiguous(), edge_ptr.contiguous()
+    E = edge_index.size(1)
+    if E > 0 and edge_index.stride(1) != 1:
+        edge_index = edge_index.contiguous()
+    stride = edge_index.stride(0) if E > 0 else 0
+    if S > 0 or not 1 <= k <= KMAX:                     # the library states the limit
+        check(lib.ugs_graphlet_canon(nodes.data_ptr(), edge_index.data_ptr() if E > 0 else None, stride, E, edge_ptr.data_ptr(), S, k,
+                                     tab.data_ptr() if tab is not None else None, tab.numel() if tab is not None else 0,
+                                     key.data_ptr(), status.data_ptr(), ids.data_ptr() if with_ids else None))
+    return key, status, ids
+
+
+def canonical(nodes_sampled, edge_index_sampled, edge_ptr, *, device=None):
+    """Key and status of every sampled subgraph: (key int64 [S], status int32 [S]).
+
+    The inputs are the first three outputs of any sampler's sample_batch / sample_graphs in mode "sample" (or of
+    PresampleCache.load, or of uniform_sampler.enumerate_graphs).  key[i] = (n << 28) | canonical code of row i, -1 where
+    status != 0; two rows have the same key exactly when their subgraphs are isomorphic.  Device tensors are used in place (a
+    strided edge_index too) and the results stay there, on torch's current stream; CPU tensors are copied to `device` (default: the
+    current GPU) and the results come back on the CPU.  One launch, no synchronisation with the host."""
+    _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, 0)
+    nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, device)
+    _select_device(dev, jobs=True)
+    key, status, _ = _canon_on_device(nodes, edge_index, eptr, False)
+    return (key.cpu(), status.cpu()) if back else (key, status)
+
+
+def class_ids(nodes_sampled, edge_index_sampled, edge_ptr, *, device=None):
+    """The graphlet class id of every sampled subgraph: int64 [S] with values in [0, num_classes(k)), and num_classes(k) for a row
+    of status 1 or 2 (module docstring).  What `wl.WLVocab.ids` answers with a vocabulary, without one: table(k)[id] is the row's
+    key.  Placement as `canonical`; the key table (at most 13 598 int64) is uploaded once per device and k.  One launch."""
+    _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, 0)
+    nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, device)
+    _select_device(dev, jobs=True)
+    _, _, ids = _canon_on_device(nodes, edge_index, eptr, True)
+    return ids.cpu() if back else ids
+
+
+def decode(key):
+    """(n, [(i, j), ...]) of a key: the vertex count and the edges i < j of the class's canonical representative."""
+    key = int(key)
+    n = key >> 28
+    if not 1 <= n <= KMAX or (key & ((1 << 28) - 1)) >> (n * (n - 1) // 2):
+        raise ValueError(f"{key} is no graphlet key")
+    return n, [(i, j) for j in range(1, n) for i in range(j) if key >> (j * (j - 1) // 2 + i) & 1]
+
+
+def is_connected(keys):
+    """bool tensor, on the device of `keys` (int64, any shape): whether the graph of each key is connected; False for -1.
+    Plain torch bit operations, no synchronisation."""
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+        raise TypeError("keys must be an int64 torch.Tensor")
+    ok = keys >= 0
+    k = torch.where(ok, keys, torch.zeros_like(keys))
+    n = k >> 28
+    nb = [torch.zeros_like(k) for _ in range(KMAX)]     # neighbour masks
+    for j in range(1, KMAX):
+        for i in range(j):
+            bit = (k >> (j * (j - 1) // 2 + i)) & 1
+            nb[i] = nb[i] | (bit << j)
+            nb[j] = nb[j] | (bit << i)
+    reach = torch.ones_like(k)
+    for _ in range(KMAX - 1):
+        step = reach
+        for v in range(KMAX):
+            step = step | (nb[v] * ((reach >> v) & 1))
+        reach = step
+    return ok & (n >= 1) & (reach == (torch.ones_like(k) << n) - 1)
+
+
+def histogram(class_ids, sample_ptr, k):
+    """The graphlet counts of every graph: int64 [G, num_classes(k)], row g counting the ids of rows sample_ptr[g] ..
+    sample_ptr[g+1]-1.  Rows with the id num_classes(k) are not counted.  Over `uniform_sampler.enumerate_graphs` rows this is
+    the graph's exact k-graphlet histogram.  A torch scatter on the tensors' device, no synchronisation."""
+    for t, name in ((class_ids, "class_ids"), (sample_ptr, "sample_ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64, got {t.dtype}")
+    if class_ids.dim() != 1:
+        raise ValueError("class_ids must have shape [S]")
+    if sample_ptr.dim() != 1 or sample_ptr.numel() < 1:
+        raise ValueError("sample_ptr must have shape [G + 1]")
+    if class_ids.device != sample_ptr.device:
+        raise ValueError("class_ids and sample_ptr must be on one device")
+    classes = num_classes(k)
+    G, S = sample_ptr.numel() - 1, class_ids.numel()
+    graph = torch.searchsorted(sample_ptr[1:].contiguous(), torch.arange(S, dtype=torch.int64, device=class_ids.device), right=True)
+    counted = (class_ids >= 0) & (class_ids < classes) & (graph < G)
+    slot = torch.where(counted, graph * classes + class_ids, torch.zeros_like(class_ids))
+    out = torch.zeros((G * classes,), dtype=torch.int64, device=class_ids.device)
+    out.scatter_add_(0, slot, counted.to(torch.int64))
+    return out.view(G, classes)
+
+
+def search_stats(key_or_code, n=None):
+    """(leaves, nodes): the complete codes the canonical search compares for a graph and the search nodes it evaluates, its measures
+    of cost; (1, n - 1) for a graph without symmetry.  Takes a key, or a raw adjacency code with n.  Host only."""
+    code = int(key_or_code)
+    if n is None:
+        n, code = code >> 28, code & ((1 << 28) - 1)
+    leaves, nodes = C.c_uint32(0), C.c_uint32(0)
+    check(lib.ugs_graphlet_search_stats(code, n, C.byref(leaves), C.byref(nodes)))
+    return leaves.value, nodes.value
