@@ -167,6 +167,25 @@ def test_statuses_do_not_disturb_neighbouring_rows():
     assert [keys[r] for r in (0, 3, 4)] == [whole[r] for r in (0, 3, 4)]
 
 
+def test_endpoints_that_only_a_32_bit_cast_would_put_in_range():
+    """2^32, 2^32 + 1 and -2^32 read as 0, 1 and 0 once narrowed to 32 bits, and 2^63 - 1 as -1: a kernel that narrows an endpoint
+    before it checks it would take three of these rows for good ones.  The law compares the 64-bit value: status 2, key -1, and
+    the rows between keep their keys."""
+    rng = random.Random(32)
+    good = [random_entry(rng, 5) for _ in range(5)]
+    wide = [1 << 32, (1 << 32) + 1, -(1 << 32), (1 << 63) - 1]
+    bad = [(5, [(0, 1), (x, 2), (3, 4)]) if r % 2 == 0 else (5, [(1, 2), (4, x)]) for r, x in enumerate(wide)]
+    entries = [good[0], bad[0], good[1], bad[1], good[2], bad[2], good[3], bad[3], good[4]]
+    arrays = pack(entries, 5)
+    assert sorted(int(x) for x in arrays[1].ravel() if not 0 <= x < 5) == sorted(wide)
+    assert [int(np.int64(x).astype(np.int32)) for x in wide] == [0, 1, 0, -1]
+    keys, stats = assert_law(arrays, "wide endpoints")
+    assert_law(arrays, "wide endpoints, strided", strided=True)
+    assert stats == [0, 2, 0, 2, 0, 2, 0, 2, 0] and [keys[r] for r in (1, 3, 5, 7)] == [-1] * 4
+    alone, _ = law.rows_law(*pack(good, 5))
+    assert [k for k in keys if k >= 0] == alone
+
+
 def test_no_rows_and_no_edge_entries():
     from ugs_sampler import graphlets
     nodes, ei, ep = on_gpu(pack([(6, [])], 6))
