@@ -946,6 +946,39 @@ int ugs_graphlet_table(int n, int64_t *keys_out, int64_t capacity, int64_t *coun
 int ugs_graphlet_canon_code(uint32_t code, int n, uint32_t *out);
 int ugs_graphlet_search_stats(uint32_t code, int n, uint32_t *leaves_out, uint32_t *nodes_out);
 
+/* ---- graphlets.orbit_ids: where every vertex of a row sits inside its class -- its automorphism orbit (centre or leaf of a star, end
+ *      or middle of a path, triangle corner or tail of a paw).  Items 1 - 7 of ugs_graphlet_canon's law hold unchanged: vertices, n,
+ *      statuses 0 / 1 / 2, the simple graph, the bit layout, the code of a permutation, key and class id.  Then:
+ *        1. vertex j of a row is its j-th entry >= 0 in row order: an entry of -1 in the middle shifts the later vertices down, and a
+ *           repeated id is two vertices;
+ *        2. the ROOTED CODE of vertex v is the minimum of code(p) over the (n - 1)! permutations p with p(n - 1) = v; 0 for n = 1.  It
+ *           does not depend on the labelling; u and v lie in one orbit of the automorphism group exactly when their rooted codes are
+ *           equal; the minimum over v is the canonical code;
+ *        3. the orbits of a class are numbered by ascending rooted code: the LOCAL INDEX of v is the number of distinct rooted codes of
+ *           the row below v's.  The root's column is 2^deg - 1, so orbits come in order of degree first;
+ *        4. the ORBIT ID is base[class id] + local index, base being the exclusive prefix sum of the orbit counts over all classes in
+ *           key order.  It does not depend on k: the ids of graphs on at most k vertices fill [0, O_k),
+ *           O_k = 1, 3, 9, 29, 119, 663, 5759, 85023 for k = 1 .. 8 (connected graphs on exactly k vertices: 1, 1, 3, 11, 58, 407,
+ *           4306, 72489 orbits; 1 + 3 + 11 + 58 = 73 are the orbits of the graphlets on 2 .. 5 vertices);
+ *        5. orbit_out [rows, k] int64: slot s holds the orbit id of the vertex that slot s is, O_k where the entry is < 0 and in
+ *           every slot of a row with status != 0.  Other rows are not disturbed.
+ *      1 <= k <= 8, otherwise UGS_E_UNSUPPORTED.  The numbering is this library's own.
+ * ugs_graphlet_orbits: all pointers are DEVICE pointers.  d_table [table_len] as for ugs_graphlet_canon (needed: the id is found
+ *      through the class), d_base [table_len + 1] the prefix sums of item 4 (ugs_graphlet_orbit_counts for n = 1 .. k summed up, the
+ *      last entry being O_k).  d_key_out, d_status_out and d_class_out may each be NULL; where given they receive what
+ *      ugs_graphlet_canon writes, bit for bit, in the same launch.  One launch on the calling thread's stream, no allocation, no
+ *      synchronisation with the host; rows = 0 is a no-op.
+ * ugs_graphlet_rooted_codes: HOST function.  out[v], v < n, = the rooted code of vertex v of the graph whose adjacency bits are `code`
+ *      (bits above n (n - 1) / 2: UGS_E_BAD_ARG), by the search the kernel runs; out[v] = 0xffffffff for n <= v < 8.
+ * ugs_graphlet_orbit_counts: HOST function, no device work.  *count_out = the number of graphs on exactly n vertices; if capacity >=
+ *      it, counts_out[i] = the number of orbits of class i of ugs_graphlet_table(n).  Built once per process and n under the
+ *      table's mutex. */
+int ugs_graphlet_orbits(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                        const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, const int64_t *d_base, int64_t table_len,
+                        int64_t *d_orbit_out, int64_t *d_key_out, int32_t *d_status_out, int64_t *d_class_out);
+int ugs_graphlet_rooted_codes(uint32_t code, int n, uint32_t *out);
+int ugs_graphlet_orbit_counts(int n, int64_t *counts_out, int64_t capacity, int64_t *count_out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

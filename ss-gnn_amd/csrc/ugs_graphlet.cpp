@@ -1,6 +1,7 @@
-// ugs_graphlet.cpp -- host side of ugs_sampler.graphlets (C ABI: ugs_graphlet_canon_code / ugs_graphlet_table in
-// include/ugs_mi355.h, which states the law; kernel: ugs_graphlet.hip; the search both share: ugs_graphlet_common.h).
-// No device work here: the table of all graphs on n vertices is built on the host, once per process and per n.
+// ugs_graphlet.cpp -- host side of ugs_sampler.graphlets (C ABI: ugs_graphlet_canon_code / ugs_graphlet_table and, for the orbits,
+// ugs_graphlet_rooted_codes / ugs_graphlet_orbit_counts in include/ugs_mi355.h, which states the laws; kernels: ugs_graphlet.hip; the
+// search all share: ugs_graphlet_common.h).
+// No device work here: the table of all graphs on n vertices, and their orbit counts, are built on the host, once per process and n.
 #include "ugs_host_internal.h"
 #include "ugs_graphlet_common.h"
 
@@ -23,8 +24,21 @@ uint32_t canon_code(uint32_t code, int n, uint32_t *stats = nullptr) {
     return ugs_gl::canon(ugs_gl::adj_of_code(code, n), n, st, stats);
 }
 
+// The rooted codes of the n vertices, and how many distinct ones there are: the number of orbits.
+int rooted_codes(uint32_t code, int n, uint32_t *out) {
+    HostStack st;
+    const uint64_t adj = ugs_gl::adj_of_code(code, n);
+    int distinct = 0;
+    for (int v = 0; v < n; ++v) {
+        out[v] = ugs_gl::rooted(adj, n, v, st);
+        distinct += std::find(out, out + v, out[v]) == out + v;
+    }
+    return distinct;
+}
+
 std::mutex g_table_mu;
 std::vector<uint32_t> g_codes[UGS_GL_KMAX + 1];       // [n]: canonical codes of all graphs on n vertices, ascending; empty = not built
+std::vector<int64_t> g_orbits[UGS_GL_KMAX + 1];       // [n]: the number of orbits of each of them; empty = not built
 
 // Every graph on n vertices is a graph on n - 1 vertices plus a last vertex, and the last vertex's column is the top n - 1 bits: all
 // (n-1)-classes times all 2^(n-1) neighbour sets reach every n-class.  Called with the mutex held.
@@ -75,6 +89,31 @@ int ugs_graphlet_table(int n, int64_t *keys_out, int64_t capacity, int64_t *coun
     *count_out = (int64_t)codes.size();
     if (capacity >= (int64_t)codes.size())
         for (size_t i = 0; i < codes.size(); ++i) keys_out[i] = ((int64_t)n << 28) | (int64_t)codes[i];
+    return UGS_OK;
+}
+
+int ugs_graphlet_rooted_codes(uint32_t code, int n, uint32_t *out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_rooted_codes: 1 <= n <= 8");
+    if (!out) return fail(UGS_E_BAD_ARG, "graphlet_rooted_codes: null output pointer");
+    if ((uint64_t)code >> ugs_gl::tri(n)) return fail(UGS_E_BAD_ARG, "graphlet_rooted_codes: the code has bits above n(n-1)/2");
+    rooted_codes(code, n, out);
+    for (int v = n; v < UGS_GL_KMAX; ++v) out[v] = 0xffffffffu;
+    return UGS_OK;
+}
+
+int ugs_graphlet_orbit_counts(int n, int64_t *counts_out, int64_t capacity, int64_t *count_out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_orbit_counts: 1 <= n <= 8");
+    if (!count_out || capacity < 0 || (capacity > 0 && !counts_out)) return fail(UGS_E_BAD_ARG, "graphlet_orbit_counts: count_out, and counts_out for capacity > 0, are needed");
+    std::lock_guard<std::mutex> lock(g_table_mu);
+    const std::vector<uint32_t> &codes = codes_of(n);
+    std::vector<int64_t> &orbits = g_orbits[n];
+    if (orbits.empty()) {
+        uint32_t rooted[UGS_GL_KMAX];
+        orbits.reserve(codes.size());
+        for (uint32_t c : codes) orbits.push_back(rooted_codes(c, n, rooted));
+    }
+    *count_out = (int64_t)orbits.size();
+    if (capacity >= (int64_t)orbits.size()) std::copy(orbits.begin(), orbits.end(), counts_out);
     return UGS_OK;
 }
 

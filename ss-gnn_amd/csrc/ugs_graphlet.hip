@@ -15,6 +15,9 @@
 //   id      lane 0 of the group: binary search of the key in the ascending table (at most 13 598 entries: 14 probes, the table
 //           stays in L2).
 // There is one path.  What the split over first picks buys, and what the most symmetric rows cost: DESIGN.md section 19.
+//
+// ugs_graphlet_orbits_kernel (law: ugs_graphlet_orbits in the same header): the same geometry and reading,
+// every lane u < n searching below its own vertex as the forced first pick; described at the kernel.
 #include "ugs_device.h"
 #include "ugs_graphlet_common.h"
 #include "../../include/ugs_mi355.h"
@@ -108,7 +111,125 @@ __global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_canon_kernel(GlArgs
     }
 }
 
+struct GlOrbitArgs {
+    GlArgs g;                    // rows, table and the optional key / status / class outputs (each may be NULL here)
+    const int64_t *base;         // [table_len + 1]: first orbit id of every class, then O_k
+    int64_t *orbit;              // [rows, k]
+};
+
+// ugs_graphlet_orbits_kernel: the geometry, the row and edge reading and the three folds of the kernel above.
+//   search  lane u < n runs ugs_gl::rooted for vertex u: the search below the FORCED first pick u, tied at the root or not and with
+//           no twin rule there.  Lanes u >= n hold 2^28, above every code;
+//   group   eight shuffles hand every lane the group's values.  Their minimum is the canonical code; a lane is a first occurrence
+//           if no lane before it holds its value; the local index is the number of first occurrences with a smaller value;
+//   id      lane 0 finds the class as above and reads base[class]; a shuffle hands it to the group;
+//   store   lane s is slot s: its vertex index j is the popcount of the group's ballot below s, lane j's local index comes by a
+//           shuffle, and a wave writes 8 k consecutive int64.
+__global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_orbits_kernel(GlOrbitArgs oa) {
+    __shared__ uint64_t cells_sh[UGS_GL_KMAX * UGS_GL_BLOCK];
+    const GlArgs &a = oa.g;
+    const int tid = (int)threadIdx.x;
+    const int u = tid & (UGS_GL_LANES - 1);                      // slot, vertex and first pick of this lane
+    const int64_t row = (int64_t)blockIdx.x * (UGS_GL_BLOCK / UGS_GL_LANES) + (tid >> 3);
+    if (row >= a.rows) return;                                   // whole groups leave; no barrier below: a lane's LDS column is its own
+
+    const int64_t id = u < a.k ? a.nodes[row * a.k + u] : -1;
+    const int gshift = (tid & 63) & ~(UGS_GL_LANES - 1);         // the group's first lane inside the wave
+    const unsigned present = (unsigned)(__ballot(id >= 0) >> gshift) & 0xffu;
+    const int n = __popc(present);
+    int bad = 0;
+    uint64_t adj = 0;
+    if (n > 0) {
+        const int64_t lo = a.edge_ptr[row], hi = a.edge_ptr[row + 1];
+        if (lo < 0 || hi < lo || hi > a.num_cols) {
+            bad = 1;                                             // not a range of edge_index: nothing is read
+        } else {
+            for (int64_t e = lo + u; e < hi; e += UGS_GL_LANES) {
+                const int64_t x = a.edge_index[e], y = a.edge_index[a.stride + e];
+                if (x < 0 || x >= n || y < 0 || y >= n) bad = 1;
+                else if (x != y) adj |= (1ull << (8 * (int)x + (int)y)) | (1ull << (8 * (int)y + (int)x));
+            }
+        }
+    }
+    for (int d = 1; d < UGS_GL_LANES; d <<= 1) {
+        adj |= __shfl_xor(adj, d);
+        bad |= __shfl_xor(bad, d);
+    }
+    const int status = n == 0 ? 1 : bad ? 2 : 0;
+
+    uint32_t val = 1u << 28;                                     // above every code
+    if (status == 0 && u < n) {
+        LdsStack st{cells_sh + tid};
+        val = ugs_gl::rooted(adj, n, u, st);
+    }
+
+    uint32_t vals[UGS_GL_LANES];
+    uint32_t code = 1u << 28;
+    bool first = true;
+#pragma unroll
+    for (int w = 0; w < UGS_GL_LANES; ++w) {
+        vals[w] = (uint32_t)__shfl((int)val, w, UGS_GL_LANES);
+        code = min(code, vals[w]);
+        first = first && !(w < u && vals[w] == val);
+    }
+    const unsigned firsts = (unsigned)(__ballot(first) >> gshift) & 0xffu;
+    int local = 0;
+#pragma unroll
+    for (int w = 0; w < UGS_GL_LANES; ++w) local += (int)((firsts >> w) & 1u) & (int)(vals[w] < val);
+
+    const int64_t fill = oa.base[a.table_len];                   // O_k
+    const int64_t key = status == 0 ? ((int64_t)n << 28) | (int64_t)code : -1;
+    int64_t first_id = fill;
+    if (u == 0) {
+        int64_t cid = a.table_len;                               // the id of a refused row: len(vocab)
+        if (status == 0) {
+            int64_t lo_i = 0, hi_i = a.table_len;                // first table key >= key
+            while (lo_i < hi_i) {
+                const int64_t mid = lo_i + ((hi_i - lo_i) >> 1);
+                if (a.table[mid] < key) lo_i = mid + 1; else hi_i = mid;
+            }
+            if (lo_i < a.table_len && a.table[lo_i] == key) cid = lo_i;
+        }
+        first_id = oa.base[cid];
+        if (a.key) a.key[row] = key;
+        if (a.status) a.status[row] = status;
+        if (a.cls) a.cls[row] = cid;
+    }
+    first_id = __shfl(first_id, 0, UGS_GL_LANES);
+    const int j = __popc(present & ((1u << u) - 1u));            // the vertex that slot u is, if its entry is >= 0
+    const int local_j = __shfl(local, j, UGS_GL_LANES);
+    if (u < a.k) oa.orbit[row * a.k + u] = (status == 0 && id >= 0) ? first_id + local_j : fill;
+}
+
 }  // namespace
+
+extern "C" int ugs_graphlet_orbits(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                                   const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, const int64_t *d_base,
+                                   int64_t table_len, int64_t *d_orbit_out, int64_t *d_key_out, int32_t *d_status_out,
+                                   int64_t *d_class_out) {
+    if (k < 1 || k > UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_orbits: 1 <= k <= 8");
+    if (rows < 0 || num_cols < 0 || (num_cols > 0 && row_stride < num_cols))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_orbits: rows >= 0, num_cols >= 0, row_stride >= num_cols");
+    if (table_len < 0) return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_orbits: table_len >= 0");
+    if (rows == 0) return UGS_OK;
+    if (!d_nodes || !d_edge_ptr || !d_orbit_out || !d_base || (table_len > 0 && !d_table) || (num_cols > 0 && !d_edge_index))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_orbits: null pointer");
+    const int64_t per_block = UGS_GL_BLOCK / UGS_GL_LANES;
+    const int64_t blocks = (rows + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffll) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_orbits: too many rows for one launch");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    GlOrbitArgs oa{};
+    GlArgs &a = oa.g;
+    a.nodes = d_nodes; a.edge_index = d_edge_index; a.stride = row_stride; a.num_cols = num_cols; a.edge_ptr = d_edge_ptr;
+    a.rows = rows; a.k = k; a.table = d_table; a.table_len = table_len;
+    a.key = d_key_out; a.status = d_status_out; a.cls = d_class_out;
+    oa.base = d_base; oa.orbit = d_orbit_out;
+    hipLaunchKernelGGL(ugs_graphlet_orbits_kernel, dim3((unsigned)blocks), dim3(UGS_GL_BLOCK), 0, s, oa);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}
 
 extern "C" int ugs_graphlet_canon(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
                                   const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, int64_t table_len,

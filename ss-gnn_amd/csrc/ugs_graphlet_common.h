@@ -136,6 +136,18 @@ UGS_GL_HD uint32_t canon(uint64_t adj, int n, Stack &st, uint32_t *stats = nullp
     return search(adj, (1ull << n) - 1ull, n - 1, 0u, st, stats);
 }
 
+// The ROOTED code of vertex u (ugs_graphlet_orbits in include/ugs_mi355.h): the smallest code over the orders that put u in the last
+// position.  u is forced as the first pick, tied at the root or not and with no twin rule there: its column is 2^deg - 1 over the one
+// cell, the search below it is the one above.  Two vertices have equal rooted codes exactly when an automorphism maps one to the
+// other, and the minimum over u is canon().
+template <class Stack>
+UGS_GL_HD uint32_t rooted(uint64_t adj, int n, int u, Stack &st) {
+    if (n <= 1) return 0;
+    const uint32_t col = (1u << popc8((uint32_t)(adj >> (8 * u)) & 0xffu)) - 1u;
+    if (n == 2) return col;                            // the root is the last level with a column
+    return search(adj, split_cells(adj, (1ull << n) - 1ull, u), n - 2, col << tri(n - 1), st);
+}
+
 }  // namespace ugs_gl
 
 #endif /* UGS_GRAPHLET_COMMON_H */

@@ -20,6 +20,18 @@ With `uniform_sampler.enumerate_graphs` the ids give a graph's exact graphlet hi
 
     nodes, edge_index, edge_ptr, sample_ptr, _, _ = uniform_sampler.enumerate_graphs(batch.edge_index, batch.ptr, k, device=dev)
     hist = graphlets.histogram(graphlets.class_ids(nodes, edge_index, edge_ptr), sample_ptr, k)     # int64 [G, num_classes(k)]
+
+`orbit_ids` says where each of a row's vertices sits inside that class: its orbit under the class's automorphism group (centre or
+leaf of a star, end or middle of a path).  The law is stated at ugs_graphlet_orbits in the same header.  The ROOTED CODE of a vertex
+is the smallest adjacency code over the orders that put it last; two vertices of a row lie in one orbit exactly when their rooted
+codes are equal.  A class's orbits are numbered by ascending rooted code and the orbit id is orbit_base[class id] + that number, so
+like the class id it does not depend on k and the ids of a k-sampler fill [0, num_orbits(k)); num_orbits(k) marks a slot < 0 and
+every slot of a row of status 1 or 2.  The numbering is this library's own (`orbit_info` decodes it), not ORCA's.  A fixed
+embedding of num_orbits(k) + 1 rows is an exact structural feature of every slot, and over the enumerated population the ids count
+the graphlet degree vector of every vertex -- how often it occupies each orbit of each connected k-graphlet:
+
+    orbit = graphlets.orbit_ids(nodes, edge_index, edge_ptr)                                        # int64 [S, k]
+    gdv = graphlets.vertex_orbit_counts(nodes, orbit, batch.num_nodes, graphlets.connected_orbits(k))
 """
 import ctypes as C
 
@@ -30,12 +42,16 @@ from . import _select_device
 from ._lib import check, lib
 from .wl import _check_inputs, _placed
 
-__all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats"]
+__all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats",
+           "orbit_ids", "num_orbits", "orbit_base", "orbit_info", "connected_orbits", "vertex_orbit_counts"]
 
 KMAX = 8
 _NUM_CLASSES = (1, 3, 7, 18, 52, 208, 1252, 13598)     # graphs on at most k vertices, k = 1 .. 8
 _host_tables = {}                                       # n -> numpy int64 keys of the graphs on exactly n vertices
 _dev_tables = {}                                        # (device index, k) -> the table for n <= k on that GPU
+_NUM_ORBITS = (1, 3, 9, 29, 119, 663, 5759, 85023)      # orbits of the graphs on at most k vertices, k = 1 .. 8
+_host_orbit_counts = {}                                 # n -> numpy int64 orbit counts of the graphs on exactly n vertices, in table order
+_dev_bases = {}                                         # (device index, k) -> orbit_base(k) on that GPU
 
 
 def _check_k(k):
@@ -188,3 +204,134 @@ def search_stats(key_or_code, n=None):
     leaves, nodes = C.c_uint32(0), C.c_uint32(0)
     check(lib.ugs_graphlet_search_stats(code, n, C.byref(leaves), C.byref(nodes)))
     return leaves.value, nodes.value
+
+
+def _orbit_counts_n(n):
+    if n not in _host_orbit_counts:
+        count = C.c_int64(0)
+        check(lib.ugs_graphlet_orbit_counts(n, None, 0, C.byref(count)))
+        counts = np.empty((count.value,), dtype=np.int64)
+        check(lib.ugs_graphlet_orbit_counts(n, counts.ctypes.data, counts.size, C.byref(count)))
+        _host_orbit_counts[n] = counts
+    return _host_orbit_counts[n]
+
+
+def num_orbits(k):
+    """The number of vertex orbits of the graphs on at most k vertices, 1 <= k <= 8: 1, 3, 9, 29, 119, 663, 5759, 85023.  The ids
+    of `orbit_ids` on [S, k] rows are below it, and it is the id of a slot without a vertex."""
+    _check_k(k)
+    return _NUM_ORBITS[k - 1]
+
+
+def orbit_base(k):
+    """int64 [num_classes(k) + 1] on the host: orbit_base(k)[c] is the first orbit id of class c, the orbits of class c being
+    orbit_base(k)[c] .. orbit_base(k)[c + 1] - 1, and the last entry is num_orbits(k).  Built by the library on first use (all of
+    k = 8 takes a fraction of a second) and kept."""
+    _check_k(k)
+    counts = np.concatenate([_orbit_counts_n(n) for n in range(1, k + 1)])
+    return torch.from_numpy(np.concatenate([np.zeros(1, np.int64), np.cumsum(counts)]))
+
+
+def _rooted_codes(code, n):
+    out = (C.c_uint32 * KMAX)()
+    check(lib.ugs_graphlet_rooted_codes(code, n, out))
+    return list(out)[:n]
+
+
+def orbit_info(orbit_id):
+    """(class id, class key, rooted code, orbit size, degree) of an orbit id: the class the orbit belongs to, the rooted code that
+    its vertices share, how many of the class's vertices it holds and the degree each of them has.  Vertex v of the class's
+    canonical representative `decode(key)` lies in it exactly when its rooted code is that one.  Host only."""
+    if isinstance(orbit_id, bool) or not isinstance(orbit_id, int):
+        raise TypeError("orbit_id must be an int")
+    if not 0 <= orbit_id < _NUM_ORBITS[-1]:
+        raise ValueError(f"{orbit_id} is no orbit id")
+    base = orbit_base(KMAX).numpy()
+    cid = int(np.searchsorted(base, orbit_id, side="right")) - 1
+    key = int(table(KMAX)[cid])
+    n = key >> 28
+    rooted = _rooted_codes(key & ((1 << 28) - 1), n)
+    code = sorted(set(rooted))[orbit_id - int(base[cid])]
+    return cid, key, code, rooted.count(code), bin(code >> ((n - 1) * (n - 2) // 2)).count("1")
+
+
+def connected_orbits(k):
+    """The ids of the orbits of the connected graphs on exactly k vertices, ascending: int64 on the host, 1, 1, 3, 11, 58, 407, 4306
+    and 72 489 of them for k = 1 .. 8.  The columns of a k-GDV (`vertex_orbit_counts`); connected_orbits(2) .. (5) together are
+    the 73 orbits of the graphlets on at most 5 vertices."""
+    _check_k(k)
+    base, keys = orbit_base(k), table(k)
+    first = num_classes(k - 1) if k > 1 else 0
+    ids = [torch.arange(int(base[c]), int(base[c + 1]), dtype=torch.int64)
+           for c in (first + torch.nonzero(is_connected(keys[first:])).view(-1)).tolist()]
+    return torch.cat(ids)
+
+
+def _device_base(dev, k):
+    key = (dev.index, k)
+    if key not in _dev_bases:
+        _dev_bases[key] = orbit_base(k).to(dev)
+    return _dev_bases[key]
+
+
+def orbit_ids(nodes_sampled, edge_index_sampled, edge_ptr, *, device=None, return_class=False):
+    """The orbit id of every slot of every sampled subgraph: int64 [S, k] with values in [0, num_orbits(k)), and num_orbits(k) where
+    the entry is < 0 and in every slot of a row of status 1 or 2 (module docstring).  Slot s answers for the vertex that entry s
+    of the row is: the j-th entry >= 0 in row order is vertex j of the row's edges.  With return_class, (orbit, class_ids) from
+    the same launch, class_ids as `class_ids` returns them.  Placement as `canonical`; the key table and `orbit_base(k)` are
+    uploaded once per device and k.  One launch, no synchronisation with the host."""
+    _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, 0)
+    nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, device)
+    _select_device(dev, jobs=True)
+    S, k = nodes.shape
+    known = 1 <= k <= KMAX
+    tab, base = (_device_table(dev, k), _device_base(dev, k)) if known else (None, None)
+    orbit = torch.empty((S, k), dtype=torch.int64, device=dev)
+    ids = torch.empty((S,), dtype=torch.int64, device=dev) if return_class else None
+    nodes, eptr = nodes.contiguous(), eptr.contiguous()
+    E = edge_index.size(1)
+    if E > 0 and edge_index.stride(1) != 1:
+        edge_index = edge_index.contiguous()
+    stride = edge_index.stride(0) if E > 0 else 0
+    if S > 0 or not known:                              # the library states the limit
+        check(lib.ugs_graphlet_orbits(nodes.data_ptr(), edge_index.data_ptr() if E > 0 else None, stride, E, eptr.data_ptr(), S, k,
+                                      tab.data_ptr() if known else None, base.data_ptr() if known else None,
+                                      tab.numel() if known else 0, orbit.data_ptr(), None, None,
+                                      ids.data_ptr() if return_class else None))
+    if back:
+        orbit, ids = orbit.cpu(), ids.cpu() if return_class else None
+    return (orbit, ids) if return_class else orbit
+
+
+def vertex_orbit_counts(nodes, orbit, num_vertices, columns):
+    """How often every vertex occupies every orbit: int64 [num_vertices, len(columns)], entry [v, c] counting the slots with node id
+    v and orbit id columns[c].  `nodes` and `orbit` are int64 of one shape on one device (a sampler's nodes [S, k] and
+    `orbit_ids` of them); `columns` is an int64 vector of ASCENDING, DISTINCT orbit ids (it is not checked: that would wait for the
+    device) and is moved to that device if it is elsewhere.  A slot whose node id is outside [0, num_vertices) or whose orbit id is
+    not in `columns` is not counted.  Over `uniform_sampler.enumerate_graphs(..., k)` rows with columns = connected_orbits(k) this is
+    the exact k-graphlet degree vector of every vertex of the batch.  There is no default for `columns`: all num_orbits(8) = 85 023
+    columns are no sensible width.  A torch searchsorted and one scatter_add_ on the tensors' device, no synchronisation."""
+    for t, name in ((nodes, "nodes"), (orbit, "orbit"), (columns, "columns")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64, got {t.dtype}")
+    if isinstance(num_vertices, bool) or not isinstance(num_vertices, int):
+        raise TypeError("num_vertices must be an int")
+    if num_vertices < 0:
+        raise ValueError("num_vertices must be >= 0")
+    if nodes.shape != orbit.shape:
+        raise ValueError("nodes and orbit must have one shape")
+    if nodes.device != orbit.device:
+        raise ValueError("nodes and orbit must be on one device")
+    if columns.dim() != 1:
+        raise ValueError("columns must have shape [C]")
+    dev, width = nodes.device, columns.numel()
+    out = torch.zeros((num_vertices * width,), dtype=torch.int64, device=dev)
+    if width > 0 and num_vertices > 0:
+        columns = columns.to(dev).contiguous()
+        v, o = nodes.reshape(-1), orbit.reshape(-1)
+        col = torch.searchsorted(columns, o).clamp_(max=width - 1)
+        counted = (columns[col] == o) & (v >= 0) & (v < num_vertices)
+        out.scatter_add_(0, torch.where(counted, v * width + col, torch.zeros_like(v)), counted.to(torch.int64))
+    return out.view(num_vertices, width)
