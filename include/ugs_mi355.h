@@ -979,6 +979,43 @@ int ugs_graphlet_orbits(const int64_t *d_nodes, const int64_t *d_edge_index, int
 int ugs_graphlet_rooted_codes(uint32_t code, int n, uint32_t *out);
 int ugs_graphlet_orbit_counts(int n, int64_t *counts_out, int64_t capacity, int64_t *count_out);
 
+/* ---- graphlets.labelled_keys: the exact class of every row as a NODE-LABELLED graph (use_node_features_in_wl), and the orbits of the
+ *      label-preserving automorphism group.  Two rows of one shape with different labels -- two molecule fragments with different
+ *      atoms -- are different classes.  Items 1 - 6 of ugs_graphlet_canon's law hold unchanged: vertices, n, statuses 0 / 1 / 2, the
+ *      simple graph, the bit layout and the code of a permutation.  Then:
+ *        1. vertex j of a row is its j-th entry >= 0 in row order, and its LABEL is labels[entry]: an entry of -1 in the middle shifts
+ *           the later vertices down, and a repeated id is two vertices with one label;
+ *        2. status 3, checked after 1 and 2 (a row with a bad endpoint or a bad edge_ptr range is 2 whatever its labels, as in
+ *           ugs_wl_hash_labeled): an entry >= num_labels, or a label outside [0, 4096).  Nothing is read outside labels
+ *           [0, num_labels).  A row of status != 0 has both key words -1 and k in every orbit slot; other rows are not disturbed;
+ *        3. a permutation p is LABEL-MONOTONE if label(p(i)) <= label(p(j)) for all positions i < j.  The LABELLED CANONICAL CODE is
+ *           the minimum of code(p) over the label-monotone permutations.  With all labels equal it is the canonical code;
+ *        4. the KEY is the 128-bit number K = n * 2^124 + code * 2^96 + sum over p < n of L[p] * 2^(12 p), L being the row's labels
+ *           sorted ascending -- the label at canonical position p.  key_out[row] = (K >> 64, K & (2^64 - 1)) as int64 bit patterns:
+ *           the [rows, 2] form of ugs_wl_hash's digests, which ugs_wl_lookup takes, ascending as 128-bit numbers.  The high word is
+ *           negative as int64 for n = 8;
+ *        5. two rows have equal keys exactly when an isomorphism of their graphs maps labels to equal labels.  The key is invertible:
+ *           n, the code and the sorted labels are bit fields of it, and (code, L) in the identity order is a representative;
+ *        6. the LABELLED ROOTED CODE of vertex u is the minimum of code(p) over the permutations with p(n - 1) = u that put the other
+ *           n - 1 vertices in non-decreasing label order by position; 0 for n = 1.  u and v lie in one orbit of the label-preserving
+ *           automorphism group exactly when label(u) = label(v) and their labelled rooted codes are equal;
+ *        7. a row's orbits are numbered 0, 1, ... by ascending (label, labelled rooted code); orbit_out [rows, k] int64: slot s holds
+ *           the number of the orbit of the vertex that slot s is, k where the entry is < 0 and in every slot of a row of
+ *           status != 0.  With all labels equal it is ugs_graphlet_orbits' orbit id minus base[class id].
+ *      1 <= k <= 8, otherwise UGS_E_UNSUPPORTED.  At most 4096 labels: 12 bits each in the key.
+ * ugs_graphlet_labelled: all pointers are DEVICE pointers.  d_labels [num_labels] int64; num_labels = 0 with a NULL d_labels is legal,
+ *      every row with an entry >= 0 is then status 3.  d_key_out [rows, 2] int64, d_status_out [rows] int32, d_orbit_out [rows, k]
+ *      int64 or NULL.  Limits and refusals as ugs_graphlet_canon.  One launch on the calling thread's stream, no allocation, no
+ *      synchronisation with the host; rows = 0 is a no-op.
+ * ugs_graphlet_labelled_code: HOST function, the same search on a graph given by its adjacency bits `code` (bits above n (n - 1) / 2:
+ *      UGS_E_BAD_ARG) and the labels of its vertices 0 .. n-1 (labels[v], v < n, outside [0, 4096): UGS_E_BAD_ARG; entries from n
+ *      on are not read).  key_out[0..1] = the two key words of item 4.  rooted_out, unless NULL: rooted_out[v] = the labelled rooted
+ *      code of vertex v, 0xffffffff for n <= v < 8. */
+int ugs_graphlet_labelled(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                          const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_labels, int64_t num_labels,
+                          int64_t *d_key_out, int32_t *d_status_out, int64_t *d_orbit_out);
+int ugs_graphlet_labelled_code(uint32_t code, int n, const int32_t *labels, int64_t *key_out, uint32_t *rooted_out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

@@ -1,6 +1,6 @@
 // ugs_graphlet.cpp -- host side of ugs_sampler.graphlets (C ABI: ugs_graphlet_canon_code / ugs_graphlet_table and, for the orbits,
-// ugs_graphlet_rooted_codes / ugs_graphlet_orbit_counts in include/ugs_mi355.h, which states the laws; kernels: ugs_graphlet.hip; the
-// search all share: ugs_graphlet_common.h).
+// ugs_graphlet_rooted_codes / ugs_graphlet_orbit_counts and, for node-labelled graphs, ugs_graphlet_labelled_code in
+// include/ugs_mi355.h, which states the laws; kernels: ugs_graphlet.hip; the search all share: ugs_graphlet_common.h).
 // No device work here: the table of all graphs on n vertices, and their orbit counts, are built on the host, once per process and n.
 #include "ugs_host_internal.h"
 #include "ugs_graphlet_common.h"
@@ -114,6 +114,35 @@ int ugs_graphlet_orbit_counts(int n, int64_t *counts_out, int64_t capacity, int6
     }
     *count_out = (int64_t)orbits.size();
     if (capacity >= (int64_t)orbits.size()) std::copy(orbits.begin(), orbits.end(), counts_out);
+    return UGS_OK;
+}
+
+int ugs_graphlet_labelled_code(uint32_t code, int n, const int32_t *labels, int64_t *key_out, uint32_t *rooted_out) {
+    if (n < 1 || n > UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_labelled_code: 1 <= n <= 8");
+    if (!labels || !key_out) return fail(UGS_E_BAD_ARG, "graphlet_labelled_code: null labels or key pointer");
+    if ((uint64_t)code >> ugs_gl::tri(n)) return fail(UGS_E_BAD_ARG, "graphlet_labelled_code: the code has bits above n(n-1)/2");
+    int lab[UGS_GL_KMAX];
+    for (int v = 0; v < n; ++v) {
+        if (labels[v] < 0 || labels[v] >= 4096) return fail(UGS_E_BAD_ARG, "graphlet_labelled_code: labels lie in [0, 4096)");
+        lab[v] = labels[v];
+    }
+    HostStack st;
+    const uint64_t adj = ugs_gl::adj_of_code(code, n);
+    const uint64_t cells = ugs_gl::label_cells(lab, n);
+    const uint64_t canon = ugs_gl::canon_cells(adj, cells, n, st);
+    std::sort(lab, lab + n);
+    uint64_t hi = ((uint64_t)n << 60) | (canon << 32), lo = 0;       // K = n 2^124 + code 2^96 + sum L[p] 2^(12 p)
+    for (int p = 0; p < n; ++p) {
+        const int at = 12 * p;
+        if (at < 64) lo |= (uint64_t)lab[p] << at;                   // L[5] straddles the words: its high 8 bits fall off here
+        if (at + 12 > 64) hi |= at >= 64 ? (uint64_t)lab[p] << (at - 64) : (uint64_t)lab[p] >> (64 - at);
+    }
+    key_out[0] = (int64_t)hi;
+    key_out[1] = (int64_t)lo;
+    if (rooted_out) {
+        for (int v = 0; v < n; ++v) rooted_out[v] = ugs_gl::rooted_cells(adj, cells, n, v, st);
+        for (int v = n; v < UGS_GL_KMAX; ++v) rooted_out[v] = 0xffffffffu;
+    }
     return UGS_OK;
 }
 

@@ -18,6 +18,9 @@
 //
 // ugs_graphlet_orbits_kernel (law: ugs_graphlet_orbits in the same header): the same geometry and reading,
 // every lane u < n searching below its own vertex as the forced first pick; described at the kernel.
+//
+// ugs_graphlet_labelled_kernel (law: ugs_graphlet_labelled in the same header): node-labelled keys, and the
+// orbits of the label-preserving automorphisms, by the same searches started from the partition by label; described at the kernel.
 #include "ugs_device.h"
 #include "ugs_graphlet_common.h"
 #include "../../include/ugs_mi355.h"
@@ -201,7 +204,184 @@ __global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_orbits_kernel(GlOrb
     if (u < a.k) oa.orbit[row * a.k + u] = (status == 0 && id >= 0) ? first_id + local_j : fill;
 }
 
+struct GlLabelArgs {
+    const int64_t *nodes;        // [rows, k]
+    const int64_t *edge_index;   // [2, num_cols], row stride `stride`
+    int64_t stride, num_cols;
+    const int64_t *edge_ptr;     // [rows + 1]
+    int64_t rows;
+    int k;
+    const int64_t *labels;       // [num_labels]
+    int64_t num_labels;
+    int64_t *key;                // [rows, 2]
+    int32_t *status;             // [rows]
+    int64_t *orbit;              // [rows, k]; the ORBITS form only
+};
+
+// ugs_graphlet_labelled_kernel (law: ugs_graphlet_labelled in the header): the geometry, the row and edge
+// reading and the folds of the kernels above.  ORBITS = false writes key and status, ORBITS = true the orbit slots as well.
+//   labels  lane s is slot s: it gathers labels[entry], the bounds check before the load, and its vertex is the popcount of the
+//           group's ballot below s.  Eight shuffles hand every lane the group's labels.  A slot's cell is the number of distinct
+//           smaller labels, its sorted position the number of smaller labels plus that of equal ones in lower slots.  Each slot
+//           sets its vertex's bit in its cell's byte and its label's 12 bits at its position; three xor-shuffles OR them into the
+//           root partition (ugs_gl::label_cells' word) and the key's 96 label bits;
+//   keys    every lane evaluates the root over those cells; lane u owns the subtree below first pick u if the root keeps u: only
+//           vertices of the largest label are candidates, so with more than one label fewer lanes search.  Minimum over the group;
+//   orbits  lane u < n runs ugs_gl::rooted_cells for vertex u and holds (cell << 28) | rooted code, which orders as (label, code).
+//           Eight shuffles hand every lane the group's values; first occurrences, local index and the slot rule as in
+//           ugs_graphlet_orbits_kernel.  The canonical code is the smallest rooted code of the last cell;
+//   store   lanes 0 and 1 write the two key words, lane 0 the status, lane s orbit slot s.
+template <bool ORBITS>
+__global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_labelled_kernel(GlLabelArgs a) {
+    __shared__ uint64_t cells_sh[UGS_GL_KMAX * UGS_GL_BLOCK];
+    const int tid = (int)threadIdx.x;
+    const int u = tid & (UGS_GL_LANES - 1);                      // slot, vertex and first pick of this lane
+    const int64_t row = (int64_t)blockIdx.x * (UGS_GL_BLOCK / UGS_GL_LANES) + (tid >> 3);
+    if (row >= a.rows) return;                                   // whole groups leave; no barrier below: a lane's LDS column is its own
+
+    const int64_t id = u < a.k ? a.nodes[row * a.k + u] : -1;
+    const int gshift = (tid & 63) & ~(UGS_GL_LANES - 1);         // the group's first lane inside the wave
+    const unsigned present = (unsigned)(__ballot(id >= 0) >> gshift) & 0xffu;
+    const int n = __popc(present);
+    int lab = -1, bad = 0, badlab = 0;
+    if (id >= 0) {
+        if (id >= a.num_labels) {
+            badlab = 1;                                          // no label of that index: nothing is read
+        } else {
+            const int64_t l = a.labels[id];
+            if (l < 0 || l >= 4096) badlab = 1; else lab = (int)l;
+        }
+    }
+    uint64_t adj = 0;
+    if (n > 0) {
+        const int64_t lo = a.edge_ptr[row], hi = a.edge_ptr[row + 1];
+        if (lo < 0 || hi < lo || hi > a.num_cols) {
+            bad = 1;                                             // not a range of edge_index: nothing is read
+        } else {
+            for (int64_t e = lo + u; e < hi; e += UGS_GL_LANES) {
+                const int64_t x = a.edge_index[e], y = a.edge_index[a.stride + e];
+                if (x < 0 || x >= n || y < 0 || y >= n) bad = 1;
+                else if (x != y) adj |= (1ull << (8 * (int)x + (int)y)) | (1ull << (8 * (int)y + (int)x));
+            }
+        }
+    }
+
+    // the root partition and the sorted labels; a slot without a label (lab = -1) takes no part
+    int cell = 0, pos = 0;
+    {
+        int labs[UGS_GL_LANES];
+#pragma unroll
+        for (int w = 0; w < UGS_GL_LANES; ++w) labs[w] = __shfl(lab, w, UGS_GL_LANES);
+#pragma unroll
+        for (int w = 0; w < UGS_GL_LANES; ++w) {
+            bool first = labs[w] >= 0;                           // no lower slot holds this label
+#pragma unroll
+            for (int x = 0; x < w; ++x) first = first && labs[x] != labs[w];
+            const bool below = labs[w] >= 0 && labs[w] < lab;
+            cell += (int)(first && below);
+            pos += (int)below + (int)(w < u && labs[w] == lab);
+        }
+    }
+    const int j = __popc(present & ((1u << u) - 1u));            // the vertex that slot u is, if its entry is >= 0
+    uint64_t cells = 0, lab_lo = 0, lab_hi = 0;                  // the labels' bits 0 .. 63 and 64 .. 95 of the key
+    if (lab >= 0) {
+        cells = 1ull << (8 * cell + j);
+        const int at = 12 * pos;
+        if (at < 64) lab_lo = (uint64_t)lab << at;               // position 5 straddles the words: its high 8 bits fall off here
+        if (at + 12 > 64) lab_hi = at >= 64 ? (uint64_t)lab << (at - 64) : (uint64_t)lab >> (64 - at);
+    }
+    for (int d = 1; d < UGS_GL_LANES; d <<= 1) {                 // the group's lanes are all here: n and the row are theirs alike
+        adj |= __shfl_xor(adj, d);
+        bad |= __shfl_xor(bad, d);
+        badlab |= __shfl_xor(badlab, d);
+        cells |= __shfl_xor(cells, d);
+        lab_lo |= __shfl_xor(lab_lo, d);
+        lab_hi |= __shfl_xor(lab_hi, d);
+    }
+    const int status = n == 0 ? 1 : bad ? 2 : badlab ? 3 : 0;
+
+    uint32_t code = 1u << 28;                                    // above every code
+    int local = 0;
+    if (!ORBITS) {
+        if (status == 0) {
+            if (n == 1) {
+                code = 0;
+            } else {
+                uint32_t tied, col;
+                ugs_gl::eval_node(adj, cells, tied, col);
+                if (n == 2) {
+                    code = col;                                  // the root is the last level with a column
+                } else if ((tied >> u) & 1u) {
+                    LdsStack st{cells_sh + tid};
+                    code = ugs_gl::search(adj, ugs_gl::split_cells(adj, cells, u), n - 2, col << ugs_gl::tri(n - 1), st);
+                }
+            }
+            for (int d = 1; d < UGS_GL_LANES; d <<= 1) code = min(code, (uint32_t)__shfl_xor((int)code, d));
+        }
+    } else {
+        uint32_t val = 0xffffffffu;                              // above every (cell, code) pair, and of no cell
+        uint32_t last = 0;
+        if (status == 0) {
+            last = (uint32_t)(63 - __builtin_clzll(cells)) >> 3;
+            if (u < n) {
+                LdsStack st{cells_sh + tid};
+                uint32_t mine = 0;
+#pragma unroll
+                for (int i = 1; i < UGS_GL_KMAX; ++i) mine = ((cells >> (8 * i + u)) & 1ull) ? (uint32_t)i : mine;
+                val = (mine << 28) | ugs_gl::rooted_cells(adj, cells, n, u, st);
+            }
+        }
+        uint32_t vals[UGS_GL_LANES];
+        bool first = true;
+#pragma unroll
+        for (int w = 0; w < UGS_GL_LANES; ++w) {
+            vals[w] = (uint32_t)__shfl((int)val, w, UGS_GL_LANES);
+            if ((vals[w] >> 28) == last) code = min(code, vals[w] & ((1u << 28) - 1u));
+            first = first && !(w < u && vals[w] == val);
+        }
+        const unsigned firsts = (unsigned)(__ballot(first) >> gshift) & 0xffu;
+#pragma unroll
+        for (int w = 0; w < UGS_GL_LANES; ++w) local += (int)((firsts >> w) & 1u) & (int)(vals[w] < val);
+    }
+
+    if (u < 2) {
+        const int64_t hi = (int64_t)(((uint64_t)n << 60) | ((uint64_t)code << 32) | lab_hi);
+        a.key[row * 2 + u] = status != 0 ? -1 : u == 0 ? hi : (int64_t)lab_lo;
+    }
+    if (u == 0) a.status[row] = status;
+    if (ORBITS) {
+        const int local_j = __shfl(local, j, UGS_GL_LANES);
+        if (u < a.k) a.orbit[row * a.k + u] = (status == 0 && id >= 0) ? (int64_t)local_j : (int64_t)a.k;
+    }
+}
+
 }  // namespace
+
+extern "C" int ugs_graphlet_labelled(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
+                                     const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_labels, int64_t num_labels,
+                                     int64_t *d_key_out, int32_t *d_status_out, int64_t *d_orbit_out) {
+    if (k < 1 || k > UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_labelled: 1 <= k <= 8");
+    if (rows < 0 || num_cols < 0 || (num_cols > 0 && row_stride < num_cols))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_labelled: rows >= 0, num_cols >= 0, row_stride >= num_cols");
+    if (num_labels < 0 || (num_labels > 0 && !d_labels)) return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_labelled: num_labels >= 0, and labels for num_labels > 0");
+    if (rows == 0) return UGS_OK;
+    if (!d_nodes || !d_edge_ptr || !d_key_out || !d_status_out || (num_cols > 0 && !d_edge_index))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_labelled: null pointer");
+    const int64_t per_block = UGS_GL_BLOCK / UGS_GL_LANES;
+    const int64_t blocks = (rows + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffll) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_labelled: too many rows for one launch");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    GlLabelArgs a{};
+    a.nodes = d_nodes; a.edge_index = d_edge_index; a.stride = row_stride; a.num_cols = num_cols; a.edge_ptr = d_edge_ptr;
+    a.rows = rows; a.k = k; a.labels = d_labels; a.num_labels = num_labels;
+    a.key = d_key_out; a.status = d_status_out; a.orbit = d_orbit_out;
+    if (d_orbit_out) hipLaunchKernelGGL(ugs_graphlet_labelled_kernel<true>, dim3((unsigned)blocks), dim3(UGS_GL_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(ugs_graphlet_labelled_kernel<false>, dim3((unsigned)blocks), dim3(UGS_GL_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}
 
 extern "C" int ugs_graphlet_orbits(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
                                    const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_table, const int64_t *d_base,

@@ -148,6 +148,52 @@ UGS_GL_HD uint32_t rooted(uint64_t adj, int n, int u, Stack &st) {
     return search(adj, split_cells(adj, (1ull << n) - 1ull, u), n - 2, col << tri(n - 1), st);
 }
 
+// ---- node-labelled graphs (ugs_graphlet_labelled in include/ugs_mi355.h) ----------------------------------------------------------
+// The orders are restricted to those that put the labels in non-decreasing order by position.  That is the search above started
+// from the partition by label instead of from one cell: cell i holds the vertices of the i-th smallest label, so the last cell --
+// the largest label -- fills the top positions, and refinement only ever splits a cell.  The twin rule holds as it stands: tied
+// candidates share a cell, hence a label.
+
+// The root partition of the labels of vertices 0 .. n-1: one cell per distinct label, ascending, compact.
+UGS_GL_HD uint64_t label_cells(const int *labels, int n) {
+    uint64_t cells = 0;
+    for (int v = 0; v < n; ++v) {
+        int below = 0;                                 // distinct labels below v's: its cell
+        for (int w = 0; w < n; ++w) {
+            bool first = labels[w] < labels[v];
+            for (int x = 0; x < w; ++x) first = first && labels[x] != labels[w];
+            below += first;
+        }
+        cells |= 1ull << (8 * below + v);
+    }
+    return cells;
+}
+
+// The labelled canonical code of the graph `adj` on n vertices whose root partition is `cells`.
+template <class Stack>
+UGS_GL_HD uint32_t canon_cells(uint64_t adj, uint64_t cells, int n, Stack &st) {
+    if (n <= 1) return 0;
+    return search(adj, cells, n - 1, 0u, st);
+}
+
+// The labelled ROOTED code of vertex u: the smallest code over the orders that put u last and the other n - 1 vertices in
+// non-decreasing label order.  u leaves its cell wherever that is (split_cells drops a cell that becomes empty); its column is
+// taken over the cells that remain.
+template <class Stack>
+UGS_GL_HD uint32_t rooted_cells(uint64_t adj, uint64_t cells, int n, int u, Stack &st) {
+    if (n <= 1) return 0;
+    const uint32_t nu = (uint32_t)(adj >> (8 * u)) & 0xffu;
+    uint32_t col = 0;
+    int pos = 0;
+    for (int i = 0; i < UGS_GL_KMAX; ++i) {
+        const uint32_t cell = (uint32_t)(cells >> (8 * i)) & 0xffu & ~(1u << u);
+        col |= ((1u << popc8(cell & nu)) - 1u) << pos;
+        pos += popc8(cell);
+    }
+    if (n == 2) return col;                            // the root is the last level with a column
+    return search(adj, split_cells(adj, cells, u), n - 2, col << tri(n - 1), st);
+}
+
 }  // namespace ugs_gl
 
 #endif /* UGS_GRAPHLET_COMMON_H */

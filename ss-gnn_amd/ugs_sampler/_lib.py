@@ -145,6 +145,8 @@ def _load():
         "ugs_graphlet_orbits": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp],
         "ugs_graphlet_rooted_codes": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)],
         "ugs_graphlet_orbit_counts": [C.c_int, vp, C.c_int64, i64p],
+        "ugs_graphlet_labelled": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, vp],
+        "ugs_graphlet_labelled_code": [C.c_uint32, C.c_int, C.POINTER(C.c_int32), i64p, C.POINTER(C.c_uint32)],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)          # AttributeError here = the library does not export what the header declares

@@ -32,6 +32,23 @@ the graphlet degree vector of every vertex -- how often it occupies each orbit o
 
     orbit = graphlets.orbit_ids(nodes, edge_index, edge_ptr)                                        # int64 [S, k]
     gdv = graphlets.vertex_orbit_counts(nodes, orbit, batch.num_nodes, graphlets.connected_orbits(k))
+
+`labelled_keys` is the exact class of a row as a NODE-LABELLED graph (the reference's use_node_features_in_wl): two rows of one shape
+with different atoms are different classes.  The law is stated at ugs_graphlet_labelled in the same header.  The orders are restricted
+to those that put the labels in non-decreasing order by position, the labelled canonical code is the smallest adjacency code over
+them, and the key is the 128-bit number n * 2^124 + code * 2^96 + sum of L[p] * 2^(12 p), L the row's labels sorted ascending, in
+the [S, 2] int64 form of `wl.wl_hash`'s digests.  There is no fixed table of labelled classes; the vocabulary is built from the data
+by the functions that take digests, and a frozen embedding reads exact ids through the path it uses for WL ids:
+
+    labels = graphlets.compact_labels(wl.feature_labels(data.x), alphabet)        # or atom numbers: int64 [N] in [0, 4096)
+    for batch in loader:                                                         # once over the dataset
+        key, status = graphlets.labelled_keys(nodes, edge_index, edge_ptr, labels)
+        wl.extend_vocab(vocab, key, status)
+    table = wl.WLVocab(vocab, dev)
+    ids = table.lookup(*graphlets.labelled_keys(nodes, edge_index, edge_ptr, labels))        # every step: two launches
+
+Status 3: an entry >= len(node_labels) or a label outside [0, 4096); such a row has key (-1, -1).  With return_orbits the same launch
+numbers the orbits of the label-preserving automorphism group inside every row.
 """
 import ctypes as C
 
@@ -40,12 +57,14 @@ import torch
 
 from . import _select_device
 from ._lib import check, lib
-from .wl import _check_inputs, _placed
+from .wl import _check_inputs, _check_labels, _placed
 
 __all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats",
-           "orbit_ids", "num_orbits", "orbit_base", "orbit_info", "connected_orbits", "vertex_orbit_counts"]
+           "orbit_ids", "num_orbits", "orbit_base", "orbit_info", "connected_orbits", "vertex_orbit_counts",
+           "labelled_keys", "decode_labelled", "compact_labels", "LABEL_BITS"]
 
 KMAX = 8
+LABEL_BITS = 12                                         # a label's width in a labelled key: labels lie in [0, 4096)
 _NUM_CLASSES = (1, 3, 7, 18, 52, 208, 1252, 13598)     # graphs on at most k vertices, k = 1 .. 8
 _host_tables = {}                                       # n -> numpy int64 keys of the graphs on exactly n vertices
 _dev_tables = {}                                        # (device index, k) -> the table for n <= k on that GPU
@@ -335,3 +354,87 @@ def vertex_orbit_counts(nodes, orbit, num_vertices, columns):
         counted = (columns[col] == o) & (v >= 0) & (v < num_vertices)
         out.scatter_add_(0, torch.where(counted, v * width + col, torch.zeros_like(v)), counted.to(torch.int64))
     return out.view(num_vertices, width)
+
+
+def labelled_keys(nodes_sampled, edge_index_sampled, edge_ptr, node_labels, *, device=None, return_orbits=False):
+    """Key and status of every sampled subgraph as a node-labelled graph: (key int64 [S, 2], status int32 [S]), and with
+    return_orbits (key, status, orbit_local int64 [S, k]) from the same launch.
+
+    node_labels is int64 [N] on the device of the sampler tensors, with values in [0, 4096) (`compact_labels` makes them); the
+    label of a row's vertex is node_labels[entry].  key[i] holds the high and the low word of the 128-bit key of the module
+    docstring as int64 bit patterns, (-1, -1) where status != 0: two rows have the same key exactly when an isomorphism of their
+    subgraphs maps labels to equal labels.  The form is that of `wl.wl_hash`'s digests: `wl.hexdigests`, `wl.extend_vocab`,
+    `wl.WLVocab` and `WLVocab.lookup` take it as it is, and `decode_labelled` reads it back.  Status 0, 1 and 2 as `canonical`;
+    3 = an entry >= N or a label outside [0, 4096), checked after 1 and 2.
+
+    orbit_local[i, s] numbers the orbit, under the label-preserving automorphism group of row i, of the vertex that slot s is:
+    0, 1, ... by ascending (label, labelled rooted code), and k where the entry is < 0 or status != 0.  With all labels equal it is
+    `orbit_ids` minus orbit_base[class id].  Placement as `canonical`.  One launch, no synchronisation with the host."""
+    _check_inputs(nodes_sampled, edge_index_sampled, edge_ptr, 0)
+    if node_labels is None:
+        raise TypeError("node_labels must be a torch.Tensor")
+    _check_labels(nodes_sampled, None, node_labels)
+    nodes, edge_index, eptr, dev, back = _placed(nodes_sampled, edge_index_sampled, edge_ptr, device)
+    _select_device(dev, jobs=True)
+    labels = node_labels.to(dev).contiguous()
+    S, k = nodes.shape
+    N = labels.numel()
+    key = torch.empty((S, 2), dtype=torch.int64, device=dev)
+    status = torch.empty((S,), dtype=torch.int32, device=dev)
+    orbit = torch.empty((S, k), dtype=torch.int64, device=dev) if return_orbits else None
+    nodes, eptr = nodes.contiguous(), eptr.contiguous()
+    E = edge_index.size(1)
+    if E > 0 and edge_index.stride(1) != 1:
+        edge_index = edge_index.contiguous()
+    stride = edge_index.stride(0) if E > 0 else 0
+    if S > 0 or not 1 <= k <= KMAX:                     # the library states the limit
+        check(lib.ugs_graphlet_labelled(nodes.data_ptr(), edge_index.data_ptr() if E > 0 else None, stride, E, eptr.data_ptr(), S, k,
+                                        labels.data_ptr() if N > 0 else None, N, key.data_ptr(), status.data_ptr(),
+                                        orbit.data_ptr() if return_orbits and S > 0 else None))
+    if back:
+        key, status, orbit = key.cpu(), status.cpu(), orbit.cpu() if return_orbits else None
+    return (key, status, orbit) if return_orbits else (key, status)
+
+
+def decode_labelled(key):
+    """(n, code, labels) of labelled keys: `key` is int64 [..., 2] (high word, low word); n and code are int64 [...], the vertex
+    count and the labelled canonical code -- bit j (j - 1) / 2 + i is the pair i < j of the representative -- and labels is int64
+    [..., 8], the label of the representative's vertex p, ascending, -1 behind n.  A key of (-1, -1), a row of status != 0, gives
+    n = 0, code = -1 and labels of -1.  Torch bit operations on the key's device, no synchronisation."""
+    if not isinstance(key, torch.Tensor) or key.dtype != torch.int64:
+        raise TypeError("key must be an int64 torch.Tensor")
+    if key.dim() < 1 or key.size(-1) != 2:
+        raise ValueError("key must have shape [..., 2]")
+    hi, lo = key[..., 0], key[..., 1]
+    none = (hi == -1) & (lo == -1)
+    mask = (1 << LABEL_BITS) - 1
+    n = torch.where(none, torch.zeros_like(hi), (hi >> 60) & 15)
+    code = torch.where(none, torch.full_like(hi, -1), (hi >> 32) & ((1 << 28) - 1))
+    fields = [(lo >> (LABEL_BITS * p)) & mask for p in range(5)]
+    fields += [((lo >> 60) & 15) | ((hi & 255) << 4), (hi >> 8) & mask, (hi >> 20) & mask]
+    labels = torch.stack(fields, dim=-1)
+    behind = torch.arange(KMAX, dtype=torch.int64, device=key.device) >= n.unsqueeze(-1)
+    return n, code, torch.where(behind, torch.full_like(labels, -1), labels)
+
+
+def compact_labels(raw, alphabet):
+    """Maps arbitrary int64 labels onto [0, len(alphabet)): the index of raw's value in `alphabet`, -1 for a value that is not in it
+    (a row with such a vertex gets status 3).  `raw` is an int64 tensor of any shape -- `wl.feature_labels(x)`, atom numbers --
+    and `alphabet` an int64 vector of ASCENDING, DISTINCT values of at most 4096 entries (the order is not checked: that would
+    wait for the device), moved to raw's device if it is elsewhere; torch.unique(all the dataset's raw labels) is one.  A torch
+    searchsorted on raw's device, no synchronisation."""
+    for t, name in ((raw, "raw"), (alphabet, "alphabet")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64, got {t.dtype}")
+    if alphabet.dim() != 1:
+        raise ValueError("alphabet must have shape [A]")
+    A = alphabet.numel()
+    if A > 1 << LABEL_BITS:
+        raise ValueError(f"a labelled key holds {LABEL_BITS} bits per label: at most {1 << LABEL_BITS} labels, got {A}")
+    if A == 0:
+        return torch.full_like(raw, -1)
+    alphabet = alphabet.to(raw.device).contiguous()
+    at = torch.searchsorted(alphabet, raw.contiguous()).clamp_(max=A - 1)
+    return torch.where(alphabet[at] == raw, at, torch.full_like(at, -1))
