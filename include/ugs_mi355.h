@@ -1016,6 +1016,45 @@ int ugs_graphlet_labelled(const int64_t *d_nodes, const int64_t *d_edge_index, i
                           int64_t *d_key_out, int32_t *d_status_out, int64_t *d_orbit_out);
 int ugs_graphlet_labelled_code(uint32_t code, int n, const int32_t *labels, int64_t *key_out, uint32_t *rooted_out);
 
+/* ---- ugs_sampler.graphlets.census(edge_index, ptr, k, limit): the exact k-graphlet histogram of every graph of a batch, counted
+ *      where the sets are found: no set is stored, so the device memory of a call does not grow with the number of sets.
+ *      The law.
+ *        1. POPULATION.  Graphs, adjacency and the population S_g are items 1 and 2 of the law at ugs_uniform_sample_batch_begin:
+ *           graph g owns the vertices ptr[g] ... ptr[g+1]-1; only columns with both endpoints inside g's range count; adjacency is
+ *           symmetrised, a loop joins nothing and duplicate columns collapse; S_g is every connected k-subset of g, none for n < k.
+ *           The order of S_g plays no part.
+ *        2. CLASS OF A SET.  The class of a set is the class of its induced simple graph on k vertices: key (k << 28) | canonical
+ *           code and class id as ugs_graphlet_canon defines them (the set's vertices in any order: the key does not depend on it).
+ *        3. COLUMNS.  d_keys [W] holds the keys of the connected graphs on exactly k vertices, ascending: W = 1, 1, 2, 6, 21, 112,
+ *           853, 11 117 for k = 1 ... 8 (graphlets.connected_classes(k) is their class ids, ascending alike).  counts[g, c] is the
+ *           number of sets of S_g whose key is d_keys[c].  A connected set's key is always one of them.
+ *        4. IDENTITY WITH THE RECIPE.  For every healthy graph, counts[g] equals the histogram of ugs_graphlet_canon's class ids over
+ *           the rows of ugs_uniform_enumerate_begin for that graph, restricted to those columns, bit for bit; every other column of
+ *           that histogram is 0; and the sum of counts[g] is |S_g|, ugs_uniform_count_graphs' count.
+ *        5. STATUS.  graph_status (host, num_graphs entries) has ugs_uniform_count_graphs' meanings: 0 healthy; 1 a graph of at
+ *           least k vertices that ugs_uniform_sample_batch_begin refuses for its size (more than 64 vertices and over the limit in
+ *           force, or outside the wide rule); 2 a graph with more than `limit` sets.  A failed graph has a row of zeros and leaves
+ *           every other graph exact.  There is no joint budget: nothing is sized by the total, healthy graphs may together exceed
+ *           limit.
+ *        6. REFUSALS.  k outside 1 ... 8: UGS_E_UNSUPPORTED.  limit outside 1 ... 2^32: UGS_E_BAD_ARG.  The work per graph is bounded
+ *           by limit: a graph past it stops at its next flush, as in the count pass.  The other argument errors are those of
+ *           ugs_uniform_count_graphs.  num_graphs = 0 and num_cols = 0 are valid.
+ *        7. Both forms of the uniform sampler take part -- the 64-bit mask form for graphs of at most 64 vertices, the wide form for 65
+ *           ... ugs_uniform_max_vertices() under k * b <= 64 -- and ugs_uniform_set_mask_vertices steers it as it steers the samplers.
+ * ugs_graphlet_census: edge_index, ptr and graph_status are HOST pointers as in ugs_uniform_count_graphs; d_keys [num_keys] int64,
+ *      d_code_col and d_counts_out [num_graphs, num_keys] int64 are DEVICE pointers.  d_code_col is the table of
+ *      ugs_graphlet_census_table for this k, required for k <= 7 and NULL for k = 8 (a raw code of 28 bits has no table: the
+ *      canonical search runs per set).  Synchronous, no job: column buckets, adjacency, one census pass (the count pass's search)
+ *      and the clearing of failed rows on the calling thread's stream, then the status read-back.  The counts are added with integer
+ *      atomics: exact in any order.
+ * ugs_graphlet_census_table: d_code_col_out [2^(n (n-1) / 2)] uint16 on the device, 1 <= n <= 7 (UGS_E_UNSUPPORTED otherwise): entry
+ *      `code` is the column (index into d_keys) of the graph whose adjacency bits in the identity order are `code`, 0xFFFF for a
+ *      graph that is not connected.  One launch on the calling thread's stream, no synchronisation. */
+int ugs_graphlet_census(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                        int k, int64_t limit, const int64_t *d_keys, int64_t num_keys, const uint16_t *d_code_col,
+                        int64_t *d_counts_out, int32_t *graph_status);
+int ugs_graphlet_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint16_t *d_code_col_out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

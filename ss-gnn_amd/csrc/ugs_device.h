@@ -298,6 +298,16 @@ hipError_t ugs_uniform_count(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
 hipError_t ugs_uniform_enum_keys(UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
 hipError_t ugs_uniform_enum_rows(const UgsUniCall &c, const UgsUniWide &w, hipStream_t s);
 hipError_t ugs_uniform_enum_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *edge_index, int64_t *edge_src, int64_t ld, hipStream_t s);
+// ugs_graphlet_census (law in include/ugs_mi355.h): count's column buckets and adjacency, then the census pass in the count pass's
+// place -- the same search, every completed set classified and counted into counts[g, column]; gcount as count leaves it; the row of a
+// graph past the budget is cleared behind it.
+struct UgsCensus {
+    const uint16_t *code_col;                // [2^(k (k-1) / 2)] raw adjacency code -> column, 0xFFFF: not connected; nullptr: canonical search per set
+    const int64_t *keys;                     // [W] ascending keys of the connected graphs on exactly k vertices: the columns
+    int64_t W;
+    unsigned long long *counts;              // [G, W]
+};
+hipError_t ugs_uniform_census(UgsUniCall &c, const UgsUniWide &w, const UgsCensus &z, hipStream_t s);
 
 // ---- the population cache (ugs_uniform_population_*): the sorted keys of a graph kept on the device across calls ----
 // A 64-bit fingerprint of a graph's adjacency: the sum over its non-zero bitmap words of a mix of (word, position), the bitmap being

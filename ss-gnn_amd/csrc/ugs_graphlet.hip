@@ -21,6 +21,9 @@
 //
 // ugs_graphlet_labelled_kernel (law: ugs_graphlet_labelled in the same header): node-labelled keys, and the
 // orbits of the label-preserving automorphisms, by the same searches started from the partition by label; described at the kernel.
+//
+// ugs_graphlet_census_table_kernel (ugs_graphlet_census in the same header): the column of every raw code of
+// n <= 7 vertices, the table the census kernels of ugs_uniform.hip classify a set with; described at the kernel.
 #include "ugs_device.h"
 #include "ugs_graphlet_common.h"
 #include "../../include/ugs_mi355.h"
@@ -355,7 +358,39 @@ __global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_labelled_kernel(GlL
     }
 }
 
+// ugs_graphlet_census_table_kernel (ugs_graphlet_census in the header): one lane per raw adjacency code of n
+// vertices.  It runs the whole canonical search alone -- the table is built once per device and n, 2^21 codes at most -- and a binary
+// search among the ascending keys of the connected graphs on n vertices gives the code's column, 0xFFFF for a graph that is not one.
+__global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_census_table_kernel(int n, const int64_t *keys, int64_t num_keys, uint16_t *out) {
+    __shared__ uint64_t cells_sh[UGS_GL_KMAX * UGS_GL_BLOCK];
+    const int tid = (int)threadIdx.x;
+    const uint32_t code = blockIdx.x * UGS_GL_BLOCK + (uint32_t)tid;
+    if (code >> ugs_gl::tri(n)) return;                          // no barrier below: a lane's LDS column is its own
+    LdsStack st{cells_sh + tid};
+    const int64_t key = ((int64_t)n << 28) | (int64_t)ugs_gl::canon(ugs_gl::adj_of_code(code, n), n, st);
+    int64_t lo_i = 0, hi_i = num_keys;                           // first key >= key
+    while (lo_i < hi_i) {
+        const int64_t mid = lo_i + ((hi_i - lo_i) >> 1);
+        if (keys[mid] < key) lo_i = mid + 1; else hi_i = mid;
+    }
+    out[code] = lo_i < num_keys && keys[lo_i] == key ? (uint16_t)lo_i : (uint16_t)0xFFFFu;
+}
+
 }  // namespace
+
+extern "C" int ugs_graphlet_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint16_t *d_code_col_out) {
+    if (n < 1 || n >= UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_census_table: 1 <= n <= 7");
+    if (!d_keys || !d_code_col_out || num_keys < 1 || num_keys >= 0xFFFF)
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_census_table: keys (1 ... 65534 of them) and the output are needed");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    const uint32_t codes = 1u << ugs_gl::tri(n);
+    hipLaunchKernelGGL(ugs_graphlet_census_table_kernel, dim3((codes + UGS_GL_BLOCK - 1) / UGS_GL_BLOCK), dim3(UGS_GL_BLOCK), 0, s, n,
+                       d_keys, num_keys, d_code_col_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}
 
 extern "C" int ugs_graphlet_labelled(const int64_t *d_nodes, const int64_t *d_edge_index, int64_t row_stride, int64_t num_cols,
                                      const int64_t *d_edge_ptr, int64_t rows, int k, const int64_t *d_labels, int64_t num_labels,

@@ -83,15 +83,17 @@ int ugs_uniform_set_mask_vertices(int n, int *previous) {
 // is handed out.
 // UNI_DISTINCT (ugs_uniform_distinct_begin): UNI_SAMPLE with per-graph seeds and uni_draw_distinct for the draws; valid_out[g] =
 // min(m, |S_g|) from the per-graph counts that come back with the status words.
-enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE, UNI_DISTINCT };
+// UNI_CENSUS (ugs_graphlet_census): UNI_COUNT with the census pass in the count pass's place; `census` names the tables and the
+// device counts, counts_out may be null.
+enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE, UNI_DISTINCT, UNI_CENSUS };
 using UniPopulate = std::function<int(const UgsUniCall &c, const UgsUniWide &w, const std::vector<UgsUniGraph> &gd, const std::vector<int64_t> &gsize,
                                       const int32_t *graph_status, const DeviceCtx &dc)>;
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
                          ugs_job **job_out, int64_t *total_edges_out, int what = UNI_SAMPLE, int64_t cap = UGS_UNI_BUDGET,
                          int64_t *rows_out = nullptr, int64_t *counts_out = nullptr, const UniPopulate *populate = nullptr,
-                         int64_t *valid_out = nullptr) {
-    if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
+                         int64_t *valid_out = nullptr, const UgsCensus *census = nullptr) {
+    if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE && what != UNI_CENSUS) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
         return fail(UGS_E_BAD_ARG, what == UNI_DISTINCT ? "bad arguments to sample_distinct" : "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     const bool per_graph = seeds != nullptr || what != UNI_SAMPLE;
@@ -135,7 +137,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     }
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
-    const bool sampling = what == UNI_SAMPLE || what == UNI_DISTINCT, counting = what == UNI_COUNT;
+    const bool sampling = what == UNI_SAMPLE || what == UNI_DISTINCT, counting = what == UNI_COUNT || what == UNI_CENSUS;
     const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? cap : 0;   // (enumerate: m = 0, its rows come later)
     const int64_t keys = counting ? 0 : budget;                         // counting stores no keys and scans nothing
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
@@ -206,7 +208,10 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     if (!sampling) {
         // the count pass (count: nothing else; enumerate: through the sorts), then the first read-back: the graphs' counts and sizes
         std::vector<int64_t> gsize(!counting && nv > 0 ? (size_t)G : 0, 0);
-        if (e == hipSuccess) e = counting ? ugs_uniform_count(c, w, dc.stream) : ugs_uniform_enum_keys(c, w, dc.stream);
+        if (e == hipSuccess)
+            e = what == UNI_CENSUS ? ugs_uniform_census(c, w, *census, dc.stream)
+                : counting     ? ugs_uniform_count(c, w, dc.stream)
+                               : ugs_uniform_enum_keys(c, w, dc.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
         if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
         if (e == hipSuccess && !gsize.empty()) e = hipMemcpyAsync(gsize.data(), c.gsize, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
@@ -215,7 +220,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
         for (int64_t g = 0; g < G; ++g) {
             const bool past = !gcount.empty() && gd[(size_t)g].enumerable && gcount[(size_t)g] > budget;
             graph_status[g] = too_big[(size_t)g] ? 1 : past ? 2 : 0;
-            if (counting) counts_out[g] = graph_status[g] ? -1 : gcount.empty() ? 0 : gcount[(size_t)g];
+            if (counting && counts_out) counts_out[g] = graph_status[g] ? -1 : gcount.empty() ? 0 : gcount[(size_t)g];
         }
         if (counting) return bail(UGS_OK);
         if (status[1])
@@ -307,6 +312,21 @@ int ugs_uniform_count_graphs(const int64_t *edge_index, int64_t row_stride, int6
     if (num_graphs > 0 && (!counts_out || !graph_status)) return fail(UGS_E_BAD_ARG, "count_graphs needs counts_out and graph_status");
     return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_COUNT, limit,
                          nullptr, counts_out);
+}
+
+// ---- ugs_sampler.graphlets.census: the exact k-graphlet histogram of every graph, no set stored (the law is stated in include/ugs_mi355.h) ----
+int ugs_graphlet_census(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,
+                        int64_t limit, const int64_t *d_keys, int64_t num_keys, const uint16_t *d_code_col, int64_t *d_counts_out,
+                        int32_t *graph_status) {
+    if (k < 1 || k > 8) return fail(UGS_E_UNSUPPORTED, "graphlet_census: 1 <= k <= 8");
+    if (limit < 1 || limit > ((int64_t)1 << 32)) return fail(UGS_E_BAD_ARG, "limit must be 1 ... 2^32 (got " + std::to_string(limit) + ")");
+    if (!d_keys || num_keys < 1 || num_keys >= 0xFFFF) return fail(UGS_E_BAD_ARG, "graphlet_census needs the keys of its columns, 1 ... 65534 of them");
+    if ((k < 8) != (d_code_col != nullptr)) return fail(UGS_E_BAD_ARG, "graphlet_census takes the code table for k <= 7 and none for k = 8");
+    if (num_graphs > 0 && (!d_counts_out || !graph_status)) return fail(UGS_E_BAD_ARG, "graphlet_census needs counts_out and graph_status");
+    UgsCensus z{};
+    z.code_col = d_code_col; z.keys = d_keys; z.W = num_keys; z.counts = reinterpret_cast<unsigned long long *>(d_counts_out);
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_CENSUS, limit,
+                         nullptr, nullptr, nullptr, nullptr, &z);
 }
 
 int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,

@@ -38,7 +38,15 @@
 //   uni_adj / uni_wadj + uni_pop_check                        (check only) the batch's adjacency against the stored fingerprints
 //   uni_draw / uni_draw_graphs                                from the sizes the host staged
 //   uni_pop_rows / uni_wpop_rows + scan, uni_pop_fill / uni_wpop_fill (finish)    a 16-lane group per row
+//
+// Graphlet census (ugs_graphlet_census): column buckets and adjacency as above, then in the count pass's place
+//   uni_census_esu / uni_census_wesu    the same search with the raw adjacency code of the placed vertices carried down the levels;
+//                                       every completed set is classified (k <= 7: one load from a code -> column table; k = 8:
+//                                       ugs_gl::canon and a search among the connected keys) and counted, runs merged per lane, into
+//                                       the workgroup's LDS counters (k <= 7) or the graph's row (k = 8); nothing is stored per set
+//   uni_census_clear                    the row of a graph past the limit
 #include "ugs_device.h"
+#include "ugs_graphlet_common.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1037,6 +1045,320 @@ __global__ __launch_bounds__(UNI_BLOCK) void uni_pop_loops(UgsUniCall c, const u
     if (want && gd.enumerable && fp != want[g]) atomicMax((unsigned long long *)&c.status[3], (unsigned long long)(c.G - g));
 }
 
+// ---- graphlet census (ugs_graphlet_census): the count pass's search, every completed set classified where it is found ----
+// The raw code of a set is the adjacency code (ugs_graphlet_canon's bit layout) of its vertices in the order the search placed them:
+// the vertex placed at position j contributes column j, its adjacency to positions 0 .. j-1.  The search keeps the adjacency rows of
+// the placed vertices (row[i]; the wide form: this lane's word of them), and since adjacency is symmetric bit w of row[i] is the
+// adjacency of ANY vertex w to position i: a level adds one column to the code, and at k - 1 placed vertices every member of ext
+// adds only its own.  KFIX = 0: k <= 7 at run time, a set's column is code_col[raw code]; KFIX = 8: k = 8, the canonical search per
+// set (one leaf depth, so one inlined copy of it) and a binary search among the connected keys.
+constexpr int CEN_ROWS = UGS_GL_KMAX - 1;
+constexpr int CEN_MEMO_BITS = 9, CEN_MEMO = 1 << CEN_MEMO_BITS;   // k = 8: classified codes a workgroup remembers (4 KiB of LDS)
+constexpr int CEN_MASK_BLOCK = 64;            // the mask form: one wave per item (root, first extension), lane = second extension vertex
+
+struct CenStack {                             // ugs_gl's per-level words of one thread, in LDS as [level][thread]
+    uint64_t *base;
+    int stride;
+    __device__ __forceinline__ void put(int level, uint64_t v) { base[level * stride] = v; }
+    __device__ __forceinline__ uint64_t get(int level) const { return base[level * stride]; }
+};
+
+// where a lane's classified sets go.  Equal columns in a row are merged into one add (a clique puts every set in one column).
+template <int KFIX>
+struct CenSink {
+    const uint16_t *code_col;
+    const int64_t *keys;
+    uint32_t W;
+    unsigned long long *hist;                 // KFIX = 0: the workgroup's W counters in LDS; KFIX = 8: the graph's row of counts
+    CenStack st;
+    uint32_t run_col, run;                    // the column of the last sets and how many of them are not yet added
+    uint32_t last_code, last_col;             // KFIX = 8: the last raw code classified (~0: none) and its column
+    unsigned long long *memo;                 // KFIX = 8: the workgroup's CEN_MEMO classified codes in LDS, behind the search's words
+};
+
+template <int KFIX>
+__device__ __forceinline__ void cen_flush(CenSink<KFIX> &s) {
+    if (s.run && s.run_col < s.W) atomicAdd(&s.hist[s.run_col], (unsigned long long)s.run);
+    s.run = 0;
+}
+
+template <int KFIX>
+__device__ __forceinline__ void cen_emit(CenSink<KFIX> &s, uint32_t code) {
+    uint32_t col;
+    if constexpr (KFIX == 0) {
+        col = s.code_col[code];
+    } else if (code == s.last_code) {                              // siblings at a leaf often attach alike (always in a clique or a
+        col = s.last_col;                                           // complete bipartite graph): the search runs once per distinct code
+    } else {
+        // the workgroup's memo, direct-mapped: an entry is (code << 32) | column in one 64-bit word, so whatever lane wrote it last it
+        // is whole, and it answers only for the code it names.  A column depends on the code alone, not on the graph.
+        volatile unsigned long long *slot = s.memo + ((code * 0x9E3779B1u) >> (32 - CEN_MEMO_BITS));
+        const unsigned long long seen = *slot;
+        if ((uint32_t)(seen >> 32) == code) {
+            col = (uint32_t)seen;
+        } else {
+            const int64_t key = ((int64_t)KFIX << 28) | (int64_t)ugs_gl::canon(ugs_gl::adj_of_code(code, KFIX), KFIX, s.st);
+            uint32_t lo = 0, hi = s.W;                              // first column key >= key
+            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s.keys[mid] < key) lo = mid + 1; else hi = mid; }
+            col = lo < s.W && s.keys[lo] == key ? lo : 0xFFFFu;
+            *slot = ((unsigned long long)code << 32) | col;
+        }
+        s.last_code = code; s.last_col = col;
+    }
+    if (col != s.run_col) { cen_flush(s); s.run_col = col; }
+    ++s.run;
+}
+
+// column of a vertex against the D placed ones: `bit` is the vertex (the wide form: its bit in this lane's word)
+template <int D>
+__device__ __forceinline__ uint32_t cen_column(const uint64_t (&row)[CEN_ROWS], int bit) {
+    uint32_t col = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) col |= (uint32_t)((row[i] >> bit) & 1ull) << i;
+    return col;
+}
+
+struct CenMask {
+    const uint64_t *adj;          // the graph's neighbour masks
+    uint64_t abv;                 // the vertices above the root
+    int k;
+    uint64_t row[CEN_ROWS];       // neighbour masks of the placed vertices, by position
+    uint64_t cnt, flushed;        // this lane's sets, and how many of them it has added to the graph's running total
+    unsigned long long *ctr;
+    unsigned long long budget;
+    bool stop;                    // the graph is past the limit
+};
+
+// D = k - 1 vertices are placed: every member of ext completes a set
+template <int D, int KFIX>
+__device__ __forceinline__ void cen_last(CenMask &x, CenSink<KFIX> &s, uint64_t ext, uint32_t code) {
+    for (uint64_t e = ext; e; e &= e - 1)
+        cen_emit(s, code | (cen_column<D>(x.row, __ffsll((unsigned long long)e) - 1) << ugs_gl::tri(D)));
+    x.cnt += (uint64_t)__popcll(ext);
+    if (x.cnt - x.flushed >= 4096) {                                // bounded work for a graph over the limit, as in uni_esu
+        cen_flush(s);
+        const unsigned long long add = x.cnt - x.flushed;
+        x.flushed = x.cnt;
+        if (atomicAdd(x.ctr, add) + add > x.budget) x.stop = true;
+    }
+}
+
+template <int D, int KFIX>
+__device__ __forceinline__ void cen_level(CenMask &x, CenSink<KFIX> &s, uint64_t ext, uint64_t nb, uint32_t code) {
+    if constexpr (KFIX != 0 && D == KFIX - 1) {
+        cen_last<D, KFIX>(x, s, ext, code);
+    } else {
+        if constexpr (KFIX == 0) {
+            if (D == x.k - 1) { cen_last<D, KFIX>(x, s, ext, code); return; }
+        }
+        if constexpr (D < CEN_ROWS) {
+            while (ext && !x.stop) {
+                const int w = __ffsll((unsigned long long)ext) - 1;
+                ext &= ext - 1;
+                const uint64_t aw = x.adj[w];
+                const uint32_t col = cen_column<D>(x.row, w);
+                x.row[D] = aw;
+                cen_level<D + 1, KFIX>(x, s, ext | (aw & ~nb & x.abv), nb | aw, code | (col << ugs_gl::tri(D)));
+            }
+        }
+    }
+}
+
+// One workgroup (one wave) per item (root v, first extension w0) of uni_esu; lane j owns the sets whose next vertex, the first taken
+// from the extension set of {v, w0}, is vertex j.  (k <= 3 has no such level: lane 0 does the item.)  A clique's sets crowd into the
+// items of its lowest roots; this split gives them 64 times the lanes of the count pass's.  A workgroup whose w0 is no extension of
+// v leaves at once.
+template <int KFIX>
+__global__ __launch_bounds__(CEN_MASK_BLOCK) void uni_census_esu(UgsUniCall c, UgsCensus z) {
+    extern __shared__ unsigned long long cen_sh[];                  // KFIX = 0: W counters; KFIX = 8: the search's [8][64] words, the memo
+    const int64_t vi = (int64_t)(blockIdx.x >> 6);
+    const int w0 = (int)(blockIdx.x & 63), j = (int)threadIdx.x;
+    const int32_t gi = c.vgraph[vi];
+    const UgsUniGraph gd = c.graphs[gi];
+    const int v = (int)(vi - gd.vbase);
+    const int k = KFIX != 0 ? KFIX : c.k;
+    CenMask x;
+    x.adj = c.adj + gd.vbase; x.abv = above_mask(v); x.k = k;
+    const uint64_t av = x.adj[v];
+    const uint64_t ext1 = av & x.abv;
+    if (k == 1 ? w0 != 0 : !((ext1 >> w0) & 1)) return;            // the whole workgroup: no barrier is left behind
+    const uint32_t W = (uint32_t)z.W;
+    CenSink<KFIX> s;
+    s.memo = cen_sh + UGS_GL_KMAX * CEN_MASK_BLOCK;
+    if (KFIX == 0) {
+        for (uint32_t i = (uint32_t)j; i < W; i += CEN_MASK_BLOCK) cen_sh[i] = 0;
+    } else {
+        for (int i = j; i < CEN_MEMO; i += CEN_MASK_BLOCK) s.memo[i] = ~0ull;      // no code has 32 bits
+    }
+    __syncthreads();
+    s.code_col = z.code_col; s.keys = z.keys; s.W = W;
+    s.hist = KFIX == 0 ? cen_sh : z.counts + (int64_t)gi * (int64_t)W;
+    s.st.base = (uint64_t *)cen_sh + j; s.st.stride = CEN_MASK_BLOCK;
+    s.run_col = 0xFFFFu; s.run = 0; s.last_code = ~0u; s.last_col = 0xFFFFu;
+    x.cnt = 0; x.flushed = 0; x.stop = false;
+    x.ctr = (unsigned long long *)&c.gcount[gi]; x.budget = (unsigned long long)c.budget;
+#pragma unroll
+    for (int i = 0; i < CEN_ROWS; ++i) x.row[i] = 0;
+    if (*(volatile unsigned long long *)x.ctr <= x.budget) {        // a graph already past the limit starts nothing more
+        if constexpr (KFIX == 0) {
+            if (k <= 2 && j == 0) { cen_emit(s, k == 1 ? 0u : 1u); x.cnt = 1; }
+        }
+        if (k >= 3) {
+            const uint64_t aw = x.adj[w0];
+            const uint64_t nb1 = av | (1ull << v);
+            const uint64_t ext2 = (ext1 & above_mask(w0)) | (aw & ~nb1 & x.abv), nb2 = nb1 | aw;
+            x.row[0] = av; x.row[1] = aw;
+            if constexpr (KFIX == 0) {
+                if (k == 3 && j == 0) cen_level<2, KFIX>(x, s, ext2, nb2, 1u);
+            }
+            if (k >= 4 && ((ext2 >> j) & 1)) {
+                const uint64_t aj = x.adj[j];
+                const uint32_t col = cen_column<2>(x.row, j);
+                x.row[2] = aj;
+                cen_level<3, KFIX>(x, s, (ext2 & above_mask(j)) | (aj & ~nb2 & x.abv), nb2 | aj, 1u | (col << ugs_gl::tri(2)));
+            }
+        }
+    }
+    cen_flush(s);
+    if (x.cnt > x.flushed) atomicAdd(x.ctr, (unsigned long long)(x.cnt - x.flushed));
+    if (KFIX == 0) {
+        __syncthreads();
+        unsigned long long *dst = z.counts + (int64_t)gi * (int64_t)W;
+        for (uint32_t i = (uint32_t)j; i < W; i += CEN_MASK_BLOCK) {
+            const unsigned long long n = cen_sh[i];
+            if (n) atomicAdd(&dst[i], n);
+        }
+    }
+}
+
+struct CenWide {
+    WGroup g;                     // as the count pass carries it (out, status and b are not used)
+    uint64_t row[CEN_ROWS];       // this lane's word of the placed vertices' bitmap rows, by position
+};
+
+template <int D, int KFIX>
+__device__ __forceinline__ void wcen_last(CenWide &x, CenSink<KFIX> &s, uint64_t ext, uint32_t code) {
+    for (uint64_t e = ext; e; e &= e - 1)                           // every lane: the members in its own word
+        cen_emit(s, code | (cen_column<D>(x.row, __ffsll((unsigned long long)e) - 1) << ugs_gl::tri(D)));
+    x.g.cnt += (uint32_t)__popcll(ext);
+    bool over = false;
+    if (x.g.cnt - x.g.flushed >= 4096 / WIDE_LANES) {               // the group flushes at least every 4096 sets
+        cen_flush(s);
+        const unsigned long long add = x.g.cnt - x.g.flushed;
+        over = atomicAdd(x.g.ctr, add) + add > (unsigned long long)x.g.budget;
+        x.g.flushed = x.g.cnt;
+    }
+    if (group_ballot(x.g, over)) x.g.stop = true;
+}
+
+template <int D, int KFIX>
+__device__ __forceinline__ void wcen_level(CenWide &x, CenSink<KFIX> &s, uint64_t ext, uint64_t nb, uint32_t code) {
+    if constexpr (KFIX != 0 && D == KFIX - 1) {
+        wcen_last<D, KFIX>(x, s, ext, code);
+    } else {
+        if constexpr (KFIX == 0) {
+            if (D == x.g.k - 1) { wcen_last<D, KFIX>(x, s, ext, code); return; }
+        }
+        if constexpr (D < CEN_ROWS) {
+            while (!x.g.stop) {
+                const int w = group_take(x.g, ext);
+                if (w < 0) break;
+                const uint64_t aw = x.g.l < x.g.W ? x.g.adj[(int64_t)w * x.g.W + x.g.l] : 0ull;
+                const uint32_t col = (uint32_t)__shfl((int)cen_column<D>(x.row, w & 63), w >> 6, WIDE_LANES);   // the lane that holds w's word
+                x.row[D] = aw;
+                wcen_level<D + 1, KFIX>(x, s, ext | (aw & ~nb & x.g.abv), nb | aw, code | (col << ugs_gl::tri(D)));
+            }
+        }
+    }
+}
+
+// uni_wesu's items and groups; the 16 items of a workgroup share their root, so the workgroup counts into one set of LDS counters.
+template <int KFIX>
+__global__ __launch_bounds__(UNI_BLOCK) void uni_census_wesu(UgsUniCall c, UgsUniWide wd, UgsCensus z) {
+    extern __shared__ unsigned long long cen_sh[];                  // KFIX = 0: W counters; KFIX = 8: the search's [8][256] words, the memo
+    const int64_t item = wd.nv_mask * 64 + (int64_t)blockIdx.x * WIDE_GROUPS + (threadIdx.x / WIDE_LANES);   // < nv * 64: the grid is exact
+    const int64_t vi = item >> 6;
+    const int slot = (int)(item & 63);
+    const int32_t gi = c.vgraph[vi];
+    const UgsUniGraph gd = c.graphs[gi];
+    const uint32_t W = (uint32_t)z.W;
+    CenSink<KFIX> s;
+    s.memo = cen_sh + UGS_GL_KMAX * UNI_BLOCK;
+    if (KFIX == 0) {
+        for (uint32_t i = threadIdx.x; i < W; i += UNI_BLOCK) cen_sh[i] = 0;
+    } else {
+        for (int i = (int)threadIdx.x; i < CEN_MEMO; i += UNI_BLOCK) s.memo[i] = ~0ull;    // no code has 32 bits
+    }
+    __syncthreads();
+    s.code_col = z.code_col; s.keys = z.keys; s.W = W;
+    s.hist = KFIX == 0 ? cen_sh : z.counts + (int64_t)gi * (int64_t)W;
+    s.st.base = (uint64_t *)cen_sh + threadIdx.x; s.st.stride = UNI_BLOCK;
+    s.run_col = 0xFFFFu; s.run = 0; s.last_code = ~0u; s.last_col = 0xFFFFu;
+    const int v = (int)(vi - gd.vbase), vw = v >> 6;
+    CenWide x;
+    x.g.adj = wd.wadj + wd.wbase[gi];
+    x.g.W = (gd.n + 63) >> 6; x.g.l = threadIdx.x & (WIDE_LANES - 1); x.g.gshift = threadIdx.x & 63 & ~(WIDE_LANES - 1);
+    x.g.b = 0; x.g.k = c.k;
+    x.g.abv = x.g.l < vw ? 0ull : x.g.l == vw ? above_mask(v & 63) : ~0ull;
+    x.g.out = nullptr; x.g.cnt = 0; x.g.flushed = 0;
+    x.g.ctr = (unsigned long long *)&c.gcount[gi];
+    x.g.budget = c.budget; x.g.status = nullptr; x.g.stop = false;
+#pragma unroll
+    for (int i = 0; i < CEN_ROWS; ++i) x.row[i] = 0;
+    // a graph already past the limit starts nothing more; the lanes of a group must agree, whenever each of them read the total
+    if (!group_ballot(x.g, *(volatile unsigned long long *)x.g.ctr > (unsigned long long)c.budget)) {
+        const uint64_t av = x.g.l < x.g.W ? x.g.adj[(int64_t)v * x.g.W + x.g.l] : 0ull;
+        const uint64_t ext1 = av & x.g.abv;
+        const uint64_t nb1 = av | (x.g.l == vw ? 1ull << (v & 63) : 0ull);
+        x.row[0] = av;
+        if constexpr (KFIX == 0) {
+            if (x.g.k == 1) {
+                if (slot == 0 && x.g.l == 0) { cen_emit(s, 0u); x.g.cnt = 1; }
+            } else if (x.g.k == 2) {
+                if (slot == 0) wcen_last<1, KFIX>(x, s, ext1, 0u);
+            }
+        }
+        if (x.g.k >= 3) {
+            const uint32_t pc = (uint32_t)__popcll(ext1), incl = row_scan(pc), excl = incl - pc;
+            const uint32_t deg = (uint32_t)__shfl((int)incl, WIDE_LANES - 1, WIDE_LANES);
+            for (uint32_t r = (uint32_t)slot; r < deg && !x.g.stop; r += 64) {
+                const bool holds = excl <= r && r < incl;           // this lane's word holds the r-th member
+                int f = 0;
+                if (holds) {
+                    uint64_t t = ext1;
+                    for (uint32_t i = r - excl; i > 0; --i) t &= t - 1;
+                    f = __ffsll((unsigned long long)t) - 1;
+                }
+                const int l0 = __ffs(group_ballot(x.g, holds)) - 1;
+                f = __shfl(f, l0, WIDE_LANES);
+                const int w = l0 * 64 + f;
+                const uint64_t aw = x.g.l < x.g.W ? x.g.adj[(int64_t)w * x.g.W + x.g.l] : 0ull;
+                const uint64_t later = x.g.l < l0 ? 0ull : x.g.l == l0 ? above_mask(f) : ~0ull;   // the members of ext1 after w
+                x.row[1] = aw;
+                wcen_level<2, KFIX>(x, s, (ext1 & later) | (aw & ~nb1 & x.g.abv), nb1 | aw, 1u);
+            }
+        }
+    }
+    cen_flush(s);
+    const uint32_t rest = row_scan(x.g.cnt - x.g.flushed);
+    if (x.g.l == WIDE_LANES - 1 && rest) atomicAdd(x.g.ctr, (unsigned long long)rest);
+    if (KFIX == 0) {
+        __syncthreads();
+        unsigned long long *dst = z.counts + (int64_t)gi * (int64_t)W;
+        for (uint32_t i = threadIdx.x; i < W; i += UNI_BLOCK) {
+            const unsigned long long n = cen_sh[i];
+            if (n) atomicAdd(&dst[i], n);
+        }
+    }
+}
+
+// behind the census pass: a graph past the limit has a row of zeros
+__global__ void uni_census_clear(UgsUniCall c, UgsCensus z) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c.G * z.W) return;
+    if (c.gcount[i / z.W] > c.budget) z.counts[i] = 0;
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // uni_draw_distinct over every graph of the call; the sort's width, and with it the LDS, follows m, not the limit
@@ -1063,7 +1385,8 @@ size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget) {
 
 // The stages every entry shares, up to the per-graph sizes: column buckets, adjacency, the count pass and -- unless `count_only` --
 // scan, write pass, sorts, gstart / gsize.  count_only stops behind the count pass: it touches neither ioff nor a key array.
-static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_only, hipStream_t s) {
+// With `cen` (count_only) the census pass takes the count pass's place.
+static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_only, hipStream_t s, const UgsCensus *cen = nullptr) {
     const int64_t nv_wide = c.nv - w.nv_mask;                                  // 0: the call runs the mask form's launches only
     UgsUniCall cm = c;                                                         // the mask form's view: its own roots
     cm.nv = w.nv_mask;
@@ -1088,6 +1411,22 @@ static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_onl
         }
         const int64_t items = c.nv * 64, mitems = cm.nv * 64, witems = nv_wide * 64;
         if (c.per_graph && (e = hipMemsetAsync(c.gcount, 0, (size_t)c.G * sizeof(int64_t), s)) != hipSuccess) return e;
+        if (cen) {                                                             // k <= 7: LDS counters; k = 8: the canonical search's words and the memo
+            const bool table = cen->code_col != nullptr;
+            const size_t words = table ? (size_t)cen->W : (size_t)UGS_GL_KMAX;
+            if (mitems > 0x7fffffffll) return hipErrorInvalidConfiguration;    // one workgroup per item of the mask roots
+            if (mitems > 0) {
+                const size_t lds = (table ? words : words * CEN_MASK_BLOCK + CEN_MEMO) * sizeof(uint64_t);
+                if (table) hipLaunchKernelGGL((uni_census_esu<0>), dim3((unsigned)mitems), dim3(CEN_MASK_BLOCK), lds, s, cm, *cen);
+                else hipLaunchKernelGGL((uni_census_esu<UGS_GL_KMAX>), dim3((unsigned)mitems), dim3(CEN_MASK_BLOCK), lds, s, cm, *cen);
+            }
+            if (witems > 0) {
+                const size_t lds = (table ? words : words * UNI_BLOCK + CEN_MEMO) * sizeof(uint64_t);
+                if (table) hipLaunchKernelGGL((uni_census_wesu<0>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), lds, s, c, w, *cen);
+                else hipLaunchKernelGGL((uni_census_wesu<UGS_GL_KMAX>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), lds, s, c, w, *cen);
+            }
+            return hipGetLastError();
+        }
         if (mitems > 0) {
             if (c.k <= 8) hipLaunchKernelGGL((uni_esu<8, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
             else hipLaunchKernelGGL((uni_esu<64, false>), dim3(blocks(mitems, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, cm);
@@ -1144,6 +1483,16 @@ hipError_t ugs_uniform_fill(const UgsUniCall &c, const UgsUniWide &w, int64_t *e
 hipError_t ugs_uniform_count(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) { return uni_prepare(c, w, true, s); }
 
 hipError_t ugs_uniform_enum_keys(UgsUniCall &c, const UgsUniWide &w, hipStream_t s) { return uni_prepare(c, w, false, s); }
+
+// k = 8 goes without the table (code_col == nullptr), every smaller k with it: the host entry checks that
+hipError_t ugs_uniform_census(UgsUniCall &c, const UgsUniWide &w, const UgsCensus &z, hipStream_t s) {
+    const int64_t cells = c.G * z.W;
+    hipError_t e = cells > 0 ? hipMemsetAsync(z.counts, 0, (size_t)cells * sizeof(uint64_t), s) : hipSuccess;
+    if (e != hipSuccess) return e;
+    if ((e = uni_prepare(c, w, true, s, &z)) != hipSuccess) return e;
+    if (c.nv > 0 && cells > 0) hipLaunchKernelGGL(uni_census_clear, dim3(blocks(cells, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, z);
+    return hipGetLastError();
+}
 
 hipError_t ugs_uniform_enum_rows(const UgsUniCall &c, const UgsUniWide &w, hipStream_t s) {
     if (c.rows > 0 && w.nv_mask > 0) hipLaunchKernelGGL(uni_enum_rows, dim3(blocks(c.rows, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c);

@@ -140,6 +140,8 @@ def _load():
         "ugs_rows_last_launch": [C.c_char_p, C.c_int],
         "ugs_graphlet_canon": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, vp],
         "ugs_graphlet_table": [C.c_int, vp, C.c_int64, i64p],
+        "ugs_graphlet_census": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp],
+        "ugs_graphlet_census_table": [C.c_int, vp, C.c_int64, vp],
         "ugs_graphlet_canon_code": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)],
         "ugs_graphlet_search_stats": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "ugs_graphlet_orbits": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp],

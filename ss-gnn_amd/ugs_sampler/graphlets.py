@@ -21,6 +21,13 @@ With `uniform_sampler.enumerate_graphs` the ids give a graph's exact graphlet hi
     nodes, edge_index, edge_ptr, sample_ptr, _, _ = uniform_sampler.enumerate_graphs(batch.edge_index, batch.ptr, k, device=dev)
     hist = graphlets.histogram(graphlets.class_ids(nodes, edge_index, edge_ptr), sample_ptr, k)     # int64 [G, num_classes(k)]
 
+`census` gives the non-zero columns of that histogram in one call that stores no rows -- the sets are classified where the search
+finds them -- so a graph may hold up to 2**32 sets where an enumeration stops at 2**25 rows, and the memory of the call does not
+grow with the population.  The law is stated at ugs_graphlet_census in the same header:
+
+    counts, failed = graphlets.census(batch.edge_index, batch.ptr, k, device=dev)      # int64 [G, len(connected_classes(k))]
+    assert torch.equal(counts, hist[:, graphlets.connected_classes(k).to(dev)])
+
 `orbit_ids` says where each of a row's vertices sits inside that class: its orbit under the class's automorphism group (centre or
 leaf of a star, end or middle of a path).  The law is stated at ugs_graphlet_orbits in the same header.  The ROOTED CODE of a vertex
 is the smallest adjacency code over the orders that put it last; two vertices of a row lie in one orbit exactly when their rooted
@@ -55,13 +62,13 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _select_device
+from . import _graphs, _select_device
 from ._lib import check, lib
 from .wl import _check_inputs, _check_labels, _placed
 
 __all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats",
            "orbit_ids", "num_orbits", "orbit_base", "orbit_info", "connected_orbits", "vertex_orbit_counts",
-           "labelled_keys", "decode_labelled", "compact_labels", "LABEL_BITS"]
+           "labelled_keys", "decode_labelled", "compact_labels", "LABEL_BITS", "census", "connected_classes"]
 
 KMAX = 8
 LABEL_BITS = 12                                         # a label's width in a labelled key: labels lie in [0, 4096)
@@ -71,6 +78,8 @@ _dev_tables = {}                                        # (device index, k) -> t
 _NUM_ORBITS = (1, 3, 9, 29, 119, 663, 5759, 85023)      # orbits of the graphs on at most k vertices, k = 1 .. 8
 _host_orbit_counts = {}                                 # n -> numpy int64 orbit counts of the graphs on exactly n vertices, in table order
 _dev_bases = {}                                         # (device index, k) -> orbit_base(k) on that GPU
+_host_connected = {}                                    # k -> connected_classes(k)
+_dev_census = {}                                        # (device index, k) -> census' column keys and code -> column table on that GPU
 
 
 def _check_k(k):
@@ -394,6 +403,73 @@ def labelled_keys(nodes_sampled, edge_index_sampled, edge_ptr, node_labels, *, d
     if back:
         key, status, orbit = key.cpu(), status.cpu(), orbit.cpu() if return_orbits else None
     return (key, status, orbit) if return_orbits else (key, status)
+
+
+def connected_classes(k):
+    """The class ids of the connected graphs on exactly k vertices, ascending: int64 on the host, 1, 1, 2, 6, 21, 112, 853 and
+    11 117 of them for k = 1 .. 8.  The columns of `census`, and the only columns of a `histogram` over `enumerate_graphs` rows
+    that can be non-zero; the class-level sibling of `connected_orbits`."""
+    _check_k(k)
+    if k not in _host_connected:
+        first = num_classes(k - 1) if k > 1 else 0
+        _host_connected[k] = first + torch.nonzero(is_connected(table(k)[first:])).view(-1)
+    return _host_connected[k].clone()
+
+
+def _census_tables(dev, k):
+    """(keys of the columns int64 [W], code -> column table or None) on `dev`; the library's device and stream are selected.  The
+    table of k <= 7 is built by one launch over all 2^(k (k-1) / 2) codes, once per device and k."""
+    at = (dev.index, k)
+    if at not in _dev_census:
+        keys = table(k)[connected_classes(k)].to(dev)
+        code_col = None
+        if k < KMAX:
+            code_col = torch.empty((1 << (k * (k - 1) // 2),), dtype=torch.int16, device=dev)     # uint16 bit patterns
+            check(lib.ugs_graphlet_census_table(k, keys.data_ptr(), keys.numel(), code_col.data_ptr()))
+            torch.cuda.current_stream(dev).synchronize()                                           # later calls may run on other streams
+        _dev_census[at] = (keys, code_col)
+    return _dev_census[at]
+
+
+def census(edge_index, ptr, k, *, limit=1 << 25, device=None):
+    """The exact k-graphlet histogram of every graph of a batch: (counts int64 [G, W], failed host bool [G]), W =
+    len(connected_classes(k)), counts[g, c] the number of connected k-subsets of graph g whose class id is connected_classes(k)[c].
+
+    What histogram(class_ids(rows), sample_ptr, k)[:, connected_classes(k)] gives over `uniform_sampler.enumerate_graphs` rows, bit
+    for bit, without the rows: every set is classified where the search finds it and nothing is stored per set, so the call's memory
+    does not grow with the population and a graph may hold up to `limit` sets, 1 ... 2**32 (ValueError otherwise), the bound of
+    `count_graphs`, not the 2**25 rows of an enumeration.  The law is stated at ugs_graphlet_census in include/ugs_mi355.h.  A graph
+    the samplers refuse for its size (`uniform_sampler.set_max_vertices` raises that limit for the census too) or with more than
+    `limit` sets has failed[g] = True and a row of zeros, and leaves the other graphs exact; there is no joint budget.  Arguments and
+    their errors are those of `count_graphs`.  counts is on the device of `edge_index`, or on `device`; for CPU tensors without
+    `device` the work runs on the current GPU and counts comes back on the CPU.  One synchronous call on torch's current stream.
+    For k <= 7 a set's class is one table load and the call is several times faster than the recipe; at k = 8 it is a canonical search
+    per set, slower than the recipe wherever the recipe can hold the rows."""
+    _check_k(k)
+    limit = int(limit)
+    if not 1 <= limit <= 1 << 32:
+        raise ValueError(f"limit must be 1 ... 2**32, got {limit}")
+    for t, name in ((edge_index, "edge_index"), (ptr, "ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _graphs.check_int64(edge_index, ptr)
+    back = device is None and edge_index.device.type != "cuda"
+    dev = torch.device(device) if device is not None else edge_index.device if not back else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError("device= must be a GPU device")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    keep, p, stride, e = _graphs._edge_index_view(edge_index.cpu())
+    pt = ptr.cpu().contiguous()
+    G = pt.numel() - 1
+    _graphs._select_device(dev, jobs=True)
+    keys, code_col = _census_tables(dev, k)
+    counts = torch.empty((max(G, 0), keys.numel()), dtype=torch.int64, device=dev)
+    status = np.zeros(max(G, 1), dtype=np.int32)
+    check(lib.ugs_graphlet_census(p, stride, e, pt.data_ptr(), G, k, limit, keys.data_ptr(), keys.numel(),
+                                  code_col.data_ptr() if code_col is not None else None, counts.data_ptr() if G > 0 else None,
+                                  status.ctypes.data))
+    return counts.cpu() if back else counts, torch.from_numpy(status[:max(G, 0)] != 0)
 
 
 def decode_labelled(key):
