@@ -1055,6 +1055,48 @@ int ugs_graphlet_census(const int64_t *edge_index, int64_t row_stride, int64_t n
                         int64_t *d_counts_out, int32_t *graph_status);
 int ugs_graphlet_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint16_t *d_code_col_out);
 
+/* ---- ugs_sampler.graphlets.vertex_census(edge_index, ptr, k, limit): the exact k-graphlet degree vector (GDV) of every vertex of a
+ *      batch -- how often the vertex sits in each automorphism orbit of each connected k-graphlet -- counted where the sets are found:
+ *      no set is stored.  The law.
+ *        1. POPULATION.  As item 1 of ugs_graphlet_census: graphs, adjacency and S_g are those of ugs_uniform_sample_batch_begin.
+ *        2. ORBIT OF A MEMBER.  The orbit of member u of a set is the orbit id ugs_graphlet_orbits gives to u in the set's induced simple
+ *           graph on k vertices.  It does not depend on the order of the set.
+ *        3. COLUMNS.  There are O = 1, 1, 3, 11, 58, 407, 4306 columns for k = 1 ... 7: column c is graphlets.connected_orbits(k)[c], the
+ *           ids of the orbits of the connected graphs on exactly k vertices, ascending.  Equivalently: with W and the class columns of
+ *           ugs_graphlet_census item 3, and obase [W + 1] the exclusive prefix sum of the orbit counts (ugs_graphlet_orbit_counts) of
+ *           those W classes in key order, obase[W] = O, the column of a member is obase[class column of the set] + its LOCAL ORBIT
+ *           INDEX: the number of distinct rooted codes (ugs_graphlet_orbits item 2) of the set's graph below the member's.
+ *           gdv[v, c], v a vertex id of the batch (0 <= v < N = ptr[num_graphs]), is the number of sets of S_g, g the graph that owns
+ *           v, that contain v and in which v's column is c.  Rows of vertices below ptr[0] are zero.
+ *        4. IDENTITY WITH THE RECIPE.  For healthy graphs gdv equals graphlets.vertex_orbit_counts(nodes, orbit ids, N,
+ *           connected_orbits(k)) over the rows of ugs_uniform_enumerate_begin and ugs_graphlet_orbits' ids of them, bit for bit.
+ *        5. IDENTITY WITH THE CENSUS.  For every graph g and every column c, of orbit q: the sum over g's vertices of gdv[v, c] = (number
+ *           of vertices of q) * ugs_graphlet_census' count of q's class in g.  The sum of row v is the number of sets that contain v.
+ *        6. STATUS, LIMIT AND REFUSALS.  graph_status as ugs_graphlet_census item 5; all vertices of a failed graph have rows of zeros,
+ *           every other vertex stays exact; no joint budget.  k = 8 and k outside 1 ... 8: UGS_E_UNSUPPORTED, before any device work
+ *           (k = 8 would be 72 489 columns a vertex and a canonical search a set).  limit outside 1 ... 2^32, ptr[0] < 0:
+ *           UGS_E_BAD_ARG.  The work per graph is bounded by limit as in the census.  The other argument errors are those of
+ *           ugs_uniform_count_graphs.  num_graphs = 0 and num_cols = 0 are valid.  Both forms of the uniform sampler take part, as
+ *           ugs_graphlet_census item 7 says.
+ * ugs_graphlet_vertex_census: edge_index, ptr and graph_status are HOST pointers as in ugs_uniform_count_graphs; d_obase [num_keys + 1]
+ *      int64 (item 3; num_keys = W, num_orbits = O = its last entry), d_table (ugs_graphlet_vertex_census_table for this k) and
+ *      d_gdv_out [N, O] int64 are DEVICE pointers.  The pass reads no keys: the table holds the class columns.  Synchronous, no job:
+ *      gdv is zeroed, then column buckets, adjacency, one pass (the count pass's search) and the clearing of failed graphs' rows on
+ *      the calling thread's stream, then the status read-back.  The counts are added with integer atomics: exact in any order.
+ * ugs_graphlet_vertex_census_table: d_table_out [2^(n (n-1) / 2)] uint32 on the device, 1 <= n <= 7 (UGS_E_UNSUPPORTED otherwise),
+ *      d_keys [num_keys] the ascending keys of the connected graphs on exactly n vertices.  Entry `code` describes the graph whose
+ *      adjacency bits in the identity order are `code`: bits 0 ... 9 its class column (index into d_keys), bits 10 + 3 p ... 12 + 3 p
+ *      the local orbit index of vertex p, p < n; 0xFFFFFFFF for a graph that is not connected.  One launch on the calling thread's
+ *      stream, no synchronisation.
+ * ugs_graphlet_vertex_census_entry: HOST function, no device work: *out = that entry, computed by the same code
+ *      (ugs_gl::vertex_entry in csrc/ugs_graphlet_common.h) from the host's own table of connected keys.  UGS_E_BAD_ARG for a code with
+ *      bits above n (n-1) / 2. */
+int ugs_graphlet_vertex_census(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
+                               int k, int64_t limit, int64_t num_keys, const int64_t *d_obase, int64_t num_orbits,
+                               const uint32_t *d_table, int64_t *d_gdv_out, int32_t *graph_status);
+int ugs_graphlet_vertex_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint32_t *d_table_out);
+int ugs_graphlet_vertex_census_entry(uint32_t code, int n, uint32_t *out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

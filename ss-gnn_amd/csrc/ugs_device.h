@@ -308,6 +308,16 @@ struct UgsCensus {
     unsigned long long *counts;              // [G, W]
 };
 hipError_t ugs_uniform_census(UgsUniCall &c, const UgsUniWide &w, const UgsCensus &z, hipStream_t s);
+// ugs_graphlet_vertex_census (law in include/ugs_mi355.h): the same, per vertex -- every completed set adds one to k cells of gdv, the
+// cell of member u being [ptr[g] + u, obase[column] + local orbit index of u's position]; the rows of a graph past the budget are
+// cleared behind the pass.
+struct UgsVertexCensus {
+    const uint32_t *table;                   // [2^(k (k-1) / 2)] raw adjacency code -> ugs_gl::vertex_entry, k <= 7
+    const int64_t *obase;                    // [W + 1] first column of each connected class's orbits; obase[W] = O
+    int64_t W, O, N;                         // classes, columns, rows (= ptr[G])
+    unsigned long long *gdv;                 // [N, O]
+};
+hipError_t ugs_uniform_vertex_census(UgsUniCall &c, const UgsUniWide &w, const UgsVertexCensus &z, hipStream_t s);
 
 // ---- the population cache (ugs_uniform_population_*): the sorted keys of a graph kept on the device across calls ----
 // A 64-bit fingerprint of a graph's adjacency: the sum over its non-zero bitmap words of a mix of (word, position), the bitmap being

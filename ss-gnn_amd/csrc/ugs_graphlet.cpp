@@ -1,6 +1,7 @@
 // ugs_graphlet.cpp -- host side of ugs_sampler.graphlets (C ABI: ugs_graphlet_canon_code / ugs_graphlet_table and, for the orbits,
-// ugs_graphlet_rooted_codes / ugs_graphlet_orbit_counts and, for node-labelled graphs, ugs_graphlet_labelled_code in
-// include/ugs_mi355.h, which states the laws; kernels: ugs_graphlet.hip; the search all share: ugs_graphlet_common.h).
+// ugs_graphlet_rooted_codes / ugs_graphlet_orbit_counts, for node-labelled graphs ugs_graphlet_labelled_code and, for the vertex
+// census, ugs_graphlet_vertex_census_entry in include/ugs_mi355.h, which states the laws; kernels: ugs_graphlet.hip; the search all
+// share: ugs_graphlet_common.h).
 // No device work here: the table of all graphs on n vertices, and their orbit counts, are built on the host, once per process and n.
 #include "ugs_host_internal.h"
 #include "ugs_graphlet_common.h"
@@ -39,6 +40,7 @@ int rooted_codes(uint32_t code, int n, uint32_t *out) {
 std::mutex g_table_mu;
 std::vector<uint32_t> g_codes[UGS_GL_KMAX + 1];       // [n]: canonical codes of all graphs on n vertices, ascending; empty = not built
 std::vector<int64_t> g_orbits[UGS_GL_KMAX + 1];       // [n]: the number of orbits of each of them; empty = not built
+std::vector<int64_t> g_connected[UGS_GL_KMAX + 1];    // [n]: the keys of the connected ones among them, ascending; empty = not built
 
 // Every graph on n vertices is a graph on n - 1 vertices plus a last vertex, and the last vertex's column is the top n - 1 bits: all
 // (n-1)-classes times all 2^(n-1) neighbour sets reach every n-class.  Called with the mutex held.
@@ -114,6 +116,26 @@ int ugs_graphlet_orbit_counts(int n, int64_t *counts_out, int64_t capacity, int6
     }
     *count_out = (int64_t)orbits.size();
     if (capacity >= (int64_t)orbits.size()) std::copy(orbits.begin(), orbits.end(), counts_out);
+    return UGS_OK;
+}
+
+int ugs_graphlet_vertex_census_entry(uint32_t code, int n, uint32_t *out) {
+    if (n < 1 || n >= UGS_GL_KMAX) return fail(UGS_E_UNSUPPORTED, "graphlet_vertex_census_entry: 1 <= n <= 7");
+    if (!out) return fail(UGS_E_BAD_ARG, "graphlet_vertex_census_entry: null output pointer");
+    if ((uint64_t)code >> ugs_gl::tri(n)) return fail(UGS_E_BAD_ARG, "graphlet_vertex_census_entry: the code has bits above n(n-1)/2");
+    const int64_t *keys;
+    int64_t num_keys;
+    {
+        std::lock_guard<std::mutex> lock(g_table_mu);
+        std::vector<int64_t> &conn = g_connected[n];  // never changed once built: read below without the lock
+        if (conn.empty())
+            for (uint32_t c : codes_of(n))
+                if (ugs_gl::connected(ugs_gl::adj_of_code(c, n), n)) conn.push_back(((int64_t)n << 28) | (int64_t)c);
+        keys = conn.data();
+        num_keys = (int64_t)conn.size();
+    }
+    HostStack st;
+    *out = ugs_gl::vertex_entry(code, n, keys, num_keys, st);
     return UGS_OK;
 }
 

@@ -24,6 +24,9 @@
 //
 // ugs_graphlet_census_table_kernel (ugs_graphlet_census in the same header): the column of every raw code of
 // n <= 7 vertices, the table the census kernels of ugs_uniform.hip classify a set with; described at the kernel.
+//
+// ugs_graphlet_vertex_census_table_kernel (ugs_graphlet_vertex_census in the same header): the column and the
+// orbit of every position of every raw code of n <= 7 vertices, the table of the vertex census kernels; described at the kernel.
 #include "ugs_device.h"
 #include "ugs_graphlet_common.h"
 #include "../../include/ugs_mi355.h"
@@ -376,7 +379,33 @@ __global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_census_table_kernel
     out[code] = lo_i < num_keys && keys[lo_i] == key ? (uint16_t)lo_i : (uint16_t)0xFFFFu;
 }
 
+// ugs_graphlet_vertex_census_table_kernel (ugs_graphlet_vertex_census in the header): one lane per raw
+// adjacency code of n vertices, as above, and besides the column the local orbit index of every position: ugs_gl::vertex_entry, the
+// code path of the host's ugs_graphlet_vertex_census_entry.  n + 1 searches a lane, once per device and n.
+__global__ __launch_bounds__(UGS_GL_BLOCK) void ugs_graphlet_vertex_census_table_kernel(int n, const int64_t *keys, int64_t num_keys, uint32_t *out) {
+    __shared__ uint64_t cells_sh[UGS_GL_KMAX * UGS_GL_BLOCK];
+    const int tid = (int)threadIdx.x;
+    const uint32_t code = blockIdx.x * UGS_GL_BLOCK + (uint32_t)tid;
+    if (code >> ugs_gl::tri(n)) return;                          // no barrier below: a lane's LDS column is its own
+    LdsStack st{cells_sh + tid};
+    out[code] = ugs_gl::vertex_entry(code, n, keys, num_keys, st);
+}
+
 }  // namespace
+
+extern "C" int ugs_graphlet_vertex_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint32_t *d_table_out) {
+    if (n < 1 || n >= UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_vertex_census_table: 1 <= n <= 7");
+    if (!d_keys || !d_table_out || num_keys < 1 || num_keys > (1 << ugs_gl::VERTEX_COL_BITS))
+        return ugs_internal_fail(UGS_E_BAD_ARG, "graphlet_vertex_census_table: keys (1 ... 1024 of them) and the output are needed");
+    hipStream_t s = nullptr;
+    if (int rc = ugs_internal_ctx(nullptr, &s)) return rc;
+    const uint32_t codes = 1u << ugs_gl::tri(n);
+    hipLaunchKernelGGL(ugs_graphlet_vertex_census_table_kernel, dim3((codes + UGS_GL_BLOCK - 1) / UGS_GL_BLOCK), dim3(UGS_GL_BLOCK), 0, s,
+                       n, d_keys, num_keys, d_table_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ugs_internal_fail(UGS_E_HIP, hipGetErrorString(e));
+    return UGS_OK;
+}
 
 extern "C" int ugs_graphlet_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint16_t *d_code_col_out) {
     if (n < 1 || n >= UGS_GL_KMAX) return ugs_internal_fail(UGS_E_UNSUPPORTED, "graphlet_census_table: 1 <= n <= 7");

@@ -148,6 +148,51 @@ UGS_GL_HD uint32_t rooted(uint64_t adj, int n, int u, Stack &st) {
     return search(adj, split_cells(adj, (1ull << n) - 1ull, u), n - 2, col << tri(n - 1), st);
 }
 
+// ---- the vertex census's table entry (ugs_graphlet_vertex_census in include/ugs_mi355.h) -----------------------------------------
+// One 32-bit word says everything a completed set needs about the graph whose adjacency bits in the identity order are `code`, n <= 7:
+// bits 0 .. 9 the column of its class among `keys` (the ascending keys of the connected graphs on n vertices, at most 853 of them), and
+// for every position p < n, bits 10 + 3 p .. 12 + 3 p the LOCAL ORBIT INDEX of position p: the number of distinct rooted codes of the
+// graph below p's, at most 6.  31 bits in all, so VERTEX_NONE -- a graph that is not connected -- is no entry.
+constexpr uint32_t VERTEX_NONE = 0xFFFFFFFFu;
+constexpr int VERTEX_COL_BITS = 10, VERTEX_ORB_BITS = 3;
+
+UGS_GL_HD uint32_t vertex_col(uint32_t entry) { return entry & ((1u << VERTEX_COL_BITS) - 1u); }
+UGS_GL_HD uint32_t vertex_local(uint32_t entry, int p) { return (entry >> (VERTEX_COL_BITS + VERTEX_ORB_BITS * p)) & ((1u << VERTEX_ORB_BITS) - 1u); }
+
+template <class Stack>
+UGS_GL_HD uint32_t vertex_entry(uint32_t code, int n, const int64_t *keys, int64_t num_keys, Stack &st) {
+    const uint64_t adj = adj_of_code(code, n);
+    const int64_t key = ((int64_t)n << 28) | (int64_t)canon(adj, n, st);
+    int64_t lo = 0, hi = num_keys;                     // first key >= key
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= num_keys || keys[lo] != key || lo >> VERTEX_COL_BITS) return VERTEX_NONE;
+    uint32_t entry = (uint32_t)lo;
+    uint32_t r[UGS_GL_KMAX];
+    for (int p = 0; p < n; ++p) r[p] = rooted(adj, n, p, st);
+    for (int p = 0; p < n; ++p) {
+        int below = 0;                                 // distinct rooted codes below r[p]: each counted at its first vertex
+        for (int q = 0; q < n; ++q) {
+            bool first = r[q] < r[p];
+            for (int i = 0; i < q; ++i) first = first && r[i] != r[q];
+            below += first;
+        }
+        entry |= (uint32_t)below << (VERTEX_COL_BITS + VERTEX_ORB_BITS * p);
+    }
+    return entry;
+}
+
+// Whether the graph `adj` on n vertices is connected.
+UGS_GL_HD bool connected(uint64_t adj, int n) {
+    uint32_t reach = 1u;
+    for (int round = 1; round < n; ++round)
+        for (int v = 0; v < n; ++v)
+            if ((reach >> v) & 1u) reach |= (uint32_t)(adj >> (8 * v)) & 0xffu;
+    return reach == (1u << n) - 1u;
+}
+
 // ---- node-labelled graphs (ugs_graphlet_labelled in include/ugs_mi355.h) ----------------------------------------------------------
 // The orders are restricted to those that put the labels in non-decreasing order by position.  That is the search above started
 // from the partition by label instead of from one cell: cell i holds the vertices of the i-th smallest label, so the last cell --

@@ -85,15 +85,17 @@ int ugs_uniform_set_mask_vertices(int n, int *previous) {
 // min(m, |S_g|) from the per-graph counts that come back with the status words.
 // UNI_CENSUS (ugs_graphlet_census): UNI_COUNT with the census pass in the count pass's place; `census` names the tables and the
 // device counts, counts_out may be null.
-enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE, UNI_DISTINCT, UNI_CENSUS };
+// UNI_VCENSUS (ugs_graphlet_vertex_census): UNI_CENSUS with the vertex census pass; `vcensus` names the tables and the device rows,
+// its N is set here, ptr[G], once ptr is known to be sound.
+enum { UNI_SAMPLE = 0, UNI_ENUMERATE, UNI_COUNT, UNI_POPULATE, UNI_DISTINCT, UNI_CENSUS, UNI_VCENSUS };
 using UniPopulate = std::function<int(const UgsUniCall &c, const UgsUniWide &w, const std::vector<UgsUniGraph> &gd, const std::vector<int64_t> &gsize,
                                       const int32_t *graph_status, const DeviceCtx &dc)>;
 static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs,
                          int m_per_graph, int k, int mode, uint64_t seed, const uint64_t *seeds, int32_t *graph_status,
                          ugs_job **job_out, int64_t *total_edges_out, int what = UNI_SAMPLE, int64_t cap = UGS_UNI_BUDGET,
                          int64_t *rows_out = nullptr, int64_t *counts_out = nullptr, const UniPopulate *populate = nullptr,
-                         int64_t *valid_out = nullptr, const UgsCensus *census = nullptr) {
-    if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE && what != UNI_CENSUS) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
+                         int64_t *valid_out = nullptr, const UgsCensus *census = nullptr, const UgsVertexCensus *vcensus = nullptr) {
+    if ((!job_out && what != UNI_COUNT && what != UNI_POPULATE && what != UNI_CENSUS && what != UNI_VCENSUS) || !ptr || num_cols < 0 || (num_cols > 0 && !edge_index))
         return fail(UGS_E_BAD_ARG, what == UNI_DISTINCT ? "bad arguments to sample_distinct" : "bad arguments to sample_batch");
     if (num_graphs < 0) return fail(UGS_E_BAD_ARG, "ptr must hold at least one entry");
     const bool per_graph = seeds != nullptr || what != UNI_SAMPLE;
@@ -137,7 +139,7 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     }
     DeviceCtx dc;
     if (int rc = device_ctx(dc)) return rc;
-    const bool sampling = what == UNI_SAMPLE || what == UNI_DISTINCT, counting = what == UNI_COUNT || what == UNI_CENSUS;
+    const bool sampling = what == UNI_SAMPLE || what == UNI_DISTINCT, counting = what == UNI_COUNT || what == UNI_CENSUS || what == UNI_VCENSUS;
     const int64_t rows = G * (int64_t)m_per_graph, items = nv * 64, budget = nv > 0 ? cap : 0;   // (enumerate: m = 0, its rows come later)
     const int64_t keys = counting ? 0 : budget;                         // counting stores no keys and scans nothing
     // one blob: inputs first (uploaded in one copy), then the scratch of every stage
@@ -208,10 +210,13 @@ static int uniform_begin(const int64_t *edge_index, int64_t row_stride, int64_t 
     if (!sampling) {
         // the count pass (count: nothing else; enumerate: through the sorts), then the first read-back: the graphs' counts and sizes
         std::vector<int64_t> gsize(!counting && nv > 0 ? (size_t)G : 0, 0);
+        UgsVertexCensus vz{};
+        if (what == UNI_VCENSUS) { vz = *vcensus; vz.N = ptr[G]; }      // scan_ptr: non-decreasing, and the entry refused ptr[0] < 0
         if (e == hipSuccess)
-            e = what == UNI_CENSUS ? ugs_uniform_census(c, w, *census, dc.stream)
-                : counting     ? ugs_uniform_count(c, w, dc.stream)
-                               : ugs_uniform_enum_keys(c, w, dc.stream);
+            e = what == UNI_CENSUS    ? ugs_uniform_census(c, w, *census, dc.stream)
+                : what == UNI_VCENSUS ? ugs_uniform_vertex_census(c, w, vz, dc.stream)
+                : counting            ? ugs_uniform_count(c, w, dc.stream)
+                                      : ugs_uniform_enum_keys(c, w, dc.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(status, c.status, sizeof(status), hipMemcpyDeviceToHost, dc.stream);
         if (e == hipSuccess && !gcount.empty()) e = hipMemcpyAsync(gcount.data(), c.gcount, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
         if (e == hipSuccess && !gsize.empty()) e = hipMemcpyAsync(gsize.data(), c.gsize, (size_t)G * 8, hipMemcpyDeviceToHost, dc.stream);
@@ -327,6 +332,25 @@ int ugs_graphlet_census(const int64_t *edge_index, int64_t row_stride, int64_t n
     z.code_col = d_code_col; z.keys = d_keys; z.W = num_keys; z.counts = reinterpret_cast<unsigned long long *>(d_counts_out);
     return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_CENSUS, limit,
                          nullptr, nullptr, nullptr, nullptr, &z);
+}
+
+// ---- ugs_sampler.graphlets.vertex_census: the exact k-graphlet degree vector of every vertex, no set stored (the law is stated in
+//      include/ugs_mi355.h) ----
+int ugs_graphlet_vertex_census(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,
+                               int64_t limit, int64_t num_keys, const int64_t *d_obase, int64_t num_orbits, const uint32_t *d_table,
+                               int64_t *d_gdv_out, int32_t *graph_status) {
+    if (k < 1 || k > 7)
+        return fail(UGS_E_UNSUPPORTED, "graphlet_vertex_census: 1 <= k <= 7 (k = 8 would be 72 489 columns a vertex and a canonical search a set)");
+    if (limit < 1 || limit > ((int64_t)1 << 32)) return fail(UGS_E_BAD_ARG, "limit must be 1 ... 2^32 (got " + std::to_string(limit) + ")");
+    if (!d_obase || !d_table || num_keys < 1 || num_keys > 1024 || num_orbits < num_keys || num_orbits > 7 * num_keys)
+        return fail(UGS_E_BAD_ARG, "graphlet_vertex_census needs the orbit bases of its classes (1 ... 1024 of them), the number of columns and the table");
+    if (num_graphs > 0 && !graph_status) return fail(UGS_E_BAD_ARG, "graphlet_vertex_census needs graph_status");
+    if (ptr && num_graphs >= 0 && ptr[0] < 0) return fail(UGS_E_BAD_ARG, "ptr[0] must be >= 0");
+    if (ptr && num_graphs >= 0 && ptr[num_graphs] > 0 && !d_gdv_out) return fail(UGS_E_BAD_ARG, "graphlet_vertex_census needs gdv_out");
+    UgsVertexCensus z{};
+    z.table = d_table; z.obase = d_obase; z.W = num_keys; z.O = num_orbits; z.gdv = reinterpret_cast<unsigned long long *>(d_gdv_out);
+    return uniform_begin(edge_index, row_stride, num_cols, ptr, num_graphs, 0, k, 0, 0, nullptr, graph_status, nullptr, nullptr, UNI_VCENSUS, limit,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, &z);
 }
 
 int ugs_uniform_enumerate_begin(const int64_t *edge_index, int64_t row_stride, int64_t num_cols, const int64_t *ptr, int64_t num_graphs, int k,

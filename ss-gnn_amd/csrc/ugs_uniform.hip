@@ -45,6 +45,12 @@
 //                                       ugs_gl::canon and a search among the connected keys) and counted, runs merged per lane, into
 //                                       the workgroup's LDS counters (k <= 7) or the graph's row (k = 8); nothing is stored per set
 //   uni_census_clear                    the row of a graph past the limit
+//
+// Graphlet vertex census (ugs_graphlet_vertex_census): the same, per vertex
+//   uni_vcensus_esu / uni_vcensus_wesu  the census's search for k <= 7 with the ids of the placed vertices carried down beside the raw
+//                                       code; one load from a code -> (column, orbit of every position) table a set, and k integer
+//                                       atomic adds into the rows of its members, the k - 1 placed ones merged over runs of siblings
+//   uni_vcensus_clear                   the rows of the vertices of a graph past the limit
 #include "ugs_device.h"
 #include "ugs_graphlet_common.h"
 
@@ -1359,6 +1365,216 @@ __global__ void uni_census_clear(UgsUniCall c, UgsCensus z) {
     if (c.gcount[i / z.W] > c.budget) z.counts[i] = 0;
 }
 
+// ---- graphlet vertex census (ugs_graphlet_vertex_census): the census's search, every completed set counted once per member ----
+// Besides the raw code the search carries the ids of the placed vertices, local to their graph, FB bits a position in one 64-bit word
+// (`ids`; the mask form: 6 bits, the wide form: 10 -- a wide graph has at most UGS_UNI_WIDE_MAX_N = 1024 vertices -- and at most six
+// positions are placed before a leaf of k <= 7).  Like `code` it is a value handed down the unrolled levels: no indexed stack.  At
+// k - 1 placed vertices every member of ext completes a set; one table load (ugs_gl::vertex_entry) gives the set's column and the
+// local orbit index of each of its k positions.  The member's cell gets one add.  The k - 1 placed vertices are the same for all
+// members of ext, so members with equal entries in a row are merged: one add of the run's length per placed position.
+struct VcSink {
+    const uint32_t *table;
+    const int64_t *obase;
+    unsigned long long *rows;     // the graph's first row of gdv
+    int64_t O;
+    uint32_t W;
+};
+
+// the run's length to the cells of the D placed vertices
+template <int D, int FB>
+__device__ __forceinline__ void vc_flush(const VcSink &s, uint32_t entry, int64_t ob, uint32_t run, uint64_t ids) {
+    if (!run || ugs_gl::vertex_col(entry) >= s.W) return;           // (a set the search completes is connected: its entry has a column)
+#pragma unroll
+    for (int p = 0; p < D; ++p)
+        atomicAdd(&s.rows[(int64_t)((ids >> (FB * p)) & ((1ull << FB) - 1)) * s.O + ob + ugs_gl::vertex_local(entry, p)], (unsigned long long)run);
+}
+
+// the members `ext` of one word (their ids are first + bit) against the D placed vertices
+template <int D, int FB>
+__device__ __forceinline__ void vc_members(const VcSink &s, const uint64_t (&row)[CEN_ROWS], uint64_t ext, int first, uint32_t code, uint64_t ids) {
+    uint32_t run_entry = ugs_gl::VERTEX_NONE, run = 0;
+    int64_t ob = 0;
+    for (uint64_t e = ext; e; e &= e - 1) {
+        const int bit = __ffsll((unsigned long long)e) - 1;
+        const uint32_t entry = s.table[code | (cen_column<D>(row, bit) << ugs_gl::tri(D))];
+        if (entry != run_entry) {
+            vc_flush<D, FB>(s, run_entry, ob, run, ids);
+            run_entry = entry; run = 0;
+            ob = ugs_gl::vertex_col(entry) < s.W ? s.obase[ugs_gl::vertex_col(entry)] : 0;
+        }
+        ++run;
+        if (ugs_gl::vertex_col(entry) < s.W)
+            atomicAdd(&s.rows[(int64_t)(first + bit) * s.O + ob + ugs_gl::vertex_local(entry, D)], 1ull);
+    }
+    vc_flush<D, FB>(s, run_entry, ob, run, ids);
+}
+
+constexpr int VC_MASK_FB = 6, VC_WIDE_FB = 10;
+
+template <int D>
+__device__ __forceinline__ void vc_last(CenMask &x, const VcSink &s, uint64_t ext, uint32_t code, uint64_t ids) {
+    vc_members<D, VC_MASK_FB>(s, x.row, ext, 0, code, ids);
+    x.cnt += (uint64_t)__popcll(ext);
+    if (x.cnt - x.flushed >= 4096) {                                // bounded work for a graph over the limit, as in uni_esu
+        const unsigned long long add = x.cnt - x.flushed;
+        x.flushed = x.cnt;
+        if (atomicAdd(x.ctr, add) + add > x.budget) x.stop = true;
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void vc_level(CenMask &x, const VcSink &s, uint64_t ext, uint64_t nb, uint32_t code, uint64_t ids) {
+    if (D == x.k - 1) { vc_last<D>(x, s, ext, code, ids); return; }
+    if constexpr (D < CEN_ROWS - 1) {                               // k <= 7: six vertices at most are placed before the leaf
+        while (ext && !x.stop) {
+            const int w = __ffsll((unsigned long long)ext) - 1;
+            ext &= ext - 1;
+            const uint64_t aw = x.adj[w];
+            const uint32_t col = cen_column<D>(x.row, w);
+            x.row[D] = aw;
+            vc_level<D + 1>(x, s, ext | (aw & ~nb & x.abv), nb | aw, code | (col << ugs_gl::tri(D)), ids | ((uint64_t)w << (VC_MASK_FB * D)));
+        }
+    }
+}
+
+// uni_census_esu<0>'s items and lanes: one wave per item (root v, first extension w0), lane j the second extension vertex.  No LDS:
+// the counts go to the k rows of each set.
+__global__ __launch_bounds__(CEN_MASK_BLOCK) void uni_vcensus_esu(UgsUniCall c, UgsVertexCensus z) {
+    const int64_t vi = (int64_t)(blockIdx.x >> 6);
+    const int w0 = (int)(blockIdx.x & 63), j = (int)threadIdx.x;
+    const int32_t gi = c.vgraph[vi];
+    const UgsUniGraph gd = c.graphs[gi];
+    const int v = (int)(vi - gd.vbase);
+    const int k = c.k;
+    CenMask x;
+    x.adj = c.adj + gd.vbase; x.abv = above_mask(v); x.k = k;
+    const uint64_t av = x.adj[v];
+    const uint64_t ext1 = av & x.abv;
+    if (k == 1 ? w0 != 0 : !((ext1 >> w0) & 1)) return;
+    VcSink s;
+    s.table = z.table; s.obase = z.obase; s.O = z.O; s.W = (uint32_t)z.W;
+    s.rows = z.gdv + gd.lo * z.O;
+    x.cnt = 0; x.flushed = 0; x.stop = false;
+    x.ctr = (unsigned long long *)&c.gcount[gi]; x.budget = (unsigned long long)c.budget;
+#pragma unroll
+    for (int i = 0; i < CEN_ROWS; ++i) x.row[i] = 0;
+    if (*(volatile unsigned long long *)x.ctr <= x.budget) {        // a graph already past the limit starts nothing more
+        x.row[0] = av;
+        if (k == 1 && j == 0) vc_last<0>(x, s, 1ull << v, 0u, 0ull);
+        if (k == 2 && j == 0) vc_last<1>(x, s, 1ull << w0, 0u, (uint64_t)v);
+        if (k >= 3) {
+            const uint64_t aw = x.adj[w0];
+            const uint64_t nb1 = av | (1ull << v);
+            const uint64_t ext2 = (ext1 & above_mask(w0)) | (aw & ~nb1 & x.abv), nb2 = nb1 | aw;
+            const uint64_t ids2 = (uint64_t)v | ((uint64_t)w0 << VC_MASK_FB);
+            x.row[1] = aw;
+            if (k == 3 && j == 0) vc_last<2>(x, s, ext2, 1u, ids2);
+            if (k >= 4 && ((ext2 >> j) & 1)) {
+                const uint64_t aj = x.adj[j];
+                const uint32_t col = cen_column<2>(x.row, j);
+                x.row[2] = aj;
+                vc_level<3>(x, s, (ext2 & above_mask(j)) | (aj & ~nb2 & x.abv), nb2 | aj, 1u | (col << ugs_gl::tri(2)),
+                            ids2 | ((uint64_t)j << (VC_MASK_FB * 2)));
+            }
+        }
+    }
+    if (x.cnt > x.flushed) atomicAdd(x.ctr, (unsigned long long)(x.cnt - x.flushed));
+}
+
+template <int D>
+__device__ __forceinline__ void wvc_last(CenWide &x, const VcSink &s, uint64_t ext, uint32_t code, uint64_t ids) {
+    vc_members<D, VC_WIDE_FB>(s, x.row, ext, x.g.l * 64, code, ids);   // every lane: the members in its own word
+    x.g.cnt += (uint32_t)__popcll(ext);
+    bool over = false;
+    if (x.g.cnt - x.g.flushed >= 4096 / WIDE_LANES) {               // the group flushes at least every 4096 sets
+        const unsigned long long add = x.g.cnt - x.g.flushed;
+        over = atomicAdd(x.g.ctr, add) + add > (unsigned long long)x.g.budget;
+        x.g.flushed = x.g.cnt;
+    }
+    if (group_ballot(x.g, over)) x.g.stop = true;
+}
+
+template <int D>
+__device__ __forceinline__ void wvc_level(CenWide &x, const VcSink &s, uint64_t ext, uint64_t nb, uint32_t code, uint64_t ids) {
+    if (D == x.g.k - 1) { wvc_last<D>(x, s, ext, code, ids); return; }
+    if constexpr (D < CEN_ROWS - 1) {
+        while (!x.g.stop) {
+            const int w = group_take(x.g, ext);
+            if (w < 0) break;
+            const uint64_t aw = x.g.l < x.g.W ? x.g.adj[(int64_t)w * x.g.W + x.g.l] : 0ull;
+            const uint32_t col = (uint32_t)__shfl((int)cen_column<D>(x.row, w & 63), w >> 6, WIDE_LANES);   // the lane that holds w's word
+            x.row[D] = aw;
+            wvc_level<D + 1>(x, s, ext | (aw & ~nb & x.g.abv), nb | aw, code | (col << ugs_gl::tri(D)), ids | ((uint64_t)w << (VC_WIDE_FB * D)));
+        }
+    }
+}
+
+// uni_census_wesu<0>'s items and groups, without its LDS counters
+__global__ __launch_bounds__(UNI_BLOCK) void uni_vcensus_wesu(UgsUniCall c, UgsUniWide wd, UgsVertexCensus z) {
+    const int64_t item = wd.nv_mask * 64 + (int64_t)blockIdx.x * WIDE_GROUPS + (threadIdx.x / WIDE_LANES);   // < nv * 64: the grid is exact
+    const int64_t vi = item >> 6;
+    const int slot = (int)(item & 63);
+    const int32_t gi = c.vgraph[vi];
+    const UgsUniGraph gd = c.graphs[gi];
+    VcSink s;
+    s.table = z.table; s.obase = z.obase; s.O = z.O; s.W = (uint32_t)z.W;
+    s.rows = z.gdv + gd.lo * z.O;
+    const int v = (int)(vi - gd.vbase), vw = v >> 6;
+    CenWide x;
+    x.g.adj = wd.wadj + wd.wbase[gi];
+    x.g.W = (gd.n + 63) >> 6; x.g.l = threadIdx.x & (WIDE_LANES - 1); x.g.gshift = threadIdx.x & 63 & ~(WIDE_LANES - 1);
+    x.g.b = 0; x.g.k = c.k;
+    x.g.abv = x.g.l < vw ? 0ull : x.g.l == vw ? above_mask(v & 63) : ~0ull;
+    x.g.out = nullptr; x.g.cnt = 0; x.g.flushed = 0;
+    x.g.ctr = (unsigned long long *)&c.gcount[gi];
+    x.g.budget = c.budget; x.g.status = nullptr; x.g.stop = false;
+#pragma unroll
+    for (int i = 0; i < CEN_ROWS; ++i) x.row[i] = 0;
+    // a graph already past the limit starts nothing more; the lanes of a group must agree, whenever each of them read the total
+    if (!group_ballot(x.g, *(volatile unsigned long long *)x.g.ctr > (unsigned long long)c.budget)) {
+        const uint64_t av = x.g.l < x.g.W ? x.g.adj[(int64_t)v * x.g.W + x.g.l] : 0ull;
+        const uint64_t ext1 = av & x.g.abv;
+        const uint64_t nb1 = av | (x.g.l == vw ? 1ull << (v & 63) : 0ull);
+        x.row[0] = av;
+        if (x.g.k == 1) {
+            if (slot == 0) wvc_last<0>(x, s, x.g.l == vw ? 1ull << (v & 63) : 0ull, 0u, 0ull);
+        } else if (x.g.k == 2) {
+            if (slot == 0) wvc_last<1>(x, s, ext1, 0u, (uint64_t)v);
+        } else {
+            const uint32_t pc = (uint32_t)__popcll(ext1), incl = row_scan(pc), excl = incl - pc;
+            const uint32_t deg = (uint32_t)__shfl((int)incl, WIDE_LANES - 1, WIDE_LANES);
+            for (uint32_t r = (uint32_t)slot; r < deg && !x.g.stop; r += 64) {
+                const bool holds = excl <= r && r < incl;           // this lane's word holds the r-th member
+                int f = 0;
+                if (holds) {
+                    uint64_t t = ext1;
+                    for (uint32_t i = r - excl; i > 0; --i) t &= t - 1;
+                    f = __ffsll((unsigned long long)t) - 1;
+                }
+                const int l0 = __ffs(group_ballot(x.g, holds)) - 1;
+                f = __shfl(f, l0, WIDE_LANES);
+                const int w = l0 * 64 + f;
+                const uint64_t aw = x.g.l < x.g.W ? x.g.adj[(int64_t)w * x.g.W + x.g.l] : 0ull;
+                const uint64_t later = x.g.l < l0 ? 0ull : x.g.l == l0 ? above_mask(f) : ~0ull;   // the members of ext1 after w
+                x.row[1] = aw;
+                wvc_level<2>(x, s, (ext1 & later) | (aw & ~nb1 & x.g.abv), nb1 | aw, 1u, (uint64_t)v | ((uint64_t)w << VC_WIDE_FB));
+            }
+        }
+    }
+    const uint32_t rest = row_scan(x.g.cnt - x.g.flushed);
+    if (x.g.l == WIDE_LANES - 1 && rest) atomicAdd(x.g.ctr, (unsigned long long)rest);
+}
+
+// behind the vertex census pass: the vertices of a graph past the limit have rows of zeros.  One workgroup per graph.
+__global__ __launch_bounds__(UNI_BLOCK) void uni_vcensus_clear(UgsUniCall c, UgsVertexCensus z) {
+    const int64_t g = (int64_t)blockIdx.x;
+    if (c.gcount[g] <= c.budget) return;
+    const UgsUniGraph gd = c.graphs[g];
+    unsigned long long *rows = z.gdv + gd.lo * z.O;
+    const int64_t cells = (int64_t)gd.n * z.O;
+    for (int64_t i = threadIdx.x; i < cells; i += UNI_BLOCK) rows[i] = 0;
+}
+
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // uni_draw_distinct over every graph of the call; the sort's width, and with it the LDS, follows m, not the limit
@@ -1385,8 +1601,9 @@ size_t ugs_uniform_cub_bytes(int64_t E, int64_t nv, int64_t budget) {
 
 // The stages every entry shares, up to the per-graph sizes: column buckets, adjacency, the count pass and -- unless `count_only` --
 // scan, write pass, sorts, gstart / gsize.  count_only stops behind the count pass: it touches neither ioff nor a key array.
-// With `cen` (count_only) the census pass takes the count pass's place.
-static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_only, hipStream_t s, const UgsCensus *cen = nullptr) {
+// With `cen` or `vcen` (count_only) the census pass, or the vertex census pass, takes the count pass's place.
+static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_only, hipStream_t s, const UgsCensus *cen = nullptr,
+                              const UgsVertexCensus *vcen = nullptr) {
     const int64_t nv_wide = c.nv - w.nv_mask;                                  // 0: the call runs the mask form's launches only
     UgsUniCall cm = c;                                                         // the mask form's view: its own roots
     cm.nv = w.nv_mask;
@@ -1425,6 +1642,12 @@ static hipError_t uni_prepare(UgsUniCall &c, const UgsUniWide &w, bool count_onl
                 if (table) hipLaunchKernelGGL((uni_census_wesu<0>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), lds, s, c, w, *cen);
                 else hipLaunchKernelGGL((uni_census_wesu<UGS_GL_KMAX>), dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), lds, s, c, w, *cen);
             }
+            return hipGetLastError();
+        }
+        if (vcen) {
+            if (mitems > 0x7fffffffll) return hipErrorInvalidConfiguration;    // one workgroup per item of the mask roots
+            if (mitems > 0) hipLaunchKernelGGL(uni_vcensus_esu, dim3((unsigned)mitems), dim3(CEN_MASK_BLOCK), 0, s, cm, *vcen);
+            if (witems > 0) hipLaunchKernelGGL(uni_vcensus_wesu, dim3(blocks(witems, WIDE_GROUPS)), dim3(UNI_BLOCK), 0, s, c, w, *vcen);
             return hipGetLastError();
         }
         if (mitems > 0) {
@@ -1491,6 +1714,16 @@ hipError_t ugs_uniform_census(UgsUniCall &c, const UgsUniWide &w, const UgsCensu
     if (e != hipSuccess) return e;
     if ((e = uni_prepare(c, w, true, s, &z)) != hipSuccess) return e;
     if (c.nv > 0 && cells > 0) hipLaunchKernelGGL(uni_census_clear, dim3(blocks(cells, UNI_BLOCK)), dim3(UNI_BLOCK), 0, s, c, z);
+    return hipGetLastError();
+}
+
+// k <= 7 and the table: the host entry checks that
+hipError_t ugs_uniform_vertex_census(UgsUniCall &c, const UgsUniWide &w, const UgsVertexCensus &z, hipStream_t s) {
+    const int64_t cells = z.N * z.O;
+    hipError_t e = cells > 0 ? hipMemsetAsync(z.gdv, 0, (size_t)cells * sizeof(uint64_t), s) : hipSuccess;
+    if (e != hipSuccess) return e;
+    if ((e = uni_prepare(c, w, true, s, nullptr, &z)) != hipSuccess) return e;
+    if (c.nv > 0 && c.G > 0) hipLaunchKernelGGL(uni_vcensus_clear, dim3((unsigned)c.G), dim3(UNI_BLOCK), 0, s, c, z);
     return hipGetLastError();
 }
 

@@ -40,6 +40,12 @@ the graphlet degree vector of every vertex -- how often it occupies each orbit o
     orbit = graphlets.orbit_ids(nodes, edge_index, edge_ptr)                                        # int64 [S, k]
     gdv = graphlets.vertex_orbit_counts(nodes, orbit, batch.num_nodes, graphlets.connected_orbits(k))
 
+`vertex_census` gives that degree vector in one call that stores no rows, as `census` gives the histogram: every set adds to the rows
+of its k members where the search finds it, up to 2**32 sets a graph, k <= 7.  The law is stated at ugs_graphlet_vertex_census in
+the same header:
+
+    gdv, failed = graphlets.vertex_census(batch.edge_index, batch.ptr, k, device=dev)   # int64 [N, len(connected_orbits(k))]
+
 `labelled_keys` is the exact class of a row as a NODE-LABELLED graph (the reference's use_node_features_in_wl): two rows of one shape
 with different atoms are different classes.  The law is stated at ugs_graphlet_labelled in the same header.  The orders are restricted
 to those that put the labels in non-decreasing order by position, the labelled canonical code is the smallest adjacency code over
@@ -68,7 +74,8 @@ from .wl import _check_inputs, _check_labels, _placed
 
 __all__ = ["canonical", "class_ids", "num_classes", "table", "decode", "is_connected", "histogram", "search_stats",
            "orbit_ids", "num_orbits", "orbit_base", "orbit_info", "connected_orbits", "vertex_orbit_counts",
-           "labelled_keys", "decode_labelled", "compact_labels", "LABEL_BITS", "census", "connected_classes"]
+           "labelled_keys", "decode_labelled", "compact_labels", "LABEL_BITS", "census", "connected_classes",
+           "vertex_census"]
 
 KMAX = 8
 LABEL_BITS = 12                                         # a label's width in a labelled key: labels lie in [0, 4096)
@@ -80,6 +87,7 @@ _host_orbit_counts = {}                                 # n -> numpy int64 orbit
 _dev_bases = {}                                         # (device index, k) -> orbit_base(k) on that GPU
 _host_connected = {}                                    # k -> connected_classes(k)
 _dev_census = {}                                        # (device index, k) -> census' column keys and code -> column table on that GPU
+_dev_vertex_census = {}                                 # (device index, k) -> vertex_census' orbit bases, width and code table on that GPU
 
 
 def _check_k(k):
@@ -470,6 +478,68 @@ def census(edge_index, ptr, k, *, limit=1 << 25, device=None):
                                   code_col.data_ptr() if code_col is not None else None, counts.data_ptr() if G > 0 else None,
                                   status.ctypes.data))
     return counts.cpu() if back else counts, torch.from_numpy(status[:max(G, 0)] != 0)
+
+
+def _vertex_census_tables(dev, k):
+    """(orbit bases of the connected classes int64 [W + 1], code -> (class column, orbit of every position) table) on `dev`, k <= 7; the
+    library's device and stream are selected.  The table is built by one launch over all 2^(k (k-1) / 2) codes, once per device and k."""
+    at = (dev.index, k)
+    if at not in _dev_vertex_census:
+        classes = connected_classes(k)
+        first = num_classes(k - 1) if k > 1 else 0
+        sizes = _orbit_counts_n(k)[(classes - first).numpy()]
+        obase = torch.from_numpy(np.concatenate([np.zeros(1, np.int64), np.cumsum(sizes)])).to(dev)
+        keys = table(k)[classes].to(dev)
+        tab = torch.empty((1 << (k * (k - 1) // 2),), dtype=torch.int32, device=dev)               # uint32 bit patterns
+        check(lib.ugs_graphlet_vertex_census_table(k, keys.data_ptr(), keys.numel(), tab.data_ptr()))
+        torch.cuda.current_stream(dev).synchronize()                                               # later calls may run on other streams
+        _dev_vertex_census[at] = (obase, int(sizes.sum()), tab)
+    return _dev_vertex_census[at]
+
+
+def vertex_census(edge_index, ptr, k, *, limit=1 << 25, device=None):
+    """The exact k-graphlet degree vector of every vertex of a batch: (gdv int64 [N, O], failed host bool [G]), N = ptr[-1], O =
+    len(connected_orbits(k)) = 1, 1, 3, 11, 58, 407, 4306 for k = 1 .. 7; gdv[v, c] is the number of connected k-subsets of v's graph
+    that contain v and in which v's orbit id is connected_orbits(k)[c].
+
+    What vertex_orbit_counts(nodes, orbit_ids(rows), N, connected_orbits(k)) gives over `uniform_sampler.enumerate_graphs` rows, bit
+    for bit, without the rows: every set adds to the rows of its k members where the search finds it, so a graph may hold up to
+    `limit` sets, 1 ... 2**32 (ValueError otherwise), and beside the result the call's memory does not grow with the population.  The
+    result is 8 * N * O bytes -- 34 KiB per vertex at k = 7, 3.2 KiB at k = 6 -- allocated with torch; there is no cap of the call's
+    own.  The law is stated at ugs_graphlet_vertex_census in include/ugs_mi355.h; summed over a graph's vertices a column is the
+    orbit's size times `census`' count of its class.  A graph the samplers refuse for its size or with more than `limit` sets has
+    failed[g] = True and rows of zeros for all its vertices, and leaves every other vertex exact; rows of vertices below ptr[0] are
+    zero.  k = 8 is refused (72 489 columns a vertex and a canonical search a set are no sensible call), before any device is touched.
+    Arguments, their errors, placement (gdv on the device of `edge_index`, or on `device`; CPU tensors in and gdv back on the CPU)
+    and `uniform_sampler.set_max_vertices` are as for `census`.  One synchronous call on torch's current stream (DESIGN.md section
+    19.4)."""
+    _check_k(k)
+    if k == KMAX:                                       # the library states the refusal, before any device work
+        check(lib.ugs_graphlet_vertex_census(None, 0, 0, None, 0, k, 1, 0, None, 0, None, None, None))
+    limit = int(limit)
+    if not 1 <= limit <= 1 << 32:
+        raise ValueError(f"limit must be 1 ... 2**32, got {limit}")
+    for t, name in ((edge_index, "edge_index"), (ptr, "ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _graphs.check_int64(edge_index, ptr)
+    back = device is None and edge_index.device.type != "cuda"
+    dev = torch.device(device) if device is not None else edge_index.device if not back else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError("device= must be a GPU device")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    keep, p, stride, e = _graphs._edge_index_view(edge_index.cpu())
+    pt = ptr.cpu().contiguous()
+    G = pt.numel() - 1
+    N = max(int(pt[-1]), 0) if G >= 0 else 0            # (the library refuses a ptr that is not sound)
+    _graphs._select_device(dev, jobs=True)
+    obase, O, tab = _vertex_census_tables(dev, k)
+    gdv = torch.empty((N, O), dtype=torch.int64, device=dev)
+    status = np.zeros(max(G, 1), dtype=np.int32)
+    check(lib.ugs_graphlet_vertex_census(p, stride, e, pt.data_ptr(), G, k, limit, obase.numel() - 1, obase.data_ptr(), O,
+                                         tab.data_ptr(), gdv.data_ptr() if N > 0 else None, status.ctypes.data))
+    return gdv.cpu() if back else gdv, torch.from_numpy(status[:max(G, 0)] != 0)
 
 
 def decode_labelled(key):
