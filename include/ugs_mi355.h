@@ -1097,6 +1097,38 @@ int ugs_graphlet_vertex_census(const int64_t *edge_index, int64_t row_stride, in
 int ugs_graphlet_vertex_census_table(int n, const int64_t *d_keys, int64_t num_keys, uint32_t *d_table_out);
 int ugs_graphlet_vertex_census_entry(uint32_t code, int n, uint32_t *out);
 
+/* ---- graphlets.census / vertex_census (..., form="csr"): the same two results for graphs of ANY size, searched over adjacency lists
+ *      instead of bitmap rows.  The law.
+ *        1. The results are those of ugs_graphlet_census items 1 ... 4 and of ugs_graphlet_vertex_census items 1 ... 5, with the same
+ *           columns and tables; on every graph the bitmap form accepts, counts and gdv are equal to its results bit for bit.
+ *        2. THE GRAPH IS THE CSR.  Item 1 of ugs_graphlet_census as a data structure: d_rowptr [num_vertices + 1] int64 and d_col
+ *           [num_entries] int32 hold the neighbours of every vertex of the batch, global vertex ids.  PRECONDITIONS: d_ptr
+ *           [num_graphs + 1] is non-decreasing, d_ptr[0] >= 0 and d_ptr[num_graphs] = num_vertices; d_rowptr is non-decreasing from 0
+ *           to num_entries; every entry of row v lies in the vertex range of v's graph and differs from v (so a vertex below d_ptr[0]
+ *           has an empty row); every row is strictly ascending; u in row v implies v in row u.  One validation launch checks all of
+ *           it before the search reads through the CSR and reads nothing outside the three arrays, whatever they hold: a CSR that
+ *           breaks a precondition is UGS_E_BAD_ARG, never a fault.  graphlets._simple_csr builds such a CSR from edge_index and ptr.
+ *        3. NO SIZE REFUSAL.  graph_status is 0 (healthy) or 2 (more than `limit` sets: zeros, every other graph exact, no joint
+ *           budget); 1 does not occur, and ugs_uniform_set_max_vertices / ugs_uniform_set_mask_vertices play no part.  A graph of
+ *           fewer than k vertices is healthy with zeros.  limit is 1 ... 2^62 (UGS_E_BAD_ARG otherwise): the counters are 64-bit.  The
+ *           work per graph is bounded by limit: a graph past it stops at its next flush, every 4096 sets of a lane.
+ *        4. REFUSALS, in this order, before any device work: k outside 1 ... 8, and k = 8 (a raw code of 28 bits has no table, and a
+ *           canonical search per set is no part of this form): UGS_E_UNSUPPORTED; limit; num_vertices >= 2^31, num_entries > 2^31 - 1,
+ *           num_graphs >= 2^31 - 1: UGS_E_UNSUPPORTED; then the pointers.  num_graphs = 0 and num_entries = 0 are valid.
+ * All pointers are DEVICE pointers except graph_status (host, num_graphs entries).  d_keys, d_code_col (required: k <= 7), d_obase and
+ * d_table are those of ugs_graphlet_census and ugs_graphlet_vertex_census for this k; d_counts_out is [num_graphs, num_keys], d_gdv_out
+ * [num_vertices, num_orbits].  Synchronous, no job, on the calling thread's stream: the output is zeroed, the validation launch and its
+ * read-back, one search pass (one wave per CSR entry with col > row), the read-back of the graphs' set counts for the status and, in
+ * a call where some graph failed, the clearing of those graphs.  The counts are added with integer atomics: exact in any order.
+ * Nothing of the batch is copied: the call's own device memory is 8 bytes a graph. */
+int ugs_graphlet_census_csr(const int64_t *d_ptr, int64_t num_graphs, const int64_t *d_rowptr, const int32_t *d_col,
+                            int64_t num_vertices, int64_t num_entries, int k, int64_t limit, const int64_t *d_keys, int64_t num_keys,
+                            const uint16_t *d_code_col, int64_t *d_counts_out, int32_t *graph_status);
+int ugs_graphlet_vertex_census_csr(const int64_t *d_ptr, int64_t num_graphs, const int64_t *d_rowptr, const int32_t *d_col,
+                                   int64_t num_vertices, int64_t num_entries, int k, int64_t limit, int64_t num_keys,
+                                   const int64_t *d_obase, int64_t num_orbits, const uint32_t *d_table, int64_t *d_gdv_out,
+                                   int32_t *graph_status);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  get_timing synchronises the
  * recorded events, returns summed milliseconds and launch counts for [0] the first-tier walk kernel, [1] overflow
  * tiers + scan kernels, [2] the fill kernel since the last call, and clears them. */

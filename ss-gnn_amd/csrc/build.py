@@ -12,8 +12,9 @@ SRCS = [os.path.join(HERE, "ugs_kernels.hip"), os.path.join(HERE, "ugs_eps.hip")
         os.path.join(HERE, "ugs_graph_cache.cpp"), os.path.join(HERE, "ugs_store.hip"), os.path.join(HERE, "ugs_eps_cache.cpp"),
         os.path.join(HERE, "ugs_apx.cpp"), os.path.join(HERE, "ugs_apx_gpu.hip"), os.path.join(HERE, "ugs_wl.hip"),
         os.path.join(HERE, "ugs_rows.hip"), os.path.join(HERE, "ugs_rows.cpp"),
-        os.path.join(HERE, "ugs_graphlet.hip"), os.path.join(HERE, "ugs_graphlet.cpp")]
-HDRS = [os.path.join(HERE, "ugs_device.h"), os.path.join(HERE, "ugs_host_internal.h"), os.path.join(HERE, "ugs_apx_common.h"), os.path.join(HERE, "ugs_graphlet_common.h"),os.path.join(HERE, "..", "..", "include", "ugs_mi355.h")]
+        os.path.join(HERE, "ugs_graphlet.hip"), os.path.join(HERE, "ugs_graphlet.cpp"),
+        os.path.join(HERE, "ugs_census_csr.hip"), os.path.join(HERE, "ugs_census_csr.cpp")]
+HDRS = [os.path.join(HERE, "ugs_device.h"), os.path.join(HERE, "ugs_host_internal.h"), os.path.join(HERE, "ugs_apx_common.h"), os.path.join(HERE, "ugs_graphlet_common.h"), os.path.join(HERE, "ugs_census_csr.h"), os.path.join(HERE, "..", "..", "include", "ugs_mi355.h")]
 DEPS = SRCS + HDRS
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

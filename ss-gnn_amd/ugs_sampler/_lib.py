@@ -144,6 +144,8 @@ def _load():
         "ugs_graphlet_census_table": [C.c_int, vp, C.c_int64, vp],
         "ugs_graphlet_vertex_census": [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp],
         "ugs_graphlet_vertex_census_table": [C.c_int, vp, C.c_int64, vp],
+        "ugs_graphlet_census_csr": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp],
+        "ugs_graphlet_vertex_census_csr": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp],
         "ugs_graphlet_vertex_census_entry": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)],
         "ugs_graphlet_canon_code": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)],
         "ugs_graphlet_search_stats": [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],

@@ -46,6 +46,11 @@ the same header:
 
     gdv, failed = graphlets.vertex_census(batch.edge_index, batch.ptr, k, device=dev)   # int64 [N, len(connected_orbits(k))]
 
+Both censuses take form="csr" for graphs above the uniform sampler's size rule -- the 1 M-vertex graph of the headline workload, a
+PROTEINS graph of 600 vertices at k = 7: the same results from a search over adjacency lists, k <= 7, up to 2**62 sets a graph:
+
+    counts, failed = graphlets.census(edge_index, ptr, 4, limit=1 << 40, form="csr")   # edge_index on the GPU is used where it is
+
 `labelled_keys` is the exact class of a row as a NODE-LABELLED graph (the reference's use_node_features_in_wl): two rows of one shape
 with different atoms are different classes.  The law is stated at ugs_graphlet_labelled in the same header.  The orders are restricted
 to those that put the labels in non-decreasing order by position, the labelled canonical code is the smallest adjacency code over
@@ -439,7 +444,77 @@ def _census_tables(dev, k):
     return _dev_census[at]
 
 
-def census(edge_index, ptr, k, *, limit=1 << 25, device=None):
+_FORMS = ("bitmap", "csr")
+
+
+def _check_form(form):
+    if form not in _FORMS:
+        raise ValueError(f"form must be one of {_FORMS}, got {form!r}")
+
+
+def _check_limit(limit, form):
+    limit = int(limit)
+    top = 62 if form == "csr" else 32
+    if not 1 <= limit <= 1 << top:
+        raise ValueError(f"limit must be 1 ... 2**{top}, got {limit}")
+    return limit
+
+
+def _simple_csr(edge_index, ptr):
+    """The simple graph of a batch as a CSR: (rowptr int64 [N + 1], col int32 [M]) on the device of `edge_index`, N = ptr[-1].  Item 1
+    of the census law as a data structure: only columns with both endpoints inside one graph's range are kept (an endpoint outside
+    [0, N) lies in no graph: such a column is dropped, as the bitmap form drops it), the adjacency is symmetrised, loops are dropped,
+    duplicates collapse, and every row is strictly ascending.  Torch ops only -- bucketize by ptr, keys u * N + v, unique,
+    searchsorted -- so it runs on CPU tensors as well.  ptr is taken as it is; the library checks it."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise RuntimeError("edge_index must have shape [2, E]")
+    dev = edge_index.device
+    ptr = ptr.to(dev).contiguous()
+    G = ptr.numel() - 1
+    N = max(int(ptr[-1]), 0) if G >= 0 else 0
+    u, v = edge_index[0].contiguous(), edge_index[1].contiguous()
+    gu = torch.bucketize(u, ptr, right=True)            # ptr[gu - 1] <= u < ptr[gu]: graph gu - 1, for 1 <= gu <= G
+    gv = torch.bucketize(v, ptr, right=True)
+    keep = (gu >= 1) & (gu <= G) & (gu == gv) & (u != v) & (u >= 0) & (u < N) & (v >= 0) & (v < N)
+    u, v = u[keep], v[keep]
+    keys = torch.unique(torch.cat([u * N + v, v * N + u]))                      # sorted: by row, then ascending inside the row
+    rowptr = torch.searchsorted(keys, torch.arange(N + 1, dtype=torch.int64, device=dev) * N)
+    col = (keys % max(N, 1)).to(torch.int32)
+    return rowptr, col
+
+
+def _csr_inputs(edge_index, ptr, device, k, limit):
+    """(rowptr, col, ptr, G, N, dev, back) of a csr-form call: the CSR and ptr on the GPU the call runs on.  Device tensors are used
+    where they are; CPU tensors go up once.  The form's limits are refused here: N before the CSR is built (its keys u * N + v need
+    N < 2**31), the entries behind it."""
+    for t, name in ((edge_index, "edge_index"), (ptr, "ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    _graphs.check_int64(edge_index, ptr)
+    if ptr.dim() != 1 or ptr.numel() < 1:
+        raise RuntimeError("ptr must hold at least one entry")
+    back = device is None and edge_index.device.type != "cuda"
+    dev = torch.device(device) if device is not None else edge_index.device if not back else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError("device= must be a GPU device")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ptr = ptr.to(dev).contiguous()
+    if int(ptr[-1]) >= 1 << 31:
+        _refuse_csr(k, limit, int(ptr[-1]), 0)
+    rowptr, col = _simple_csr(edge_index.to(dev), ptr)
+    if col.numel() >= 1 << 31:
+        _refuse_csr(k, limit, rowptr.numel() - 1, col.numel())
+    G = ptr.numel() - 1
+    return rowptr, col, ptr, G, rowptr.numel() - 1, dev, back
+
+
+def _refuse_csr(k, limit, N=0, M=0):
+    """The refusals of the csr form that touch no device, stated by the library."""
+    check(lib.ugs_graphlet_census_csr(None, 0, None, None, N, M, k, limit, None, 0, None, None, None))
+
+
+def census(edge_index, ptr, k, *, limit=1 << 25, device=None, form="bitmap"):
     """The exact k-graphlet histogram of every graph of a batch: (counts int64 [G, W], failed host bool [G]), W =
     len(connected_classes(k)), counts[g, c] the number of connected k-subsets of graph g whose class id is connected_classes(k)[c].
 
@@ -452,11 +527,29 @@ def census(edge_index, ptr, k, *, limit=1 << 25, device=None):
     their errors are those of `count_graphs`.  counts is on the device of `edge_index`, or on `device`; for CPU tensors without
     `device` the work runs on the current GPU and counts comes back on the CPU.  One synchronous call on torch's current stream.
     For k <= 7 a set's class is one table load and the call is several times faster than the recipe; at k = 8 it is a canonical search
-    per set, slower than the recipe wherever the recipe can hold the rows."""
+    per set, slower than the recipe wherever the recipe can hold the rows.
+
+    form="csr" gives the same result for graphs of ANY size: the search runs over sorted adjacency lists (`_simple_csr`) instead of
+    bitmap rows, so no graph fails for its size and `set_max_vertices` plays no part.  k = 1 ... 7 (k = 8 is refused before any device
+    work); `limit` may be 1 ... 2**62; N = ptr[-1] < 2**31 and at most 2**31 - 1 adjacency entries.  A GPU `edge_index` or `ptr` is used
+    where it is, CPU tensors are uploaded once.  On graphs the default form accepts, the default is the faster one: the form is for the
+    graphs it refuses.  The law is stated at ugs_graphlet_census_csr in the same header.  A `form` other than
+    "bitmap" and "csr" is a ValueError, before anything else."""
+    _check_form(form)
     _check_k(k)
-    limit = int(limit)
-    if not 1 <= limit <= 1 << 32:
-        raise ValueError(f"limit must be 1 ... 2**32, got {limit}")
+    limit = _check_limit(limit, form)
+    if form == "csr":
+        if k == KMAX:                                   # the library states the refusal, before any device work
+            _refuse_csr(k, limit)
+        rowptr, col, pt, G, N, dev, back = _csr_inputs(edge_index, ptr, device, k, limit)
+        _graphs._select_device(dev, jobs=True)
+        keys, code_col = _census_tables(dev, k)
+        counts = torch.empty((G, keys.numel()), dtype=torch.int64, device=dev)
+        status = np.zeros(max(G, 1), dtype=np.int32)
+        check(lib.ugs_graphlet_census_csr(pt.data_ptr(), G, rowptr.data_ptr(), col.data_ptr() if col.numel() > 0 else None, N, col.numel(), k,
+                                          limit, keys.data_ptr(), keys.numel(), code_col.data_ptr(), counts.data_ptr() if G > 0 else None,
+                                          status.ctypes.data))
+        return counts.cpu() if back else counts, torch.from_numpy(status[:G] != 0)
     for t, name in ((edge_index, "edge_index"), (ptr, "ptr")):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
@@ -497,7 +590,7 @@ def _vertex_census_tables(dev, k):
     return _dev_vertex_census[at]
 
 
-def vertex_census(edge_index, ptr, k, *, limit=1 << 25, device=None):
+def vertex_census(edge_index, ptr, k, *, limit=1 << 25, device=None, form="bitmap"):
     """The exact k-graphlet degree vector of every vertex of a batch: (gdv int64 [N, O], failed host bool [G]), N = ptr[-1], O =
     len(connected_orbits(k)) = 1, 1, 3, 11, 58, 407, 4306 for k = 1 .. 7; gdv[v, c] is the number of connected k-subsets of v's graph
     that contain v and in which v's orbit id is connected_orbits(k)[c].
@@ -512,13 +605,27 @@ def vertex_census(edge_index, ptr, k, *, limit=1 << 25, device=None):
     zero.  k = 8 is refused (72 489 columns a vertex and a canonical search a set are no sensible call), before any device is touched.
     Arguments, their errors, placement (gdv on the device of `edge_index`, or on `device`; CPU tensors in and gdv back on the CPU)
     and `uniform_sampler.set_max_vertices` are as for `census`.  One synchronous call on torch's current stream (DESIGN.md section
-    19.4)."""
+    19.4).
+
+    form="csr": the same result for graphs of any size, as `census` describes it -- no size refusal, `limit` 1 ... 2**62, device
+    tensors used where they are (ugs_graphlet_vertex_census_csr in the same header)."""
+    _check_form(form)
     _check_k(k)
     if k == KMAX:                                       # the library states the refusal, before any device work
+        if form == "csr":
+            _refuse_csr(k, 1)
         check(lib.ugs_graphlet_vertex_census(None, 0, 0, None, 0, k, 1, 0, None, 0, None, None, None))
-    limit = int(limit)
-    if not 1 <= limit <= 1 << 32:
-        raise ValueError(f"limit must be 1 ... 2**32, got {limit}")
+    limit = _check_limit(limit, form)
+    if form == "csr":
+        rowptr, col, pt, G, N, dev, back = _csr_inputs(edge_index, ptr, device, k, limit)
+        _graphs._select_device(dev, jobs=True)
+        obase, O, tab = _vertex_census_tables(dev, k)
+        gdv = torch.empty((N, O), dtype=torch.int64, device=dev)
+        status = np.zeros(max(G, 1), dtype=np.int32)
+        check(lib.ugs_graphlet_vertex_census_csr(pt.data_ptr(), G, rowptr.data_ptr(), col.data_ptr() if col.numel() > 0 else None, N,
+                                                 col.numel(), k, limit, obase.numel() - 1, obase.data_ptr(), O, tab.data_ptr(),
+                                                 gdv.data_ptr() if N > 0 else None, status.ctypes.data))
+        return gdv.cpu() if back else gdv, torch.from_numpy(status[:G] != 0)
     for t, name in ((edge_index, "edge_index"), (ptr, "ptr")):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
